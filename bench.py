@@ -18,6 +18,13 @@ Workload: 64 patches x 50 years (synthetic,
 Appendix C generator, md5-checked), 512 x 512 grid, -m 400 -d 100, FP64.
 Launch:  python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts N ranks itself)
          torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, ...).  --full adds everything that takes
+runs of its own: the job-shaped timing, per-kernel durations and roofline, the
+strong-scaling blocks (N > 1) and projection (N = 1), the CPU baseline with
+its parity sample and the CLI end-to-end walls.  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (float64, finite).
 """
 from __future__ import annotations
 
@@ -228,6 +235,47 @@ def cpu_baseline(input_path, g_e, g_c, lik_gpu, ltot_gpu, tmax, tmpdir, budget_s
     return res, parity
 
 
+DUMP_CAP_BYTES = 32 << 20  # all arrays of one run together (well under 64 MB)
+DUMP_SEED = 20161014
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: each array of `arrays` (name -> ndarray: what a caller
+    of the timed path receives from its last step) as DIR/<name>.npy in
+    float64.  Each array gets an equal share of DUMP_CAP_BYTES; one over its
+    share is written as a fixed sample: the elements at share / 8 distinct
+    flat (C-order) indices drawn once from numpy's default_rng(DUMP_SEED), in
+    ascending index order, so two builds given the same arguments write the
+    same elements (and arrays of one shape the same positions).  The files
+    hold finite numbers only: a NaN or an infinity left in an array is an
+    error, not something to store."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not np.isfinite(a).all():
+            raise SystemExit(f"bench.py: output {name} holds {int((~np.isfinite(a)).sum())} non-finite values")
+        if a.nbytes > share:
+            idx = np.random.default_rng(DUMP_SEED).choice(a.size, size=share // 8, replace=False)
+            idx.sort()
+            a = a.ravel()[idx]
+        np.save(d / f"{name}.npy", a)
+
+
+def loglik_arrays(lik):
+    """The log L grid as --dump-outputs stores it.  Where the likelihood is
+    exactly 0 (e = 0, e = 1 or c = 0 on the benchmark's [0, 1] grids) the
+    engine returns log L = -inf, as the reference does, which no finite file
+    can hold: `loglik` carries the grid's smallest finite log L there, and
+    `loglik_zero` marks those points with 1.0 (0.0 elsewhere), so both which
+    points have L = 0 and every finite value can be compared between builds.
+    A NaN or +inf is left in place for dump_outputs to refuse."""
+    zero = np.isneginf(lik)
+    floor = lik[~zero].min() if not zero.all() else 0.0
+    return {"loglik": np.where(zero, floor, lik), "loglik_zero": zero.astype(np.float64)}
+
+
 def _coll_name(args):
     """The collective library a multi-rank line used: RCCL for the nccl
     backend (ROCm), else the rehearsal backend's own name."""
@@ -277,7 +325,9 @@ def bench_future(args, world, rank, dev):
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     fut.check(stream)  # no replicate overflowed the posterior look-back
-    kms = fut.time_kernel(r1 - r0, tfut, seed=seed, reps=args.steps)
+    if args.dump_outputs and rank == 0:  # the per-year counts as the last step left them (rank 0: reduced)
+        dump_outputs(args.dump_outputs, {"future_counts": counts.cpu().numpy()})
+    kms = fut.time_kernel(r1 - r0, tfut, seed=seed, reps=args.steps) if args.full else None
     if world > 1:
         t = _coll_tensor(torch.tensor([dt], dtype=torch.float64, device=dev), args)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -300,7 +350,7 @@ def bench_future(args, world, rank, dev):
     achieved = insts = None
     valu_src = None
     vf = ROOT / "profiles" / "pmc_valu_cfg5.json"
-    if vf.exists():
+    if args.full and vf.exists():
         pv = json.loads(vf.read_text())
         if pv.get("replicates") == r1 - r0 and pv.get("years") == tfut and "issue_cycles_per_launch" in pv:
             achieved = pv["issue_cycles_per_launch"] / (kms * 1e-3) / 1e9
@@ -318,19 +368,21 @@ def bench_future(args, world, rank, dev):
                    "patches": int(n), "replicates": nsim, "years": tfut,
                    "parallelism": f"replicate ranges x{world}" + (f", {_coll_name(args)} reduce" if world > 1 else ""),
                    "backend": args.backend if world > 1 else None},
-        "kernel_ms": {"k_future": kms},
-        "roofline": {"kernel": "k_future", "bound": "valu-issue",
-                     "compute_unit": "VALU issue cycles (Philox integer work), instructions priced by class",
-                     "achieved": achieved, "peak": issue_peak, "unit": "G SIMD issue cycles/s",
-                     "frac": achieved / issue_peak if achieved else None, **_pmc_traffic(5),
-                     "valu_source": valu_src,
-                     "valu_insts_rate": insts, "valu_insts_peak": valu_issue_peak,
-                     "valu_insts_frac": insts / valu_issue_peak if insts else None,
-                     "fp64_tflops": flop_per_ry * (r1 - r0) * tfut / (kms * 1e-3) / 1e12,
-                     "flop_per_replicate_year": flop_per_ry},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result.update({
+            "kernel_ms": {"k_future": kms},
+            "roofline": {"kernel": "k_future", "bound": "valu-issue",
+                         "compute_unit": "VALU issue cycles (Philox integer work), instructions priced by class",
+                         "achieved": achieved, "peak": issue_peak, "unit": "G SIMD issue cycles/s",
+                         "frac": achieved / issue_peak if achieved else None, **_pmc_traffic(5),
+                         "valu_source": valu_src,
+                         "valu_insts_rate": insts, "valu_insts_peak": valu_issue_peak,
+                         "valu_insts_frac": insts / valu_issue_peak if insts else None,
+                         "fp64_tflops": flop_per_ry * (r1 - r0) * tfut / (kms * 1e-3) / 1e12,
+                         "flop_per_replicate_year": flop_per_ry}})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         threads = _all_threads()
         t0 = time.perf_counter()
@@ -396,8 +448,15 @@ def bench_dieoff(args, world, rank, dev):
         dist.barrier()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
-    job_ms = time_job(step, gather, dev, world, reps=1)
-    kms = sc.time_kernels(out.data_ptr(), stream, reps=max(1, min(args.steps, 5)))
+    if args.dump_outputs and rank == 0:  # the last pass's likelihood grid [e][c][K] (N > 1: as gathered)
+        slabs = [out] if world == 1 else gathered
+        rows = [mdist.row_slab(r, world, s) for r in range(world)]
+        dump_outputs(args.dump_outputs, {"dieoff_lik": np.concatenate(
+            [t[: b - a].cpu().numpy() for t, (a, b) in zip(slabs, rows)])})
+    job_ms = kms = None
+    if args.full:
+        job_ms = time_job(step, gather, dev, world, reps=1)
+        kms = sc.time_kernels(out.data_ptr(), stream, reps=max(1, min(args.steps, 5)))
     torch.cuda.synchronize(dev)
     if world > 1:
         t = _coll_tensor(torch.tensor([dt], dtype=torch.float64, device=dev), args)
@@ -409,7 +468,6 @@ def bench_dieoff(args, world, rank, dev):
     # application (3^n FMAs) + n Pe passes over 2^(n-1) pairs (3 flop each)
     flop_year = 2 * 3 ** n + 3 * n * (ns // 2)
     nloc = (r1 - r0) * s * s
-    achieved = flop_year * nloc * ts / (kms["k_scn_lik"] * 1e-3) / 1e12
     result = {
         "metric": "grid-point x timestep likelihood evals/sec (MIDASPOM_dieoff 3-D grid)",
         "value": s ** 3 * (ts + tdis) * args.steps / dt,
@@ -422,16 +480,19 @@ def bench_dieoff(args, world, rank, dev):
                    "grid": [s, s, s], "patches": int(n), "states": ns,
                    "parallelism": f"e-row slabs x{world}" + (f", {_coll_name(args)} gather" if world > 1 else ""),
                    "backend": args.backend if world > 1 else None},
-        "job": {"ms": job_ms, "what": "one pass + one gather to rank 0" if world > 1 else "one pass"},
-        "kernel_ms": kms,
-        "roofline": {"kernel": "k_scn_lik", "bound": "fp64-valu", "compute_unit": "FP64 VALU",
-                     "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / FP64_PEAK_TFLOPS, **_pmc_traffic(4), "flop_per_point_year": flop_year},
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_projection:
+    if args.full:
+        achieved = flop_year * nloc * ts / (kms["k_scn_lik"] * 1e-3) / 1e12
+        result.update({
+            "job": {"ms": job_ms, "what": "one pass + one gather to rank 0" if world > 1 else "one pass"},
+            "kernel_ms": kms,
+            "roofline": {"kernel": "k_scn_lik", "bound": "fp64-valu", "compute_unit": "FP64 VALU",
+                         "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved / FP64_PEAK_TFLOPS, **_pmc_traffic(4), "flop_per_point_year": flop_year}})
+    if args.full and world == 1 and not args.no_projection:
         result["projection"] = projection_block(args, dev, stream, [4])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         rng = np.random.default_rng(0)
         lik = out[: r1 - r0].cpu().numpy()
@@ -726,7 +787,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=None,
                     help="GPUs (ranks) of this node; under a launcher it must equal WORLD_SIZE, without one "
                          "bench.py starts that many ranks itself (default 1)")
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS) + [4, 5])
     ap.add_argument("--grid4", type=int, default=256, help="config 4 grid points per axis")
@@ -739,7 +800,17 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="multi-rank plumbing only, no GPU (tests)")
     ap.add_argument("--no-projection", action="store_true",
                     help="N = 1: skip the one-GPU strong-scaling projection of configs 2, 3, 4 and 6")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: job timing, per-kernel durations and roofline, "
+                         "strong-scaling blocks / projection, CPU baseline with parity, CLI end-to-end walls "
+                         "(the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, "
+                         "finite: log L = -inf points are marked in loglik_zero.npy; a fixed seeded sample "
+                         "when a run's outputs exceed 32 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
 
     world, rank, local, spawn = resolve_world(args)
     if spawn:
@@ -758,7 +829,7 @@ def main():
     # not share the device with a live bench process either (round 3 took
     # them after the timed loop, beside this process's own context)
     e2e, tmpdir = None, Path(tempfile.mkdtemp(prefix="mdp_bench_"))
-    if world == 1 and not args.no_cpu_baseline and args.config in CONFIGS:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config in CONFIGS:
         e2e = e2e_walls(synth.write(tmpdir / "e2e_input.txt", **CONFIGS[2]["gen"]), tmpdir)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -831,6 +902,48 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last pass's log L in the device layout (N > 1: the slabs as
+        # gathered to rank 0, joined along e), before anything else runs
+        parts = [out.cpu().numpy()] if world == 1 else [x.cpu().numpy() for x in gathered]
+        dump_outputs(args.dump_outputs, loglik_arrays(np.concatenate(parts, axis=1 if args.layout == "ce" else 0)))
+    if world > 1:
+        t = _coll_tensor(torch.tensor([dt], dtype=torch.float64, device=dev), args)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    units = world * s * s * (tmax - 1) * args.steps
+    head = {
+        "metric": "grid-point x timestep likelihood evals/sec",
+        "value": units / dt,
+        "unit": "grid-point-timestep evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        # value: each rank its own s x s slab (per-GPU work fixed as N grows);
+        # N > 1 --full lines carry the fixed-grid figures of configs 2 and 3 in "strong"
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SURVEY.md Appendix C generator, md5-checked input)",
+        "config": {"workload": cfg["name"], "patches": model.n, "years": tmax, "grid": [world * s, s],
+                   "per_rank_grid": [s, s], "nvar": model.nvar, "nstates": model.nstates,
+                   "nextid": model.nextid,
+                   "parallelism": f"e-row slabs x{world}" + (f", {_coll_name(args)} gather" if world > 1 else ""),
+                   "backend": args.backend if world > 1 else None,
+                   # [c][e] is the product's layout: the CLIs (mdp_loglik_grid_layout), the torchrun
+                   # drop-in (dist.gather_colslabs) and the normaliser / writer views all use it
+                   "layout": "[c][e] (MDP_LAYOUT_CE, the drop-ins' layout)" if args.layout == "ce"
+                             else "[e][c] (reference lik[i][j] order)"},
+    }
+    if not args.full:  # the plain run: the headline figure only
+        eng.close()
+        if rank == 0:
+            print(json.dumps({**head, "cpu_baseline": None}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     weak_same = None
     if world > 1 and rank == 0:
         # the gathered (N s) x s grid against the same grid computed by this
@@ -864,10 +977,6 @@ def main():
     # rocprofv3 --kernel-trace --stats of the same command (profiles/).
     kms = eng.time_kernels(out.data_ptr(), s, stream, reps=args.steps)
     torch.cuda.synchronize(dev)
-    if world > 1:
-        t = _coll_tensor(torch.tensor([dt], dtype=torch.float64, device=dev), args)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
 
     # HBM traffic of the forward kernel per launch, from the committed
     # rocprofv3 PMC passes of this workload (scripts/gpu_pmc.sh,
@@ -877,7 +986,6 @@ def main():
     if tf.exists():
         traffic = json.loads(tf.read_text())["hbm_bytes_per_launch"]
         traffic_src = str(tf.relative_to(ROOT))
-    units = world * s * s * (tmax - 1) * args.steps
     work = eng.work(s, s)
     fact = eng.work_fact(s, s)
     info = eng.info()
@@ -897,29 +1005,7 @@ def main():
     flop_every = fact["flop"] if fused else s * s * (fact["weight_pt"] + fact["use_pt"] + fact["final_pt"])
     achieved_tf = flop_fwd / (fwd_ms * 1e-3) / 1e12
     result = {
-        "metric": "grid-point x timestep likelihood evals/sec",
-        "value": units / dt,
-        "unit": "grid-point-timestep evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        # value: each rank its own s x s slab (per-GPU work fixed as N grows);
-        # N > 1 lines carry the fixed-grid figures of configs 2 and 3 in "strong"
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (SURVEY.md Appendix C generator, md5-checked input)",
-        "config": {"workload": cfg["name"], "patches": model.n, "years": tmax, "grid": [world * s, s],
-                   "per_rank_grid": [s, s], "nvar": model.nvar, "nstates": model.nstates,
-                   "nextid": model.nextid,
-                   "parallelism": f"e-row slabs x{world}" + (f", {_coll_name(args)} gather" if world > 1 else ""),
-                   "backend": args.backend if world > 1 else None,
-                   # [c][e] is the product's layout: the CLIs (mdp_loglik_grid_layout), the torchrun
-                   # drop-in (dist.gather_cols) and the normaliser / writer views all use it
-                   "layout": "[c][e] (MDP_LAYOUT_CE, the drop-ins' layout)" if args.layout == "ce"
-                             else "[e][c] (reference lik[i][j] order)"},
+        **head,
         # the reference's job shape: ONE pass over the grid plus the single
         # gather of the slabs (main_MIDASPOM_MPI.c:361-368, 482-506), median of 3
         "job": {"ms": job_ms, "value": world * s * s * (tmax - 1) / (job_ms * 1e-3),

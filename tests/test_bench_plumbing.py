@@ -99,6 +99,77 @@ def test_coll_name():
     assert b._coll_name(argparse.Namespace(backend="gloo")) == "gloo"
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an array within the cap is written whole in float64; a
+    larger one as the elements at a fixed, ascending set of distinct flat
+    indices, the same set on every call."""
+    import numpy as np
+    b = _bench()
+    small = np.arange(12, dtype=np.int64).reshape(3, 4)
+    b.dump_outputs(tmp_path / "a", {"small": small})
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    assert b.DUMP_CAP_BYTES <= 32 << 20  # a run's arrays share it: under 64 MB in all
+    with pytest.raises(SystemExit):  # the files hold finite numbers only
+        b.dump_outputs(tmp_path / "a", {"bad": np.array([1.0, np.nan])})
+    lik = np.array([[-np.inf, -3.0], [-700.5, -np.inf]])
+    arrs = b.loglik_arrays(lik)
+    assert np.array_equal(arrs["loglik"], [[-700.5, -3.0], [-700.5, -700.5]])
+    assert np.array_equal(arrs["loglik_zero"], [[1.0, 0.0], [0.0, 1.0]])
+    assert np.isnan(b.loglik_arrays(np.array([np.nan, -1.0]))["loglik"][0])  # a NaN stays, to be refused
+    monkeypatch.setattr(b, "DUMP_CAP_BYTES", 80)  # ten float64
+    big = np.random.default_rng(5).standard_normal((7, 9))
+    b.dump_outputs(tmp_path / "a", {"big": big})
+    b.dump_outputs(tmp_path / "b", {"big": big})
+    s1, s2 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert s1.dtype == np.float64 and s1.shape == (10,) and np.array_equal(s1, s2)
+    idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(big.size, size=10, replace=False))
+    assert np.unique(idx).size == 10 and np.array_equal(s1, big.ravel()[idx])
+
+
+@pytest.mark.gpu
+def test_plain_run_headline_and_dump(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`:
+    one line with the headline keys and none of the --full blocks, K timed
+    steps, and DIR/loglik.npy equal bit for bit to the slab the same engine
+    calls give here (config 2, 512 x 512, [c][e]) wherever that is finite;
+    the L = 0 points (log L = -inf) are marked in DIR/loglik_zero.npy."""
+    import numpy as np
+    import torch
+    import midaspom_amd as mdp
+    from midaspom_amd import synth
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=240, env=_clean_env(), cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr
+    res = _json_line(r.stdout)
+    assert res["metric"] == "grid-point x timestep likelihood evals/sec"
+    assert res["unit"] == "grid-point-timestep evals/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
+    assert res["ms_per_step"] > 0
+    assert res["config"]["years"] == 50
+    assert res["value"] == pytest.approx(512 * 512 * 49 / (res["ms_per_step"] * 1e-3))
+    assert not {"job", "kernel_ms", "roofline", "projection", "parity", "strong"} & set(res)
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["loglik.npy", "loglik_zero.npy"]
+    got, zero = np.load(tmp_path / "dump" / "loglik.npy"), np.load(tmp_path / "dump" / "loglik_zero.npy")
+    assert got.dtype == zero.dtype == np.float64 and got.shape == zero.shape == (512, 512)
+    assert np.isfinite(got).all() and set(np.unique(zero)) == {0.0, 1.0}
+    model = mdp.Model.load(synth.write(tmp_path / "in.txt", **synth.CONFIG2), m=400.0, p=0.5, d=100.0)
+    g, _ = mdp.grid(512, 0.0, 1.0)
+    with mdp.Engine(model, devices=[0]) as eng:
+        eng.set_grid(g, g)
+        eng.set_layout("ce")
+        out = torch.empty((512, 512), dtype=torch.float64, device="cuda")
+        eng.run(out.data_ptr(), 512, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        ref = out.cpu().numpy()
+    # L = 0 exactly where e = 0, e = 1 or c = 0: marked, and stored as the smallest finite log L
+    edge = np.zeros((512, 512), dtype=bool)
+    edge[0, :] = edge[:, 0] = edge[:, -1] = True
+    assert np.array_equal(np.isneginf(ref), edge) and np.array_equal(zero == 1.0, edge)
+    assert np.array_equal(got[~edge], ref[~edge]) and (got[edge] == ref[~edge].min()).all()
+
+
 @pytest.mark.gpu
 def test_projection_legs_on_gpu():
     """The projection legs the default N = 1 line carries, on config 2 (both
