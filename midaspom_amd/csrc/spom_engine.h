@@ -1,0 +1,358 @@
+// midaspom_amd/csrc/spom_engine.h -- internal to the posterior engine (not
+// installed; the public ABI is include/midaspom.h).  Shared by
+//   spom_plan.cpp    host planning: options, plan tables, hipRTC sources
+//   spom_engine.hip  device set-up, launches, timing, and the kernels
+//   plan_check.cpp   the planner's stand-alone driver
+// Plain C++17: the HIP headers below give the vector and handle types only.
+#ifndef MDP_SPOM_ENGINE_H
+#define MDP_SPOM_ENGINE_H
+
+#include <hip/hip_runtime_api.h>
+#include <hip/hip_vector_types.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <mutex>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "mdp_internal.h"
+#include "spom_jit.h"
+
+// ---------------------------------------------------------------------------
+// The contract between the plan tables (spom_plan.cpp) and the kernels and
+// launchers that read them (spom_engine.hip): packed bit fields, LDS image
+// sizes, per-wave work item shapes.
+// ---------------------------------------------------------------------------
+constexpr int kBlock = 256;
+constexpr int kEPL = 2;         // k_forward: default grid points (e values) per lane
+constexpr int kMaxDeg = 24;
+constexpr uint32_t kSubPart = 16;   // k_coefs: subsets per work part
+constexpr uint32_t kOffBits = 22;   // coefficient offset bits in a use descriptor
+constexpr uint32_t kOffMask = (1u << kOffBits) - 1u;
+constexpr size_t kFwdLds = 48 * 1024;      // max coefficient block staged by k_forward_lds
+constexpr int kZTermsDev = 8;    // terms of a Z row's small-column series (zseries, z_split)
+constexpr uint32_t kQGroup = 8;  // config 3: 808 lanes, one pass of k_qrows, <= 3 shuffle levels
+constexpr uint32_t kQLanesMax = 64;  // k_qrows: lanes per entry (a power of two, <= a wave)
+constexpr int kQLevelsRows = 16;     // k_qrows: groups per lane <= 2^(kQLevelsRows - 1)
+constexpr uint32_t kMmaThreads = 1024;  // 16 waves
+constexpr uint32_t kMmaU = 2;           // K steps (of 4) per pipeline chunk: years padded to 8 entries
+constexpr uint32_t kMmaDummy = 1u << 21; // K-entry field of the descriptor row k (bits 21-28)
+// the kernel's shape for NPM states a year (padded to 16): points per block,
+// state buffer rows (>= 128, for the slices' partial sums), power-table row
+// stride (rows r and r + 1 on different LDS bank halves)
+constexpr uint32_t mma_pts(uint32_t npm) { return npm > 128 ? 32u : 64u; }
+constexpr uint32_t mma_rows(uint32_t npm) { return npm > 128 ? npm : 128u; }
+constexpr uint32_t mma_ps(uint32_t npm) { return mma_pts(npm) + 16u; }
+// K steps (of 4 entries) per pipeline chunk: 2, or 1 with 4 point tiles
+// (their 4 W operands a step leave no registers for a second step in flight)
+constexpr uint32_t mmt_u(uint32_t rt) { return rt == 4 ? 1u : 2u; }
+constexpr uint32_t kMmtMaxTiles = 64;   // column tiles a year (1 024 states)
+constexpr uint32_t mmt_pts(uint32_t rt) { return 16u * rt; }
+// power-table row stride (doubles): rows r and r + 1 on different LDS bank halves
+constexpr uint32_t mmt_ps(uint32_t rt) { return rt % 2 ? 16u * rt : 16u * rt + 16u; }
+constexpr uint32_t kHsRadix = 4;  // k_fwd_hs: patches per v Pe pass (at most; the plan's default)
+constexpr size_t kQrowsLdsMax = 160 * 1024;  // k_qrows: every table of its c values (else MDP_QGLOBAL's path)
+constexpr size_t kFusedLdsMax = 64 * 1024;  // fused forward kernel: every table of one column
+constexpr int kZTerms = kZTermsDev;  // z_split: terms of the small columns' series
+constexpr int kJitKblockTall = 512;  // threads of the reading kernel's tall variant (jit_build)
+
+// ---------------------------------------------------------------------------
+// types
+// ---------------------------------------------------------------------------
+struct DevCtx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    double *S = nullptr;
+    uint32_t *var_cols = nullptr, *row_col = nullptr;
+    uint32_t *pairA = nullptr, *pairB = nullptr, *pairOff = nullptr;
+    uint32_t *udesc = nullptr, *prog = nullptr, *pairPart0 = nullptr, *partP = nullptr, *partK0 = nullptr;
+    double *e = nullptr, *c = nullptr;
+    size_t cap_e = 0, cap_c = 0;
+    uint32_t ne = 0, nc = 0;
+    uint32_t ne_sform = 0;  // e rows of this grid on the s-form (x < y), for the work count
+    // forward kernels with several points per lane: list positions -> e rows
+    // (bit 31: a duplicate that is computed, not stored), grouped by ratio form
+    uint32_t *plist = nullptr;
+    size_t cap_plist = 0;
+    uint32_t nlist = 0, nlist_epl = 0;  // list length (a multiple of nlist_epl, its points per lane)
+    bool plist_identity = true;          // the list is 0, 1, ... (nothing uploaded; plist passed as null)
+    double *ZPV = nullptr, *R = nullptr, *out = nullptr, *gpart = nullptr;
+    size_t cap_zpv = 0, cap_r = 0, cap_out = 0, cap_gpart = 0;
+    unsigned long long *stamps[3] = {nullptr, nullptr, nullptr};  // k_zpv, k_coefs, k_forward
+    size_t cap_st[3] = {0, 0, 0};
+    size_t nst[3] = {0, 0, 0};
+    // direct path: k_zrows / k_qrows tables (zs, row-major [row][k], depends
+    // on the grid's c range)
+    double *zs = nullptr, *sv = nullptr, *Qrow = nullptr, *Zg = nullptr;
+    double *zsq = nullptr;  // zs chain-major, [row][k mod 4][k / 4] (k_qrows: a lane's chain contiguous)
+    double *zc = nullptr;   // Z-row series coefficients [row][kZTerms]
+    size_t cap_zc = 0;
+    uint2 *items = nullptr;  // per item {B | row << 24, j | (row >> 8) << 24}
+    uint2 *qslot = nullptr;  // k_qrows phase-3 lane table
+    uint32_t *qlane = nullptr;  // k_qrows phase-3 Pc slots per lane (nvar <= 8)
+    uint32_t *islot = nullptr;  // k_qrows: each item's Pc slot
+    uint32_t *itemB = nullptr, *qstart = nullptr, *qitem = nullptr;
+    size_t cap_zs = 0, cap_zsq = 0, cap_qrow = 0, cap_zg = 0;
+    uint32_t zs_len = 0;    // doubles in zs = zs_kmax * nj
+    double *coltab = nullptr;  // fused kernel's column tables (plan offsets, zs last), 1 KiB padded
+    size_t cap_coltab = 0;
+    uint32_t ct_len = 0;       // doubles
+    uint32_t zs_kmax = 0;   // padded length of the longest pruned row
+    uint32_t qrows_cb = 1;  // c values per k_qrows workgroup for this grid
+    bool qrows_attr_set = false;  // k_qrows' LDS limit raised on this device
+    double zs_cmax = -1.0;  // c bound the uploaded zs was pruned for (-1: none yet)
+    // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
+    // reading at kJitKblockTall threads (tall grids, set_grid_dev)
+    hipModule_t jit_mod[3] = {nullptr, nullptr, nullptr};
+    hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
+    // a long series: one forward kernel per chunk of years, the state vector
+    // handed over in vscr[state][c][e] (ldv e values per (state, c))
+    std::vector<hipModule_t> cmod;
+    std::vector<hipFunction_t> cfn;
+    std::vector<uint32_t *> cqidx;  // per chunk: gather indices into the Q row (null: whole row)
+    double *vscr = nullptr;
+    size_t cap_vscr = 0;
+    uint32_t ldv = 0;
+    bool fused = false;  // this grid runs the fused forward kernel (no k_qrows)
+    bool tall = false;   // this grid runs the reading kernel at kJitKblockTall threads
+    uint32_t ncu = 0;    // the device's compute units (0: not asked yet)
+    // wide path: per-chunk item factors, state-vector scratch, tables
+    double *Pg = nullptr, *V = nullptr;
+    size_t cap_pg = 0, cap_v = 0;
+    uint32_t *np_d = nullptr, *udesc_w = nullptr;
+    uint2 *mma_kt = nullptr, *mma_wplan = nullptr;
+    uint32_t *mma_kbase = nullptr, *mma_desc = nullptr, *mma_dbase = nullptr;
+    uint2 *mmt_kt = nullptr, *mmt_ktile = nullptr, *mmt_wplan = nullptr;  // k_fwd_mmt tables
+    uint32_t *mmt_cidx = nullptr;
+    // k_fwd_hs tables
+    uint32_t *hs_kt = nullptr, *hs_cidx = nullptr, *hs_pbase = nullptr, *hs_dpos = nullptr, *hs_dbase = nullptr,
+             *hs_pk = nullptr;
+    uint2 *hs_ppos = nullptr, *hs_dpk = nullptr;
+    uint4 *hs_wplan = nullptr;
+    uint4 *hs_pass = nullptr;
+    uint32_t wide_cb_items = 1, wide_cb_fwd = 1;  // c values per k_witems / k_fwd_wide launch
+    std::vector<hipEvent_t> ev;  // kNumEv events per profiled run, reused
+    std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
+    size_t ev_used = 0;          // event sets recorded since the last collect
+};
+
+struct EngineOpts {
+    std::map<std::string, std::string> kv;
+    const char *get(const char *name) const
+    {
+        auto it = kv.find(name);
+        return it == kv.end() ? nullptr : it->second.c_str();
+    }
+};
+
+struct mdp_engine {
+    uint32_t n = 0, tmax = 0, nvar = 0, nstates = 0, nextid = 0;
+    uint32_t npairs = 0, nuses = 0, ncoef = 0, npmax = 1, variant = 0;
+    uint32_t deg = 0;         // homogeneous transition degree D
+    uint32_t maxA = 0;        // max |A| over uses
+    int epl = kEPL;           // k_forward points per lane (MDP_EPL overrides: 1, 2, 4)
+    bool fwd_lds = false;     // coefficient block staged in LDS (k_forward_lds)
+    size_t fwd_lds_bytes = 0;
+    bool lds_zpv = true;      // k_coefs stages Z/PV in LDS
+    bool lds_part = true;     // k_coefs keeps subset partial sums in LDS
+    bool diag = false;        // MDP_DIAG: record phase stamps
+    bool jit = false;         // forward kernel specialised with hipRTC (spom_jit.cpp)
+    bool wide = false;        // wide path (k_witems + k_wq + k_fwd_wide): npmax > 16 or MDP_WIDE=1
+    bool qrows_xcd = true;    // k_qrows deals c ranges XCD-aware (MDP_QROWS_XCD=0: blockIdx order)
+    double wide_flops_pt = 0; // its FP64 flops per grid point
+    int jit_epl = 1;          // its grid points per lane (Q-row reading variant and chunks)
+    uint32_t jit_kblock = kBlock;  // its threads per column
+    // the fused variant's: 512 threads x 1 point per column by default (the
+    // same 512 e rows per block as 256 x 2, so the grid shape is shared): with
+    // one point per lane its 1 024-thread blocks fit 4 waves per SIMD, and the
+    // per-column prologue runs over twice the threads (config 2: -2 to -3 %)
+    int jit_epl_fused = 2;
+    uint32_t jit_kblock_fused = kBlock;
+    uint32_t jit_pro_fused = 2;
+    bool jit_shape_env = false;  // MDP_EPL / MDP_JIT_KBLOCK set: one shape for both variants
+    double jit_flops_pt = 0;  // its FP64 flops per grid point (counted by the generator)
+    size_t ldQ = 0;           // per-c Q block (doubles, even) read by the JIT kernel
+    std::vector<char> jit_code[3];  // forward kernel code objects [variant, as DevCtx::jit_fn], compiled on demand
+    std::string jit_src[3];         // their sources (a cached object the runtime refuses is rebuilt)
+    std::vector<std::string> chunk_src;
+    std::vector<MdpJitPlan> chunks;               // > 1: the series runs as chunks of years
+    std::vector<std::vector<char>> chunk_code;    // their code objects
+    bool qglobal = false;     // Q rows built by k_zrows + k_witems + k_wq (k_qrows' tables exceed the LDS)
+    int layout = MDP_LAYOUT_EC;  // mdp_engine_run's output layout (mdp_engine_set_layout)
+    double cbound = 0.0;         // the per-c tables' |c| bound at least this (mdp_engine_set_cbound)
+    int fused_mode = -1;            // MDP_FUSED: -1 auto, 0, 1
+    MdpJitPlan jit_plan;
+    // direct path (jit): k_qrows computes Pc[j][b] for the needed (j, b)
+    // items, the forward kernel assembles Q from them
+    uint32_t nj = 0, nitems = 0, ncoef_d = 0;
+    size_t ldP = 0;
+    std::vector<uint32_t> cj_bits, cj_item0, itemB, qstart, qitem, udesc_d, var_cols;
+    std::vector<uint32_t> itemRow;  // row (j slot) of each item
+    std::vector<uint2> qslot;       // k_qrows phase-3 lanes (build_direct_plan)
+    std::vector<uint32_t> qlane;    // their groups' Pc slots, kQGroup a lane (nvar <= 8)
+    std::vector<uint32_t> islot;    // k_qrows: each item's Pc slot (slots 0-15: zeros)
+    uint32_t npl_slots = 0;         // k_qrows: Pc slots per c value
+    uint32_t slot_conflicts = 0;    // k_qrows: extra gather cycles its slot colouring leaves (per c pair)
+    uint32_t slot_store_conflicts = 0;  // and extra store-group conflicts
+    // k_fwd_mma (wide years on the matrix cores): per year t its K entries
+    // (k | |A_k| << 8 | m << 16 | valid << 31, padded to 4) from kbase[t],
+    // and the Q-row slot of each (K entry, new state l) from gbase[t]
+    bool mma = false;
+    uint32_t mma_npm = 0;
+    std::vector<uint2> mma_kt;  // per year its K entries: LDS byte offsets of the W rows, m, k
+    std::vector<uint2> mma_wplan;  // per (year, wave) its work item (chunk range, column tile, slice)
+    std::vector<uint32_t> mma_kbase, mma_desc, mma_dbase;
+    uint32_t mma_ktmax = 16;
+    // k_fwd_mmt (round 6, the default matrix-core forward: years of up to
+    // 1 024 states): RT point tiles a block, per (year, tile) K lists, per
+    // (year, wave) work items (build_mmt_plan)
+    bool mmt = false;
+    uint32_t mmt_rt = 0, mmt_rows = 0;
+    std::vector<uint2> mmt_kt, mmt_ktile, mmt_wplan;
+    std::vector<uint32_t> mmt_cidx;
+    double mmt_flops_pt = 0;  // executed MFMA flops per grid point (padding included)
+    // k_fwd_hs (round 6, through the hidden states: build_hs_plan): 2^hs_nb
+    // cube positions, RT point tiles; per (year, tile) K lists of hidden
+    // states and their item offsets, per year butterfly passes, the new
+    // states' cube positions in tile order and free 16-row park blocks
+    bool hs = false;
+    uint32_t hs_rt = 0, hs_nb = 0, hs_nw = 16;
+    uint32_t hs_probe = 0;  // MDP_HS_PROBE (timing probes only, wrong results): 1 skips v Pe, 2 U Pc
+    std::vector<uint32_t> hs_kt, hs_cidx, hs_pbase, hs_dpos, hs_dbase, hs_pk;
+    std::vector<uint2> hs_ppos, hs_dpk;
+    std::vector<uint4> hs_wplan;
+    std::vector<uint4> hs_pass;
+    double hs_flops_pt = 0, hs_mfma_pt = 0;  // FP64 flops per grid point (padding included), of them MFMA
+    std::vector<uint32_t> ystate;  // each year's states (short_state bits), year_off order
+    uint32_t qslot_lglmax = 0;      // log2 of the widest lane segment
+    std::vector<uint8_t> isvar;
+    std::vector<double> Sj;  // [nj][n] colonisation sums of every column for each needed j
+    std::string jit_log;
+    size_t coef_lds = 0;      // k_coefs dynamic LDS bytes
+    size_t lds_max = 160 * 1024;  // the device's LDS per workgroup (mdp_plan_engine's argument; 160 KiB on gfx950)
+    double prior0 = 1.0;
+    std::vector<uint32_t> np, pairA, pairB, pairOff, use_pair, prog, udesc, pairPart0, partP, partK0;
+    std::vector<DevCtx> devs;
+    EngineOpts opts;          // mdp_engine_create_opts (variant selection; no environment reads)
+    mutable std::set<std::string, std::less<>> launched;  // kernel instantiations launched so far (mdp_engine_launched)
+    mutable std::mutex launched_mu;                         // engines may be driven from several host threads
+    int profiling = 0;
+    double last_ms[3] = {0, 0, 0};  // mean per run over the last collected runs
+    int nlast = 0;
+    uint64_t runs_collected = 0;
+};
+
+// The forward kernels' output strides: log L of point (ie, ic) at
+// out[ie * se + ic * sc] -- [e][c] rows (se = ld, sc = 1) or [c][e] columns
+// (se = 1, sc = ld); every forward kernel takes both.  Passed explicitly down
+// every launch path: only mdp_engine_run / mdp_engine_time_kernels honour the
+// engine's layout (mdp_engine_set_layout); mdp_loglik_grid always fills its
+// device slab in [e][c] (its host contract).
+struct OutStrides {
+    uint32_t se, sc;
+};
+inline OutStrides layout_strides(int layout, uint32_t ld)
+{
+    return layout == MDP_LAYOUT_CE ? OutStrides{1u, ld} : OutStrides{ld, 1u};
+}
+
+// ---------------------------------------------------------------------------
+// LDS and table sizes both sides compute (inline: the run path calls them)
+// ---------------------------------------------------------------------------
+// per-c coefficient stride: every forward use (deg+1 coefficients padded to
+// an even count) plus two zero transitions of prefetch padding
+inline size_t rsp_of(const mdp_engine *eng) { return (eng->deg + 2) & ~1u; }
+inline size_t ldR_of(const mdp_engine *eng) { return ((size_t)eng->nuses + 2) * rsp_of(eng); }
+
+// k_fwd_mma: two state buffers and the power tables of the block's points,
+// and (LDS staging) three years' K entries
+inline size_t mma_lds(const mdp_engine *eng)
+{
+    const uint32_t npm = eng->mma_npm;
+    return (2 * (size_t)mma_rows(npm) * mma_pts(npm) + 2 * ((size_t)eng->maxA + 1) * mma_ps(npm)) * sizeof(double) +
+           0;
+}
+
+// k_fwd_mmt: the state buffer and the power tables of the block's points
+// k_fwd_mmt's shapes by the largest year: RT point tiles, state rows, two buffers
+struct MmtShape {
+    uint32_t rt, rows;
+    bool db;
+};
+// (measured, profiles/r06/wide: years of up to 128 states run 25 % faster on
+// <4, 128, 2buf> than on <2, 256, 1buf>; a 256-state problem 6 % faster on
+// one buffer than on <2, 256, 2buf>)
+inline MmtShape mmt_shape(const mdp_engine *eng)
+{
+    const uint32_t npmax = eng->npmax;
+    if (npmax <= 128) return {4u, 128u, true};
+    if (npmax <= 256) return {2u, 256u, false};
+    if (npmax <= 512) return {2u, 512u, false};
+    return {1u, 1024u, false};
+}
+
+inline size_t mmt_lds(const mdp_engine *eng)
+{
+    const MmtShape sh = mmt_shape(eng);
+    return ((sh.db ? 2 : 1) * (size_t)sh.rows * mmt_pts(sh.rt) + 2 * ((size_t)eng->maxA + 1) * mmt_ps(sh.rt)) *
+           sizeof(double);
+}
+
+// k_fwd_hs: the cube of the block's points (128 KiB for each shape)
+inline size_t hs_lds(const mdp_engine *eng)
+{
+    return (((size_t)1 << eng->hs_nb) + eng->hs_nb + 1) * mmt_pts(eng->hs_rt) * sizeof(double);  // + y^k table
+}
+
+// k_qrows LDS for cb c values per workgroup: Z, var-column S, Pc, Q CSR
+inline size_t qrows_lds(const mdp_engine *eng, uint32_t cb)
+{
+    const size_t nv = eng->nvar <= 8 ? 8 : eng->nvar <= 16 ? 16 : 24;  // k_qrows NV
+    return ((((size_t)cb * eng->nj + 1) & ~(size_t)1) + (size_t)eng->nj * (cb * nv + 2) + (size_t)cb * eng->npl_slots) *
+               sizeof(double) +
+           ((size_t)eng->ncoef_d + 1 + eng->qitem.size()) * sizeof(uint32_t);  // (items stay in registers)
+}
+
+// The fused forward kernel keeps its column's tables (ct_len doubles,
+// dynamic LDS), Z, Pc and Q in LDS.
+inline size_t fused_lds(const mdp_engine *eng, size_t ct_len)
+{
+    const size_t fc = (size_t)eng->jit_plan.fused_cols;
+    return (ct_len + 2 + fc * (eng->nj + eng->nitems + 2 * eng->ldQ)) * sizeof(double);  // + staging scratch
+}
+
+// k_fwd_wide: per-lane x^r, y^r tables, r <= maxA
+inline size_t wide_lds(const mdp_engine *eng) { return 2 * ((size_t)eng->maxA + 1) * kBlock * sizeof(double); }
+
+// ---------------------------------------------------------------------------
+// planner entry points (spom_plan.cpp)
+// ---------------------------------------------------------------------------
+
+// diag_build: the measurement-only names (MDP_DIAG, ...) are accepted
+int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build);
+
+// How far mdp_plan_engine goes with hipRTC.
+enum class MdpPlanMode {
+    Compile,       // compile the forward kernel the first grid most likely runs
+    OfflineCheck,  // MDP_JIT_CHECK=1 without a device: compile every kernel, then MDP_ENODEV
+    // no hipRTC: the specialised kernel is taken to compile, so eng->jit is
+    // set with no code object behind it.  For plan_check only: an engine
+    // planned this way must never reach init_device or a launch.
+    TablesOnly
+};
+// Plan the engine for problem p (eng->opts parsed): the generic plan, then the
+// direct / chunked / vlds / wide one the problem and the options select, with
+// lds_max the device's LDS per workgroup (160 KiB on gfx950).  jit_t (may be
+// null) receives the steady-clock seconds around the hipRTC step.
+int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t);
+
+void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
+             std::vector<uint32_t> *cols = nullptr);
+std::string jit_source(mdp_engine *eng, int variant);  // the forward kernel's source (no hipRTC)
+int jit_build(mdp_engine *eng, int variant);
+int jit_build_chunks(mdp_engine *eng);
+
+#endif

@@ -1,32 +1,29 @@
 // midaspom_amd/csrc/spom_engine.hip -- MI355X (gfx950) posterior-grid
-// likelihood engine for the stochastic patch occupancy model.
+// likelihood engine for the stochastic patch occupancy model: the device unit.
 //
-// Replaces the reference hot loop /root/reference/sources/main_MIDASPOM.c:341-395
-// (colonisation pressure :350-358, compPePc :18-50, P = Pe*Pc dgemm :363,
-// forward propagation :368-384, prior sum + log :386-392).
+// Files of the engine:
+//   spom_engine.h    constants, types and size helpers shared by the planner,
+//                    the kernels and the launchers
+//   spom_plan.cpp    host planning: options, the plan tables the kernels
+//                    index, the hipRTC sources, the host-only C ABI functions;
+//                    no HIP runtime call
+//   spom_engine.hip  (this file) the kernels, device set-up (uploads,
+//                    set_grid_dev), the launch paths, run_dev, timing and the
+//                    rest of the C ABI
+//   spom_jit.cpp     generator and hipRTC cache of the specialised forward
 //
-// Factorisation (DESIGN.md §3).  For observed short states a -> b with bit
-// sets A, B and hidden intermediate state j (extinction first, then
-// colonisation) the reference forms P[a][b] = sum_j Pe[a][j] Pc[j][b] with
-//   Pe[a][j] = [j <= A] x^{|A|-|j|} y^{|j|}        (x = min(e,1), y = 1-x)
-//   Pc[j][b] = [j <= B] prod_{k : j_k = 0} (B_k ? pC_jk : 1-pC_jk),
-//   pC_jk    = min(1, c * S[j][k]),   S = grid-invariant dispersal sums.
-// Pe depends on e only through |j| and Pc on c only, so
-//   P[a][b](e,c) = sum_{m=0}^{|A&B|} x^{|A|-m} y^m Q_ab[m](c),
-//   Q_ab[m](c)   = sum_{j <= A&B, |j| = m} Pc[j][b](c).
-// Multiplying by (x+y)^{D-|A|} = 1 makes every transition a homogeneous
-// polynomial of ONE degree D (>= every |A|) with non-negative coefficients
-//   P[a][b](e,c) = sum_{r=0}^{D} R_ab[r](c) W_r(e),  W_r = x^{D-r} y^r,
-//   R_ab[r]      = sum_m Q_ab[m] C(D-|A|, r-m),
-// so a transition costs D+1 FMAs against per-point weights held in VGPRs and
-// per-c coefficients that are wave-uniform (scalar loads, no descriptors).
-//
-// Kernels (per run over an ne x nc grid):
-//   k_zpv      [c][j]     Z = prod_{always-zero k} (1-pC_jk), PV_b = pC_j,var(b)
-//   k_coefs    one WG / c Q (subset sums, LDS) -> R in forward-use order
-//   k_forward  one lane / (e,c) point x EPL: forward recursion over the years,
-//              c wave-uniform, R streamed through the scalar cache.
-// Once per engine: k_colsum builds S.
+// Paths (mdp_plan_engine picks one per engine; DESIGN.md sections 3-4):
+//   generic  any problem (MDP_JIT=0, or hipRTC failed): k_zpv -> k_coefs ->
+//            k_forward(_lds), transitions as degree-D polynomials in e;
+//            tables from build_plan.
+//   direct   years of at most 16 states: k_zrows -> k_qrows -> the forward
+//            kernel specialised to the problem, or its fused variant alone;
+//            long series as chunks of years (plan_chunks), years of 17-64
+//            states with their state vectors in LDS; tables from
+//            build_direct_plan and z_split.
+//   wide     larger years: k_zrows -> k_witems (+ k_wq) -> k_fwd_hs
+//            (build_hs_plan), k_fwd_mmt (build_mmt_plan), k_fwd_mma or
+//            k_fwd_wide (build_wide_plan); work items from plan_waves.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -37,41 +34,26 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <new>
-#include <set>
 #include <string>
-#include <thread>
-#include <unordered_map>
 #include <vector>
 
-#include "mdp_internal.h"
-#include "spom_jit.h"
+#include "spom_engine.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kZpvJ = 64;       // k_zpv: hidden states per workgroup
 constexpr int kZpvSlices = 4;   // k_zpv: waves splitting the zero-column product
 constexpr int kZpvCT = 2;       // k_zpv: c values per thread
 constexpr int kZpvUnroll = 8;   // k_zpv: S loads in flight per lane
-constexpr int kEPL = 2;         // k_forward: default grid points (e values) per lane
-constexpr int kMaxDeg = 24;
 constexpr int kStampSlots = 8;      // diagnostic stamps per workgroup
-constexpr uint32_t kSubPart = 16;   // k_coefs: subsets per work part
-constexpr uint32_t kOffBits = 22;   // coefficient offset bits in a use descriptor
-constexpr uint32_t kOffMask = (1u << kOffBits) - 1u;
 constexpr unsigned kWaitLgkm0 = 0xC07F;  // s_waitcnt lgkmcnt(0), other counters untouched
-constexpr size_t kLdsBudget = 120 * 1024;  // dynamic LDS of k_coefs
-constexpr size_t kFwdLds = 48 * 1024;      // max coefficient block staged by k_forward_lds
-constexpr uint32_t kJitMaxUses = 2048;     // uses of one forward kernel; longer series run in chunks
-constexpr uint32_t kJitChunkUses = 1024;   // target uses per chunk (hipRTC time grows faster than the code)
-constexpr uint32_t kVldsMaxStates = 64;     // wide years the specialised kernel takes (states in LDS;
-                                            // 128-state years compile to MB-sized programs)
-constexpr uint32_t kVldsMaxUses = 16384;    // ... up to this many uses (hipRTC time)
-constexpr size_t kJitMaxLds = 64 * 1024;   // Pc row + Q block of the direct path
-constexpr size_t kJitChunkQ = kJitMaxLds / sizeof(double) - 2;  // gathered coefficients per chunk
+#ifdef MDP_DIAG_BUILD
+constexpr bool kDiagBuild = true;  // the measurement-only options are accepted (parse_engine_opts)
+#else
+constexpr bool kDiagBuild = false;
+#endif
 
 __constant__ double c_binom[kMaxDeg + 1][kMaxDeg + 1];
 
@@ -116,6 +98,33 @@ thread_local KernelEvents t_kev;
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
+
+// The generic path replaces the reference's hot loop, main_MIDASPOM.c:341-395
+// (colonisation pressure :350-358, compPePc :18-50, P = Pe*Pc dgemm :363,
+// forward propagation :368-384, prior sum + log :386-392).
+//
+// Factorisation (DESIGN.md §3).  For observed short states a -> b with bit
+// sets A, B and hidden intermediate state j (extinction first, then
+// colonisation) the reference forms P[a][b] = sum_j Pe[a][j] Pc[j][b] with
+//   Pe[a][j] = [j <= A] x^{|A|-|j|} y^{|j|}        (x = min(e,1), y = 1-x)
+//   Pc[j][b] = [j <= B] prod_{k : j_k = 0} (B_k ? pC_jk : 1-pC_jk),
+//   pC_jk    = min(1, c * S[j][k]),   S = grid-invariant dispersal sums.
+// Pe depends on e only through |j| and Pc on c only, so
+//   P[a][b](e,c) = sum_{m=0}^{|A&B|} x^{|A|-m} y^m Q_ab[m](c),
+//   Q_ab[m](c)   = sum_{j <= A&B, |j| = m} Pc[j][b](c).
+// Multiplying by (x+y)^{D-|A|} = 1 makes every transition a homogeneous
+// polynomial of ONE degree D (>= every |A|) with non-negative coefficients
+//   P[a][b](e,c) = sum_{r=0}^{D} R_ab[r](c) W_r(e),  W_r = x^{D-r} y^r,
+//   R_ab[r]      = sum_m Q_ab[m] C(D-|A|, r-m),
+// so a transition costs D+1 FMAs against per-point weights held in VGPRs and
+// per-c coefficients that are wave-uniform (scalar loads, no descriptors).
+//
+// Kernels (per run over an ne x nc grid):
+//   k_zpv      [c][j]     Z = prod_{always-zero k} (1-pC_jk), PV_b = pC_j,var(b)
+//   k_coefs    one WG / c Q (subset sums, LDS) -> R in forward-use order
+//   k_forward  one lane / (e,c) point x EPL: forward recursion over the years,
+//              c wave-uniform, R streamed through the scalar cache.
+// Once per engine: k_colsum builds S.
 
 // S2[r][j] = S[col(r)][j]: the colonisation sum of column k = col(r) for
 // hidden state j, i.e. the sum over set bits of j (ascending variable column
@@ -231,7 +240,6 @@ __global__ __launch_bounds__(kBlock) void k_zpv(
 // Product of a Z row's small-column factors: exp(-c (P1 + c (P2/2 + ... +
 // c P8/8))), Horner from the top (upload_qrows_tables; the fused kernel
 // evaluates the same expression)
-constexpr int kZTermsDev = 8;
 __device__ __forceinline__ double zseries(const double (&p)[kZTermsDev], double c)
 {
     double q = p[kZTermsDev - 1];
@@ -350,10 +358,7 @@ __device__ __forceinline__ double quad_dpp(double v)
     return __hiloint2double(hi, lo);
 }
 
-constexpr uint32_t kQGroup = 8;  // config 3: 808 lanes, one pass of k_qrows, <= 3 shuffle levels
 constexpr int kQLevels = 24;
-constexpr uint32_t kQLanesMax = 64;  // k_qrows: lanes per entry (a power of two, <= a wave)
-constexpr int kQLevelsRows = 16;     // k_qrows: groups per lane <= 2^(kQLevelsRows - 1)
 
 constexpr int kQrowsBlock = 1024;
 constexpr uint32_t kQrowsMaxC = 4;
@@ -1177,8 +1182,9 @@ __global__ __launch_bounds__(kBlock) void k_forward_lds(
 // Pg[cl * ldp + it] = Pc[j][B] of item `it` at c = cvals[c0 + cl] (ldp: nitems,
 // or nitems + 1 for k_fwd_hs, whose rows end in a zero slot): Z_row(c) times the
 // var-column factors f_b = B_b ? pC_b : 1 - pC_b, pC_b = min(1, c S[j][b])
-// (1.0 for the columns of j, marked -1 in sv), combined in k_qrows' pairwise
-// tree over NV slots -- the same bits k_qrows produces.
+// (1.0 for the columns of j, marked +inf in sv: fmin(c inf, 1) = 1.0),
+// combined in k_qrows' pairwise tree over NV slots -- the same bits k_qrows
+// produces.
 template <int NV>
 __global__ __launch_bounds__(kBlock) void k_witems(const double *__restrict__ cvals, uint32_t nc, uint32_t c0,
                                                    uint32_t nvar, const double *__restrict__ Zg,
@@ -1274,15 +1280,6 @@ __global__ __launch_bounds__(kBlock) void k_wq(uint32_t c0, uint32_t nitems, con
 // transition descriptors two and the C gathers one; the loop body is
 // unrolled four times so the slots are fixed.  The products sum in another
 // order than k_fwd_wide's (positive terms: ~1e-15 relative).
-constexpr uint32_t kMmaThreads = 1024;  // 16 waves
-constexpr uint32_t kMmaU = 2;           // K steps (of 4) per pipeline chunk: years padded to 8 entries
-constexpr uint32_t kMmaDummy = 1u << 21; // K-entry field of the descriptor row k (bits 21-28)
-// the kernel's shape for NPM states a year (padded to 16): points per block,
-// state buffer rows (>= 128, for the slices' partial sums), power-table row
-// stride (rows r and r + 1 on different LDS bank halves)
-constexpr uint32_t mma_pts(uint32_t npm) { return npm > 128 ? 32u : 64u; }
-constexpr uint32_t mma_rows(uint32_t npm) { return npm > 128 ? npm : 128u; }
-constexpr uint32_t mma_ps(uint32_t npm) { return mma_pts(npm) + 16u; }
 typedef double mdp_d4 __attribute__((ext_vector_type(4)));
 template <int NPM>  // states per year, padded (64, 128 or 256)
 __global__ __launch_bounds__(kMmaThreads) void k_fwd_mma(
@@ -1518,13 +1515,6 @@ __global__ __launch_bounds__(kMmaThreads) void k_fwd_mma(
 // Workgroups are dealt XCD-aware (the point blocks of one column on one XCD,
 // so the column's Q row is gathered from that XCD's L2).  The products sum
 // in another order than k_fwd_wide's (positive terms: ~1e-15 relative).
-// K steps (of 4 entries) per pipeline chunk: 2, or 1 with 4 point tiles
-// (their 4 W operands a step leave no registers for a second step in flight)
-constexpr uint32_t mmt_u(uint32_t rt) { return rt == 4 ? 1u : 2u; }
-constexpr uint32_t kMmtMaxTiles = 64;   // column tiles a year (1 024 states)
-constexpr uint32_t mmt_pts(uint32_t rt) { return 16u * rt; }
-// power-table row stride (doubles): rows r and r + 1 on different LDS bank halves
-constexpr uint32_t mmt_ps(uint32_t rt) { return rt % 2 ? 16u * rt : 16u * rt + 16u; }
 // the instantiations (RT point tiles of 16, ROWS state rows, two buffers or
 // one): <4, 128, true> years of up to 128 states, <2, 256, false> 256,
 // <2, 512, false> 512, <1, 1 024, false> 1 024 (mmt_shape)
@@ -1792,7 +1782,6 @@ __global__ __launch_bounds__(kMmaThreads) void k_fwd_mmt(
 // semantics: ones at year 0's states; L = prior0 x the sum over the last
 // year's states.  Sums reordered against the reference's (positive terms
 // for e in [0, 1]: ~1e-15 relative).
-constexpr uint32_t kHsRadix = 4;  // k_fwd_hs: patches per v Pe pass (at most; the plan's default)
 constexpr uint32_t kHsPre = 4;    // k_fwd_hs: v Pe passes a year whose descriptors are loaded up front
 // diag build, MDP_HS_PROBE bit 2: workgroup 0's wave 0 stamps the shader
 // clock at each phase of each year into out[] (results not stored)
@@ -2233,263 +2222,6 @@ const char *const kKernelNames[3][3] = {{"k_zpv", "k_coefs", "k_forward"},
                                         {"k_zrows", "k_qrows", "k_forward"},
                                         {"k_zrows", "k_witems+k_wq", "k_fwd_wide"}};
 
-struct DevCtx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    double *S = nullptr;
-    uint32_t *var_cols = nullptr, *row_col = nullptr;
-    uint32_t *pairA = nullptr, *pairB = nullptr, *pairOff = nullptr;
-    uint32_t *udesc = nullptr, *prog = nullptr, *pairPart0 = nullptr, *partP = nullptr, *partK0 = nullptr;
-    double *e = nullptr, *c = nullptr;
-    size_t cap_e = 0, cap_c = 0;
-    uint32_t ne = 0, nc = 0;
-    uint32_t ne_sform = 0;  // e rows of this grid on the s-form (x < y), for the work count
-    // forward kernels with several points per lane: list positions -> e rows
-    // (bit 31: a duplicate that is computed, not stored), grouped by ratio form
-    uint32_t *plist = nullptr;
-    size_t cap_plist = 0;
-    uint32_t nlist = 0, nlist_epl = 0;  // list length (a multiple of nlist_epl, its points per lane)
-    bool plist_identity = true;          // the list is 0, 1, ... (nothing uploaded; plist passed as null)
-    double *ZPV = nullptr, *R = nullptr, *out = nullptr, *gpart = nullptr;
-    size_t cap_zpv = 0, cap_r = 0, cap_out = 0, cap_gpart = 0;
-    unsigned long long *stamps[3] = {nullptr, nullptr, nullptr};  // k_zpv, k_coefs, k_forward
-    size_t cap_st[3] = {0, 0, 0};
-    size_t nst[3] = {0, 0, 0};
-    // direct path: k_zrows / k_qrows tables (zs, row-major [row][k], depends
-    // on the grid's c range)
-    double *zs = nullptr, *sv = nullptr, *Qrow = nullptr, *Zg = nullptr;
-    double *zsq = nullptr;  // zs chain-major, [row][k mod 4][k / 4] (k_qrows: a lane's chain contiguous)
-    double *zc = nullptr;   // Z-row series coefficients [row][kZTerms]
-    size_t cap_zc = 0;
-    uint2 *items = nullptr;  // per item {B | row << 24, j | (row >> 8) << 24}
-    uint2 *qslot = nullptr;  // k_qrows phase-3 lane table
-    uint32_t *qlane = nullptr;  // k_qrows phase-3 Pc slots per lane (nvar <= 8)
-    uint32_t *islot = nullptr;  // k_qrows: each item's Pc slot
-    uint32_t *itemB = nullptr, *qstart = nullptr, *qitem = nullptr;
-    size_t cap_zs = 0, cap_zsq = 0, cap_qrow = 0, cap_zg = 0;
-    uint32_t zs_len = 0;    // doubles in zs = zs_kmax * nj
-    double *coltab = nullptr;  // fused kernel's column tables (plan offsets, zs last), 1 KiB padded
-    size_t cap_coltab = 0;
-    uint32_t ct_len = 0;       // doubles
-    uint32_t zs_kmax = 0;   // padded length of the longest pruned row
-    uint32_t qrows_cb = 1;  // c values per k_qrows workgroup for this grid
-    bool qrows_attr_set = false;  // k_qrows' LDS limit raised on this device
-    double zs_cmax = -1.0;  // c bound the uploaded zs was pruned for (-1: none yet)
-    // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
-    // reading at kJitKblockTall threads (tall grids, set_grid_dev)
-    hipModule_t jit_mod[3] = {nullptr, nullptr, nullptr};
-    hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
-    // a long series: one forward kernel per chunk of years, the state vector
-    // handed over in vscr[state][c][e] (ldv e values per (state, c))
-    std::vector<hipModule_t> cmod;
-    std::vector<hipFunction_t> cfn;
-    std::vector<uint32_t *> cqidx;  // per chunk: gather indices into the Q row (null: whole row)
-    double *vscr = nullptr;
-    size_t cap_vscr = 0;
-    uint32_t ldv = 0;
-    bool fused = false;  // this grid runs the fused forward kernel (no k_qrows)
-    bool tall = false;   // this grid runs the reading kernel at kJitKblockTall threads
-    uint32_t ncu = 0;    // the device's compute units (0: not asked yet)
-    // wide path: per-chunk item factors, state-vector scratch, tables
-    double *Pg = nullptr, *V = nullptr;
-    size_t cap_pg = 0, cap_v = 0;
-    uint32_t *np_d = nullptr, *udesc_w = nullptr;
-    uint2 *mma_kt = nullptr, *mma_wplan = nullptr;
-    uint32_t *mma_kbase = nullptr, *mma_desc = nullptr, *mma_dbase = nullptr;
-    uint2 *mmt_kt = nullptr, *mmt_ktile = nullptr, *mmt_wplan = nullptr;  // k_fwd_mmt tables
-    uint32_t *mmt_cidx = nullptr;
-    // k_fwd_hs tables
-    uint32_t *hs_kt = nullptr, *hs_cidx = nullptr, *hs_pbase = nullptr, *hs_dpos = nullptr, *hs_dbase = nullptr,
-             *hs_pk = nullptr;
-    uint2 *hs_ppos = nullptr, *hs_dpk = nullptr;
-    uint4 *hs_wplan = nullptr;
-    uint4 *hs_pass = nullptr;
-    uint32_t wide_cb_items = 1, wide_cb_fwd = 1;  // c values per k_witems / k_fwd_wide launch
-    std::vector<hipEvent_t> ev;  // kNumEv events per profiled run, reused
-    std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
-    size_t ev_used = 0;          // event sets recorded since the last collect
-};
-
-}  // namespace
-
-// Engine options (ABI 7, mdp_engine_create_opts): "NAME=VALUE" pairs
-// separated by ';', ',' or white space.  They select among the engine's
-// parity-tested kernel variants; the defaults are the
-// measured best.  The library reads no tuning knob from the environment:
-// mdp_engine_create is mdp_engine_create_opts with no options.  Names
-// marked measurement-only exist in the diag build alone (-DMDP_DIAG_BUILD,
-// libmidaspom_diag.so, used by scripts/): MDP_JIT_HACK's kernels do not
-// store correct results, and phase stamps / occupancy hints are profiling
-// aids.  An unknown name, or a measurement-only name in the default
-// build, is MDP_EINVAL.
-namespace {
-const char *const kEngineOptNames[] = {
-    "MDP_JIT", "MDP_FUSED", "MDP_FUSED_COLS", "MDP_EPL", "MDP_JIT_SLOTS", "MDP_JIT_WINDOW", "MDP_JIT_XCD",
-    "MDP_JIT_EFAST", "MDP_QROWS_XCD", "MDP_FWD", "MDP_WIDE", "MDP_VSPLIT", "MDP_VLDS_EPL", "MDP_VLDS_MAXUSES",
-    "MDP_JIT_CHUNK", "MDP_JIT_GATHER", "MDP_QGLOBAL", "MDP_FAST_LOG", "MDP_JIT_KBLOCK", "MDP_WIDE_CB",
-    "MDP_JIT_CHECK", "MDP_JIT_DUMP", "MDP_JIT_THREADS", "MDP_JIT_VERBOSE", "MDP_JIT_SPLIT", "MDP_JIT_ROT",
-    "MDP_WIDE_MMA", "MDP_HS_RADIX", "MDP_HS_WAVES"};
-const char *const kDiagOptNames[] = {"MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE"};
-#ifdef MDP_DIAG_BUILD
-constexpr bool kDiagBuild = true;
-#else
-constexpr bool kDiagBuild = false;
-#endif
-}  // namespace
-
-struct EngineOpts {
-    std::map<std::string, std::string> kv;
-    const char *get(const char *name) const
-    {
-        auto it = kv.find(name);
-        return it == kv.end() ? nullptr : it->second.c_str();
-    }
-};
-
-static int parse_engine_opts(const char *s, EngineOpts &o)
-{
-    o.kv.clear();
-    if (!s) return MDP_OK;
-    std::string cur;
-    auto flush = [&]() -> int {
-        if (cur.empty()) return MDP_OK;
-        const size_t eq = cur.find('=');
-        const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string("1") : cur.substr(eq + 1);
-        cur.clear();
-        bool known = false, diag = false;
-        for (const char *n : kEngineOptNames) known |= k == n;
-        for (const char *n : kDiagOptNames) diag |= k == n;
-        if (diag && !kDiagBuild)
-            return mdp_set_error(MDP_EINVAL, "option %s is measurement-only (libmidaspom_diag.so, -DMDP_DIAG_BUILD)",
-                                 k.c_str());
-        if (!known && !diag) return mdp_set_error(MDP_EINVAL, "unknown engine option '%s'", k.c_str());
-        o.kv[k] = v;
-        return MDP_OK;
-    };
-    for (const char *c = s;; ++c) {
-        if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
-            const int rc = flush();
-            if (rc) return rc;
-            if (*c == 0) break;
-        } else {
-            cur += *c;
-        }
-    }
-    return MDP_OK;
-}
-
-struct mdp_engine {
-    uint32_t n = 0, tmax = 0, nvar = 0, nstates = 0, nextid = 0;
-    uint32_t npairs = 0, nuses = 0, ncoef = 0, npmax = 1, variant = 0;
-    uint32_t deg = 0;         // homogeneous transition degree D
-    uint32_t maxA = 0;        // max |A| over uses
-    int epl = kEPL;           // k_forward points per lane (MDP_EPL overrides: 1, 2, 4)
-    bool fwd_lds = false;     // coefficient block staged in LDS (k_forward_lds)
-    size_t fwd_lds_bytes = 0;
-    bool lds_zpv = true;      // k_coefs stages Z/PV in LDS
-    bool lds_part = true;     // k_coefs keeps subset partial sums in LDS
-    bool diag = false;        // MDP_DIAG: record phase stamps
-    bool jit = false;         // forward kernel specialised with hipRTC (spom_jit.cpp)
-    bool wide = false;        // wide path (k_witems + k_wq + k_fwd_wide): npmax > 16 or MDP_WIDE=1
-    bool qrows_xcd = true;    // k_qrows deals c ranges XCD-aware (MDP_QROWS_XCD=0: blockIdx order)
-    double wide_flops_pt = 0; // its FP64 flops per grid point
-    int jit_epl = 1;          // its grid points per lane (Q-row reading variant and chunks)
-    uint32_t jit_kblock = kBlock;  // its threads per column
-    // the fused variant's: 512 threads x 1 point per column by default (the
-    // same 512 e rows per block as 256 x 2, so the grid shape is shared): with
-    // one point per lane its 1 024-thread blocks fit 4 waves per SIMD, and the
-    // per-column prologue runs over twice the threads (config 2: -2 to -3 %)
-    int jit_epl_fused = 2;
-    uint32_t jit_kblock_fused = kBlock;
-    uint32_t jit_pro_fused = 2;
-    bool jit_shape_env = false;  // MDP_EPL / MDP_JIT_KBLOCK set: one shape for both variants
-    double jit_flops_pt = 0;  // its FP64 flops per grid point (counted by the generator)
-    size_t ldQ = 0;           // per-c Q block (doubles, even) read by the JIT kernel
-    std::vector<char> jit_code[3];  // forward kernel code objects [variant, as DevCtx::jit_fn], compiled on demand
-    std::string jit_src[3];         // their sources (a cached object the runtime refuses is rebuilt)
-    std::vector<std::string> chunk_src;
-    std::vector<MdpJitPlan> chunks;               // > 1: the series runs as chunks of years
-    std::vector<std::vector<char>> chunk_code;    // their code objects
-    bool qglobal = false;     // Q rows built by k_zrows + k_witems + k_wq (k_qrows' tables exceed the LDS)
-    int layout = MDP_LAYOUT_EC;  // mdp_engine_run's output layout (mdp_engine_set_layout)
-    double cbound = 0.0;         // the per-c tables' |c| bound at least this (mdp_engine_set_cbound)
-    int fused_mode = -1;            // MDP_FUSED: -1 auto, 0, 1
-    MdpJitPlan jit_plan;
-    // direct path (jit): k_qrows computes Pc[j][b] for the needed (j, b)
-    // items, the forward kernel assembles Q from them
-    uint32_t nj = 0, nitems = 0, ncoef_d = 0;
-    size_t ldP = 0;
-    std::vector<uint32_t> cj_bits, cj_item0, itemB, qstart, qitem, udesc_d, var_cols;
-    std::vector<uint32_t> itemRow;  // row (j slot) of each item
-    std::vector<uint2> qslot;       // k_qrows phase-3 lanes (build_direct_plan)
-    std::vector<uint32_t> qlane;    // their groups' Pc slots, kQGroup a lane (nvar <= 8)
-    std::vector<uint32_t> islot;    // k_qrows: each item's Pc slot (slots 0-15: zeros)
-    uint32_t npl_slots = 0;         // k_qrows: Pc slots per c value
-    uint32_t slot_conflicts = 0;    // k_qrows: extra gather cycles its slot colouring leaves (per c pair)
-    uint32_t slot_store_conflicts = 0;  // and extra store-group conflicts
-    // k_fwd_mma (wide years on the matrix cores): per year t its K entries
-    // (k | |A_k| << 8 | m << 16 | valid << 31, padded to 4) from kbase[t],
-    // and the Q-row slot of each (K entry, new state l) from gbase[t]
-    bool mma = false;
-    uint32_t mma_npm = 0;
-    std::vector<uint2> mma_kt;  // per year its K entries: LDS byte offsets of the W rows, m, k
-    std::vector<uint2> mma_wplan;  // per (year, wave) its work item (chunk range, column tile, slice)
-    std::vector<uint32_t> mma_kbase, mma_desc, mma_dbase;
-    uint32_t mma_ktmax = 16;
-    // k_fwd_mmt (round 6, the default matrix-core forward: years of up to
-    // 1 024 states): RT point tiles a block, per (year, tile) K lists, per
-    // (year, wave) work items (build_mmt_plan)
-    bool mmt = false;
-    uint32_t mmt_rt = 0, mmt_rows = 0;
-    std::vector<uint2> mmt_kt, mmt_ktile, mmt_wplan;
-    std::vector<uint32_t> mmt_cidx;
-    double mmt_flops_pt = 0;  // executed MFMA flops per grid point (padding included)
-    // k_fwd_hs (round 6, through the hidden states: build_hs_plan): 2^hs_nb
-    // cube positions, RT point tiles; per (year, tile) K lists of hidden
-    // states and their item offsets, per year butterfly passes, the new
-    // states' cube positions in tile order and free 16-row park blocks
-    bool hs = false;
-    uint32_t hs_rt = 0, hs_nb = 0, hs_nw = 16;
-    uint32_t hs_probe = 0;  // MDP_HS_PROBE (timing probes only, wrong results): 1 skips v Pe, 2 U Pc
-    std::vector<uint32_t> hs_kt, hs_cidx, hs_pbase, hs_dpos, hs_dbase, hs_pk;
-    std::vector<uint2> hs_ppos, hs_dpk;
-    std::vector<uint4> hs_wplan;
-    std::vector<uint4> hs_pass;
-    double hs_flops_pt = 0, hs_mfma_pt = 0;  // FP64 flops per grid point (padding included), of them MFMA
-    std::vector<uint32_t> ystate;  // each year's states (short_state bits), year_off order
-    uint32_t qslot_lglmax = 0;      // log2 of the widest lane segment
-    std::vector<uint8_t> isvar;
-    std::vector<double> Sj;  // [nj][n] colonisation sums of every column for each needed j
-    std::string jit_log;
-    size_t coef_lds = 0;      // k_coefs dynamic LDS bytes
-    double prior0 = 1.0;
-    std::vector<uint32_t> np, pairA, pairB, pairOff, use_pair, prog, udesc, pairPart0, partP, partK0;
-    std::vector<DevCtx> devs;
-    EngineOpts opts;          // mdp_engine_create_opts (variant selection; no environment reads)
-    mutable std::set<std::string, std::less<>> launched;  // kernel instantiations launched so far (mdp_engine_launched)
-    mutable std::mutex launched_mu;                         // engines may be driven from several host threads
-    int profiling = 0;
-    double last_ms[3] = {0, 0, 0};  // mean per run over the last collected runs
-    int nlast = 0;
-    uint64_t runs_collected = 0;
-};
-
-namespace {
-
-// The forward kernels' output strides: log L of point (ie, ic) at
-// out[ie * se + ic * sc] -- [e][c] rows (se = ld, sc = 1) or [c][e] columns
-// (se = 1, sc = ld); every forward kernel takes both.  Passed explicitly down
-// every launch path: only mdp_engine_run / mdp_engine_time_kernels honour the
-// engine's layout (mdp_engine_set_layout); mdp_loglik_grid always fills its
-// device slab in [e][c] (its host contract).
-struct OutStrides {
-    uint32_t se, sc;
-};
-inline OutStrides layout_strides(int layout, uint32_t ld)
-{
-    return layout == MDP_LAYOUT_CE ? OutStrides{1u, ld} : OutStrides{ld, 1u};
-}
-
 // record a launched kernel instantiation ("k_qrows<16,0,2>", ...)
 void note_launch(const mdp_engine *eng, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void note_launch(const mdp_engine *eng, const char *fmt, ...)
@@ -2503,433 +2235,6 @@ void note_launch(const mdp_engine *eng, const char *fmt, ...)
     // after the first launch of each this allocates nothing
     std::lock_guard<std::mutex> lk(eng->launched_mu);
     if (eng->launched.find(b) == eng->launched.end()) eng->launched.emplace(b);
-}
-
-constexpr int kDegBuckets[] = {4, 8, 16, 24};
-
-int select_variant(mdp_engine *eng)
-{
-    uint32_t np = 0;
-    for (uint32_t b : {1u, 2u, 4u, 8u, 16u})
-        if (eng->npmax <= b) { np = b; break; }
-    // a year with more than 16 states (over 4 missing patches) exceeds the
-    // register-resident forward kernels: the wide path takes the problem
-    if (!np) eng->wide = true;
-    uint32_t deg = 0;
-    for (int b : kDegBuckets)
-        if (eng->maxA <= (uint32_t)b) { deg = (uint32_t)b; break; }
-    if (!deg) return mdp_set_error(MDP_EUNSUPPORTED, "%u occupied patches in one state (max %d)", eng->maxA, kMaxDeg);
-    eng->deg = deg;
-    eng->variant = eng->wide ? 20000u + deg : np * 100 + deg;
-    return MDP_OK;
-}
-
-// Host plan: distinct transition pairs (sorted by |A&B| descending for load
-// balance in k_coefs), Q offsets, the per-use pair index in forward order, and
-// the step program (runs of 1x1 transitions / general years).
-int build_plan(mdp_engine *eng, const mdp_problem *p)
-{
-    eng->n = p->n;
-    eng->tmax = p->tmax;
-    eng->nvar = p->nvar;
-    eng->nextid = p->nextid;
-    if (p->nvar > 24)
-        return mdp_set_error(MDP_EUNSUPPORTED, "%u variable columns (engine limit 24)", p->nvar);
-    eng->nstates = 1u << p->nvar;
-    eng->prior0 = (double)p->prior[0];
-    if (const char *wv = eng->opts.get("MDP_WIDE")) eng->wide = atoi(wv) != 0;
-    eng->np.resize(p->tmax);
-    eng->npmax = 1;
-    for (uint32_t t = 0; t < p->tmax; ++t) {
-        eng->np[t] = p->year_off[t + 1] - p->year_off[t];
-        eng->npmax = std::max(eng->npmax, eng->np[t]);
-    }
-    eng->ystate.clear();
-    for (uint32_t i = 0; i < p->year_off[p->tmax]; ++i)
-        eng->ystate.push_back(p->year_ids[i] < p->nextid ? p->short_state[p->year_ids[i]] : ~0u);
-    std::map<uint64_t, uint32_t> pair_index;
-    std::vector<uint32_t> A0, B0, use0;
-    for (uint32_t t = 1; t < p->tmax; ++t) {
-        const uint32_t *prev = p->year_ids + p->year_off[t - 1];
-        const uint32_t *cur = p->year_ids + p->year_off[t];
-        for (uint32_t l = 0; l < eng->np[t]; ++l)
-            for (uint32_t k = 0; k < eng->np[t - 1]; ++k) {
-                const uint32_t a = prev[k], b = cur[l];
-                if (a >= p->nextid || b >= p->nextid)
-                    return mdp_set_error(MDP_EINVAL, "short id out of range in year %u", t);
-                const uint64_t key = ((uint64_t)a << 32) | b;
-                auto it = pair_index.find(key);
-                uint32_t pi;
-                if (it == pair_index.end()) {
-                    pi = (uint32_t)A0.size();
-                    pair_index.emplace(key, pi);
-                    A0.push_back(p->short_state[a]);
-                    B0.push_back(p->short_state[b]);
-                } else {
-                    pi = it->second;
-                }
-                use0.push_back(pi);
-                eng->maxA = std::max(eng->maxA, (uint32_t)__builtin_popcount(p->short_state[a]));
-            }
-    }
-    // sort pairs by subset count (heaviest first), stable
-    std::vector<uint32_t> order(A0.size());
-    for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return __builtin_popcount(A0[x] & B0[x]) > __builtin_popcount(A0[y] & B0[y]);
-    });
-    std::vector<uint32_t> rank(order.size());
-    uint32_t off = 0;
-    for (uint32_t r = 0; r < order.size(); ++r) {
-        const uint32_t i = order[r];
-        rank[i] = r;
-        eng->pairA.push_back(A0[i]);
-        eng->pairB.push_back(B0[i]);
-        eng->pairOff.push_back(off);
-        off += (uint32_t)__builtin_popcount(A0[i] & B0[i]) + 1u;
-    }
-    for (uint32_t u : use0) eng->use_pair.push_back(rank[u]);
-    // k_coefs subset parts (pair, first subset index), and per-use descriptors
-    for (uint32_t pi = 0; pi < eng->pairA.size(); ++pi) {
-        const uint32_t nX = (uint32_t)__builtin_popcount(eng->pairA[pi] & eng->pairB[pi]);
-        eng->pairPart0.push_back((uint32_t)eng->partP.size());
-        for (uint32_t k0 = 0; k0 < (1u << nX); k0 += kSubPart) {
-            eng->partP.push_back(pi);
-            eng->partK0.push_back(k0);
-        }
-    }
-    eng->pairPart0.push_back((uint32_t)eng->partP.size());
-    if (off > kOffMask) return mdp_set_error(MDP_EUNSUPPORTED, "too many transition coefficients");
-    for (uint32_t pi : eng->use_pair) {
-        const uint32_t A = eng->pairA[pi], B = eng->pairB[pi];
-        const uint32_t nA = (uint32_t)__builtin_popcount(A), nX = (uint32_t)__builtin_popcount(A & B);
-        eng->udesc.push_back(eng->pairOff[pi] | (nX << kOffBits) | (nA << 27));
-    }
-    eng->npairs = (uint32_t)eng->pairA.size();
-    eng->nuses = (uint32_t)eng->use_pair.size();
-    eng->ncoef = off;
-    int rc = select_variant(eng);
-    if (rc) return rc;
-    if (eng->wide) return MDP_OK;  // no step program / k_coefs plan: build_wide_plan
-    // step program
-    for (uint32_t t = 1; t < p->tmax;) {
-        if (eng->np[t - 1] == 1 && eng->np[t] == 1) {
-            uint32_t cnt = 0;
-            while (t < p->tmax && eng->np[t - 1] == 1 && eng->np[t] == 1) {
-                ++cnt;
-                ++t;
-            }
-            eng->prog.push_back(cnt << 1);
-        } else {
-            eng->prog.push_back(1u | (eng->np[t - 1] << 8) | (eng->np[t] << 16));
-            ++t;
-        }
-    }
-    eng->prog.push_back(0u);  // pad: the forward kernel reads one word ahead
-    // k_coefs LDS plan: [Z/PV block] [part partials] [Q] [binomials]; the
-    // partials spill to a global scratch when they do not fit
-    const size_t zbytes = (size_t)(eng->nvar + 1) * eng->nstates * sizeof(double);
-    const size_t pbytes = (size_t)eng->partP.size() * (eng->nvar + 1) * sizeof(double);
-    const size_t qbytes = ((size_t)eng->ncoef + (size_t)(kMaxDeg + 1) * (kMaxDeg + 1)) * sizeof(double);
-    if (zbytes + pbytes + qbytes <= kLdsBudget) {
-        eng->lds_zpv = eng->lds_part = true;
-        eng->coef_lds = zbytes + pbytes + qbytes;
-    } else if (pbytes + qbytes <= kLdsBudget) {
-        eng->lds_zpv = false;
-        eng->lds_part = true;
-        eng->coef_lds = pbytes + qbytes;
-    } else if (qbytes <= kLdsBudget) {
-        eng->lds_zpv = eng->lds_part = false;
-        eng->coef_lds = qbytes;
-    } else {
-        return mdp_set_error(MDP_EUNSUPPORTED, "%u transition coefficients exceed the LDS budget",
-                             eng->ncoef);
-    }
-    return MDP_OK;
-}
-
-// Direct-path plan.  Transitions that share X = A & B and the target state B
-// share Q; each (X, B) group needs Pc[j][B] for every j <= X.  Items are the
-// distinct (j, B), numbered by j ascending then B ascending; qstart / qitem
-// list, for every Q entry (group, m), its items with |j| = m in ascending j.
-int build_direct_plan(mdp_engine *eng, const mdp_problem *p)
-{
-    std::map<uint64_t, uint32_t> group;  // (X, B) -> Q offset
-    std::vector<std::pair<uint32_t, uint32_t>> groups;
-    std::vector<uint32_t> pair_group(eng->pairA.size());
-    uint32_t off = 0;
-    std::vector<uint32_t> goff;
-    for (size_t pi = 0; pi < eng->pairA.size(); ++pi) {
-        const uint32_t B = eng->pairB[pi], X = eng->pairA[pi] & B;
-        const uint64_t key = ((uint64_t)X << 32) | B;
-        auto it = group.find(key);
-        if (it == group.end()) {
-            it = group.emplace(key, (uint32_t)groups.size()).first;
-            groups.push_back({X, B});
-            // even start: the forward kernels read a group's coefficients
-            // pairwise as 16-byte aligned ds_read_b128 (an unaligned pair
-            // becomes a ds_read2_b64, twice the LDS cycles per byte)
-            off = (off + 1u) & ~1u;
-            goff.push_back(off);
-            off += (uint32_t)__builtin_popcount(X) + 1u;
-        }
-        pair_group[pi] = it->second;
-    }
-    if (off > kOffMask) return mdp_set_error(MDP_EUNSUPPORTED, "too many transition coefficients");
-    eng->ncoef_d = off;
-    std::map<uint32_t, std::vector<uint32_t>> jb;  // j -> states B (sorted, unique)
-    auto for_subsets = [](uint32_t X, auto &&fn) {  // ascending j <= X
-        const uint32_t nX = (uint32_t)__builtin_popcount(X);
-        for (uint32_t k = 0; k < (1u << nX); ++k) {
-            uint32_t j = 0, xs = X;
-            for (uint32_t i = 0; i < nX; ++i) {
-                const uint32_t low = xs & (0u - xs);
-                if ((k >> i) & 1u) j |= low;
-                xs ^= low;
-            }
-            fn(j);
-        }
-    };
-    for (auto &g : groups) for_subsets(g.first, [&](uint32_t j) { jb[j].push_back(g.second); });
-    std::map<uint64_t, uint32_t> item;  // (j, B) -> item
-    eng->cj_bits.clear();
-    eng->cj_item0.clear();
-    eng->itemB.clear();
-    for (auto &kv : jb) {
-        auto &v = kv.second;
-        std::sort(v.begin(), v.end());
-        v.erase(std::unique(v.begin(), v.end()), v.end());
-        eng->cj_bits.push_back(kv.first);
-        eng->cj_item0.push_back((uint32_t)eng->itemB.size());
-        for (uint32_t B : v) {
-            item.emplace(((uint64_t)kv.first << 32) | B, (uint32_t)eng->itemB.size());
-            eng->itemB.push_back(B);
-        }
-    }
-    eng->cj_item0.push_back((uint32_t)eng->itemB.size());
-    eng->nj = (uint32_t)eng->cj_bits.size();
-    if (eng->nj > 0xffffu) return mdp_set_error(MDP_EUNSUPPORTED, "%u hidden-state rows (direct path max 65535)", eng->nj);
-    eng->itemRow.assign(eng->itemB.size(), 0u);
-    for (uint32_t js = 0; js < eng->nj; ++js)
-        for (uint32_t i = eng->cj_item0[js]; i < eng->cj_item0[js + 1]; ++i) eng->itemRow[i] = js;
-    eng->nitems = (uint32_t)eng->itemB.size();
-    eng->ldP = ((size_t)eng->nitems + 1) & ~(size_t)1;
-    eng->qstart.assign(1, 0u);
-    eng->qitem.clear();
-    for (auto &g : groups) {
-        const uint32_t nX = (uint32_t)__builtin_popcount(g.first);
-        if ((eng->qstart.size() - 1) & 1u) eng->qstart.push_back((uint32_t)eng->qitem.size());  // pad slot
-        for (uint32_t m = 0; m <= nX; ++m) {
-            for_subsets(g.first, [&](uint32_t j) {
-                if ((uint32_t)__builtin_popcount(j) == m)
-                    eng->qitem.push_back(item.at(((uint64_t)j << 32) | g.second));
-            });
-            eng->qstart.push_back((uint32_t)eng->qitem.size());
-        }
-    }
-    // k_qrows' phase-3 lane table (the canonical Q-sum order, kQGroup): per
-    // entry q < ldQ an aligned segment of L = min(P, kQLanesMax) lanes, P =
-    // its group count rounded up to a power of two, each lane 2^G = P / L
-    // groups; segments packed largest first, so each is aligned and lies in
-    // one wave; padded to whole waves
-    {
-        const size_t ldq = ((size_t)off + 1) & ~(size_t)1;
-        struct Ent { uint32_t lgL, lgG, q; };
-        std::vector<Ent> ents;
-        for (uint32_t q = 0; q < ldq; ++q) {
-            const uint32_t n = q + 1 < eng->qstart.size() ? eng->qstart[q + 1] - eng->qstart[q] : 0u;
-            const uint32_t ng = std::max<uint32_t>(1u, (n + kQGroup - 1) / kQGroup);
-            uint32_t lgP = 0;
-            while ((1u << lgP) < ng) ++lgP;
-            uint32_t lgL = 0;
-            while ((1u << lgL) < kQLanesMax && lgL < lgP) ++lgL;
-            if (lgP - lgL >= (uint32_t)kQLevelsRows)
-                return mdp_set_error(MDP_EUNSUPPORTED, "a Q entry of %u items (k_qrows' lane table)", n);
-            ents.push_back({lgL, lgP - lgL, q});
-        }
-        std::stable_sort(ents.begin(), ents.end(), [](const Ent &x, const Ent &y) { return x.lgL > y.lgL; });
-        eng->qslot.clear();
-        eng->qslot_lglmax = ents.empty() ? 0u : ents[0].lgL;
-        for (const Ent &en : ents)
-            for (uint32_t le = 0; le < (1u << en.lgL); ++le)
-                eng->qslot.push_back(make_uint2(en.q, le | (en.lgL << 8) | (en.lgG << 12)));
-        while (eng->qslot.size() % 64) eng->qslot.push_back(make_uint2(0xffffffffu, 0u));
-        // nvar <= 8 (one group per lane): each lane's kQGroup items, nitems
-        // past its entry; at least 64 lanes
-        const uint32_t ni = eng->nitems;
-        eng->qlane.assign(std::max<size_t>(eng->qslot.size(), 64) * kQGroup, ni);
-        if (eng->nvar <= 8)
-            for (size_t sl = 0; sl < eng->qslot.size(); ++sl) {
-                const uint32_t q = eng->qslot[sl].x, le = eng->qslot[sl].y & 0xffu;
-                if ((size_t)q + 1 >= eng->qstart.size()) continue;  // padding lanes: q = ~0
-                const uint32_t j0 = eng->qstart[q] + le * kQGroup, i1 = eng->qstart[q + 1];
-                for (uint32_t u = 0; u < kQGroup && j0 + u < i1; ++u) eng->qlane[sl * kQGroup + u] = eng->qitem[j0 + u];
-            }
-        // Pc slots (16 bytes per slot and c pair in LDS).  Phase 3 gathers
-        // item u of every lane in one ds_read_b128, serviced in four 16-lane
-        // groups, conflict-free when a group's slots differ mod 16; phase 2
-        // stores eight consecutive items per 8-lane group of a
-        // ds_write_b128, conflict-free when they differ mod 8.  The items are
-        // coloured (colour = slot mod 16) greedily under both rules, the
-        // least-used allowed colour first; slots 0-15 hold zeros, and each
-        // group's padding takes the zero slot of a colour none of its items
-        // has.  nvar > 8 (CSR path): slot = item + 16.
-        eng->islot.resize(ni);
-        for (uint32_t it = 0; it < ni; ++it) eng->islot[it] = it + 16;
-        eng->npl_slots = ni + 16;
-        if (eng->nvar <= 8) {
-            auto lgroup = [](uint32_t l) -> uint32_t {  // ds_read_b128 lane groups
-                const uint32_t h = l & 31u;
-                const uint32_t g = (h < 4 || (h >= 12 && h < 16) || (h >= 20 && h < 28)) ? 0u : 1u;
-                return g + (l >= 32 ? 2u : 0u);
-            };
-            const size_t nl = eng->qslot.size();
-            std::vector<std::vector<uint32_t>> grp;  // per (wave, u, lane group): its items
-            for (size_t w0 = 0; w0 < nl; w0 += 64)
-                for (uint32_t u = 0; u < kQGroup; ++u) {
-                    std::vector<uint32_t> g4[4];
-                    for (uint32_t l = 0; l < 64 && w0 + l < nl; ++l) {
-                        const uint32_t it = eng->qlane[(w0 + l) * kQGroup + u];
-                        if (it < ni) g4[lgroup(l)].push_back(it);
-                    }
-                    for (auto &g : g4) {
-                        std::sort(g.begin(), g.end());
-                        g.erase(std::unique(g.begin(), g.end()), g.end());
-                        grp.push_back(std::move(g));
-                    }
-                }
-            std::vector<std::vector<uint32_t>> ig(ni);
-            for (uint32_t gi = 0; gi < grp.size(); ++gi)
-                for (uint32_t it : grp[gi]) ig[it].push_back(gi);
-            std::vector<int> col(ni, -1);
-            uint32_t cnt[16] = {};
-            for (uint32_t it = 0; it < ni; ++it) {
-                uint32_t forb = 0;
-                for (uint32_t gi : ig[it])
-                    for (uint32_t o : grp[gi])
-                        if (col[o] >= 0) forb |= 1u << col[o];
-                for (uint32_t o = it & ~7u; o < (it | 7u) + 1 && o < ni; ++o)  // phase 2's store group
-                    if (o != it && col[o] >= 0) forb |= 0x101u << (col[o] & 7);
-                int best = -1;
-                for (int pass = 0; pass < 2 && best < 0; ++pass)
-                    for (int cc = 0; cc < 16; ++cc)
-                        if ((pass || !((forb >> cc) & 1u)) && (best < 0 || cnt[cc] < cnt[best])) best = cc;
-                col[it] = best;
-                ++cnt[best];
-            }
-            // min-conflicts repair: move an item to the colour its groups use
-            // least while that lowers its own conflicts (each move lowers the
-            // total, which is symmetric in the pairs), a few sweeps.  A gather
-            // conflict costs a cycle per group; a store conflict only about a
-            // quarter of one (a ds_write_b128's transfer, 13 cycles, hides all
-            // but 3 of the 16 array cycles of a 2-way conflict): weights 4 : 1
-            for (int sweep = 0; sweep < 16; ++sweep) {
-                bool moved = false;
-                for (uint32_t it = 0; it < ni; ++it) {
-                    uint32_t cost[16] = {};
-                    for (uint32_t gi : ig[it])
-                        for (uint32_t o : grp[gi])
-                            if (o != it) cost[col[o]] += 4;
-                    for (uint32_t o = it & ~7u; o < (it | 7u) + 1 && o < ni; ++o)
-                        if (o != it) {
-                            ++cost[col[o] & 7];
-                            ++cost[(col[o] & 7) + 8];
-                        }
-                    int best = col[it];
-                    for (int cc = 0; cc < 16; ++cc)
-                        if (cost[cc] < cost[best] || (cost[cc] == cost[best] && cnt[cc] + 1 < cnt[best])) best = cc;
-                    if (best != col[it]) {
-                        --cnt[col[it]];
-                        ++cnt[best];
-                        col[it] = best;
-                        moved = true;
-                    }
-                }
-                if (!moved) break;
-            }
-            uint32_t next[16];
-            for (uint32_t cc = 0; cc < 16; ++cc) next[cc] = 16 + cc;
-            uint32_t top = 16;
-            for (uint32_t it = 0; it < ni; ++it) {
-                eng->islot[it] = next[col[it]];
-                next[col[it]] += 16;
-                top = std::max(top, eng->islot[it] + 1);
-            }
-            eng->npl_slots = top;
-            // what the colouring leaves: per phase-3 group the extra cycles of
-            // its busiest residue, per phase-2 store group those mod 8
-            uint32_t extra = 0, sextra = 0;
-            for (const auto &g : grp) {
-                uint32_t m[16] = {};
-                for (uint32_t it : g) ++m[eng->islot[it] & 15u];
-                extra += *std::max_element(m, m + 16) - (g.empty() ? 0u : 1u);
-            }
-            for (uint32_t g0 = 0; g0 < ni; g0 += 8) {
-                uint32_t m[8] = {};
-                for (uint32_t it = g0; it < std::min(ni, g0 + 8); ++it) ++m[eng->islot[it] & 7u];
-                sextra += *std::max_element(m, m + 8) - 1u;
-            }
-            eng->slot_conflicts = extra;
-            eng->slot_store_conflicts = sextra;
-            // the lanes' slots; each (wave, u, lane group)'s padding on a free colour
-            for (size_t w0 = 0; w0 < std::max<size_t>(nl, 64); w0 += 64)
-                for (uint32_t u = 0; u < kQGroup; ++u) {
-                    uint32_t used[4] = {};
-                    for (uint32_t l = 0; l < 64; ++l) {
-                        const uint32_t it = eng->qlane[(w0 + l) * kQGroup + u];
-                        if (it < ni) used[lgroup(l)] |= 1u << (eng->islot[it] & 15u);
-                    }
-                    for (uint32_t l = 0; l < 64; ++l) {
-                        uint32_t &x = eng->qlane[(w0 + l) * kQGroup + u];
-                        if (x < ni) {
-                            x = eng->islot[x];
-                        } else {
-                            const uint32_t fr = ~used[lgroup(l)] & 0xffffu;
-                            x = fr ? (uint32_t)__builtin_ctz(fr) : 0u;
-                        }
-                    }
-                }
-        }
-    }
-    eng->udesc_d.clear();
-    for (uint32_t pi : eng->use_pair) {
-        const uint32_t A = eng->pairA[pi], B = eng->pairB[pi];
-        const uint32_t nA = (uint32_t)__builtin_popcount(A), nX = (uint32_t)__builtin_popcount(A & B);
-        eng->udesc_d.push_back(goff[pair_group[pi]] | (nX << kOffBits) | (nA << 27));
-    }
-    // colonisation sums S[j][k] = sum over var columns l in j (ascending),
-    // l != k, of M[l][k] -- the reference's per-point sum (:350-357) with its
-    // zero terms dropped, in its order
-    const uint32_t n = p->n, nvar = p->nvar;
-    eng->var_cols.assign(p->var_cols, p->var_cols + nvar);
-    eng->isvar.assign(n, 0);
-    for (uint32_t b = 0; b < nvar; ++b) eng->isvar[p->var_cols[b]] = 1;
-    eng->Sj.assign((size_t)eng->nj * n, 0.0);
-    for (uint32_t js = 0; js < eng->nj; ++js) {
-        const uint32_t j = eng->cj_bits[js];
-        for (uint32_t k = 0; k < n; ++k) {
-            double acc = 0.0;
-            for (uint32_t b = 0; b < nvar; ++b) {
-                const uint32_t col = p->var_cols[b];
-                if (((j >> (nvar - 1 - b)) & 1u) && col != k) acc += p->M[(size_t)col * n + k];
-            }
-            eng->Sj[(size_t)js * n + k] = acc;
-        }
-    }
-    return MDP_OK;
-}
-
-// Wide-path plan: the direct plan's groups, items and per-use descriptors,
-// plus the FP64 work per grid point of k_fwd_wide (every use a (nX+1)-term
-// dot product with a weight multiply per term, one FMA into the state
-// vector; the per-lane power tables; the final prior sum).
-// k_fwd_mma: two state buffers and the power tables of the block's points,
-// and (LDS staging) three years' K entries
-size_t mma_lds(const mdp_engine *eng)
-{
-    const uint32_t npm = eng->mma_npm;
-    return (2 * (size_t)mma_rows(npm) * mma_pts(npm) + 2 * ((size_t)eng->maxA + 1) * mma_ps(npm)) * sizeof(double) +
-           0;
 }
 
 // the k_fwd_mma instantiation of the engine's plan
@@ -2950,31 +2255,6 @@ size_t device_lds_max()
     return 160 * 1024;
 }
 
-// k_fwd_mmt: the state buffer and the power tables of the block's points
-// k_fwd_mmt's shapes by the largest year: RT point tiles, state rows, two buffers
-struct MmtShape {
-    uint32_t rt, rows;
-    bool db;
-};
-// (measured, profiles/r06/wide: years of up to 128 states run 25 % faster on
-// <4, 128, 2buf> than on <2, 256, 1buf>; a 256-state problem 6 % faster on
-// one buffer than on <2, 256, 2buf>)
-inline MmtShape mmt_shape(const mdp_engine *eng)
-{
-    const uint32_t npmax = eng->npmax;
-    if (npmax <= 128) return {4u, 128u, true};
-    if (npmax <= 256) return {2u, 256u, false};
-    if (npmax <= 512) return {2u, 512u, false};
-    return {1u, 1024u, false};
-}
-
-size_t mmt_lds(const mdp_engine *eng)
-{
-    const MmtShape sh = mmt_shape(eng);
-    return ((sh.db ? 2 : 1) * (size_t)sh.rows * mmt_pts(sh.rt) + 2 * ((size_t)eng->maxA + 1) * mmt_ps(sh.rt)) *
-           sizeof(double);
-}
-
 const void *mmt_kernel(const mdp_engine *eng)
 {
     if (eng->mmt_rows == 128) return (const void *)k_fwd_mmt<4, 128, true>;
@@ -2983,600 +2263,11 @@ const void *mmt_kernel(const mdp_engine *eng)
     return (const void *)k_fwd_mmt<1, 1024, false>;
 }
 
-// per (year, wave) work items over a year's column tiles of nch[tile]
-// pipeline chunks each (k_fwd_mmt, k_fwd_hs): more than 16 tiles are dealt
-// longest list first to the least-loaded wave (up to tmaxit each); up to 16
-// give every tile a wave and the spare waves to the tiles whose slices are
-// longest (at least two chunks each; slices past the first `inplace` of a
-// tile park their partials, `room` 16-row blocks at most)
-void plan_waves(const std::vector<uint32_t> &nch, uint32_t tmaxit, uint32_t inplace, uint32_t room, uint2 *wp,
-                uint32_t nw = 16)
-{
-    const uint32_t ncol = (uint32_t)nch.size();
-    if (ncol <= nw) {
-        // waves per tile: one each, the rest to the tile whose slices
-        // are longest (each slice at least two chunks; the parked
-        // partials -- every slice past the first `inplace` of a tile --
-        // within the buffer's rows past the year's tiles)
-        std::vector<uint32_t> w(ncol, 1);
-        uint32_t parked = 0;
-        for (uint32_t spare = nw - ncol; spare; --spare) {
-            uint32_t best = ncol;
-            for (uint32_t i = 0; i < ncol; ++i)
-                if (nch[i] / (w[i] + 1) >= 2 && (w[i] + 1 <= inplace || parked < room) &&
-                    (best == ncol || nch[i] * w[best] > nch[best] * w[i]))
-                    best = i;
-            if (best == ncol) break;
-            if (++w[best] > inplace) ++parked;
-        }
-        const uint32_t split = *std::max_element(w.begin(), w.end()) > 1 ? 1u : 0u;
-        for (uint32_t wv = 0; wv < nw; ++wv)
-            for (uint32_t i = 0; i < tmaxit; ++i) wp[wv * tmaxit + i] = make_uint2(0u, split << 22);
-        uint32_t wv = 0, pbase = 0;
-        for (uint32_t tile = 0; tile < ncol; ++tile) {
-            for (uint32_t ks = 0; ks < w[tile]; ++ks, ++wv) {
-                const uint32_t cb = nch[tile] * ks / w[tile], ce = nch[tile] * (ks + 1) / w[tile];
-                wp[wv * tmaxit] = make_uint2(cb | ce << 16, tile | ks << 8 | w[tile] << 12 | pbase << 17 |
-                                                               split << 22 | 1u << 24);
-            }
-            pbase += w[tile] > inplace ? w[tile] - inplace : 0;
-        }
-    } else {
-        std::vector<uint32_t> order(ncol), cnt(nw, 0);
-        std::vector<uint64_t> load(nw, 0);
-        for (uint32_t i = 0; i < ncol; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return nch[x] > nch[y]; });
-        for (uint32_t wv = 0; wv < nw; ++wv)
-            for (uint32_t i = 0; i < tmaxit; ++i) wp[wv * tmaxit + i] = make_uint2(0u, 0u);
-        for (uint32_t tile : order) {
-            uint32_t best = nw;
-            for (uint32_t wv = 0; wv < nw; ++wv)
-                if (cnt[wv] < tmaxit && (best == nw || load[wv] < load[best])) best = wv;
-            wp[best * tmaxit + cnt[best]++] = make_uint2(nch[tile] << 16, tile | 1u << 12 | 1u << 24);
-            load[best] += nch[tile];
-        }
-    }
-}
-
-// k_fwd_mmt's tables (c-independent): years of at most 1 024 states.
-//  * per (year, column tile) its K entries: every source k with m = 0 ..
-//    the largest nX over the tile's new states (the rest of m <= |A_k| would
-//    meet only zero slots), padded to whole pipeline chunks; and per K entry
-//    and new state l of the tile, the byte offset in the Q row of Q_kl[m]
-//    (the zero slot where m > nX_kl, for padded states and padded entries)
-//    -- 64 bytes per entry, so the kernel's gathers need no lookup;
-//  * per (year, wave) up to ROWS / 256 work items: tiles of years of more
-//    than 16 tiles dealt longest list first to the least-loaded wave;
-//    smaller years give every tile a wave and the spare waves to the tiles
-//    with the longest lists, each tile's list split into as many slices
-//    (at least two chunks each).
-void build_mmt_plan(mdp_engine *eng)
-{
-    if (eng->npmax > 1024 || eng->maxA > 24 || eng->tmax < 2) return;
-    const MmtShape shp = mmt_shape(eng);
-    const uint32_t rows = shp.rows, rt = shp.rt, pts = mmt_pts(rt), ps = mmt_ps(rt);
-    const uint32_t tmaxit = rows > 256 ? rows / 256 : 1, cw = 4 * mmt_u(rt), inplace = shp.db ? 2u : 1u;
-    const uint32_t none = (uint32_t)eng->ncoef_d;
-    if (none > kOffMask) return;
-    eng->mmt_rt = rt;
-    eng->mmt_rows = rows;
-    eng->mmt_kt.clear();
-    eng->mmt_cidx.clear();
-    eng->mmt_ktile.assign((size_t)(eng->tmax + 1) * kMmtMaxTiles, make_uint2(0u, 1u));
-    eng->mmt_wplan.assign((size_t)(eng->tmax + 1) * 16 * tmaxit, make_uint2(0u, 0u));
-    double fl = 0.0;
-    size_t ub = 0;
-    for (uint32_t t = 1; t < eng->tmax; ++t) {
-        const uint32_t npp = eng->np[t - 1], npc = eng->np[t], ncol = (npc + 15) / 16;
-        const uint32_t *ud = eng->udesc_d.data() + ub;  // ud[l * npp + k]
-        std::vector<uint32_t> nch(ncol);
-        for (uint32_t tile = 0; tile < ncol; ++tile) {
-            const size_t start = eng->mmt_kt.size();
-            const uint32_t l1 = std::min(16 * tile + 16, npc);
-            for (uint32_t k = 0; k < npp; ++k) {
-                const uint32_t a = ud[k] >> 27;  // |A_k|
-                uint32_t mx = 0;
-                for (uint32_t l = 16 * tile; l < l1; ++l) mx = std::max(mx, (ud[(size_t)l * npp + k] >> kOffBits) & 31u);
-                for (uint32_t m = 0; m <= mx; ++m) {  // V row k, y^m row, x^(a-m) row (bytes); m; k
-                    eng->mmt_kt.push_back(make_uint2((k * pts * 8u) | ((m * ps * 8u) << 18),
-                                                     ((a - m) * ps * 8u) | (m << 16) | (k << 21)));
-                    for (uint32_t l = 16 * tile; l < 16 * tile + 16; ++l) {
-                        uint32_t o = none;
-                        if (l < npc) {
-                            const uint32_t dsc = ud[(size_t)l * npp + k];
-                            if (m <= ((dsc >> kOffBits) & 31u)) o = (dsc & kOffMask) + m;
-                        }
-                        eng->mmt_cidx.push_back(o * 8u);
-                    }
-                }
-            }
-            while ((eng->mmt_kt.size() - start) % cw) {
-                eng->mmt_kt.push_back(make_uint2(0u, npp << 21));
-                for (uint32_t l = 0; l < 16; ++l) eng->mmt_cidx.push_back(none * 8u);
-            }
-            nch[tile] = (uint32_t)((eng->mmt_kt.size() - start) / cw);
-            eng->mmt_ktile[(size_t)t * kMmtMaxTiles + tile] = make_uint2((uint32_t)start, nch[tile]);
-            fl += 2.0 * 16.0 * (double)(eng->mmt_kt.size() - start);
-        }
-        plan_waves(nch, tmaxit, inplace, (rows - ncol * 16) / 16, eng->mmt_wplan.data() + (size_t)t * 16 * tmaxit);
-        ub += (size_t)npp * npc;
-    }
-    eng->mmt_flops_pt = fl + 2.0 * (eng->maxA + 1) + (double)eng->np[eng->tmax - 1];
-    // (the offsets' table is the plan's largest: 64 bytes per K entry)
-    eng->mmt = mmt_lds(eng) <= device_lds_max() && eng->mmt_kt.size() < (1u << 26) && (size_t)none * 8u < 0xffffffffu;
-    if (!eng->mmt) {
-        eng->mmt_kt.clear();
-        eng->mmt_cidx.clear();
-    }
-}
-
-// k_fwd_hs: the cube of the block's points (128 KiB for each shape)
-size_t hs_lds(const mdp_engine *eng)
-{
-    return (((size_t)1 << eng->hs_nb) + eng->hs_nb + 1) * mmt_pts(eng->hs_rt) * sizeof(double);  // + y^k table
-}
-
 const void *hs_kernel(const mdp_engine *eng)
 {
     if (eng->hs_nb == 8) return eng->hs_nw == 8 ? (const void *)k_fwd_hs<2, 8, 8> : (const void *)k_fwd_hs<4, 8, 16>;
     if (eng->hs_nb == 9) return (const void *)k_fwd_hs<2, 9, 16>;
     return (const void *)k_fwd_hs<1, 10, 16>;
-}
-
-// k_fwd_hs's tables (c-independent; nvar <= 10, years of at most 1 024
-// states).  Per year t >= 1:
-//  * butterfly passes over W = the bits of year t - 1's states, up to
-//    kHsRadix patches a pass: first the patches set in no hidden state the
-//    year's products read, then greedily the one adding the fewest new cube
-//    positions; a pass lists its cosets (g, the masks of the positions it
-//    reads and writes: only those whose value still reaches a hidden state
-//    the products read).  After the passes every such j holds U[j];
-//  * the year's states ordered by (B & W, B), so a tile's 16 states share
-//    their reachable hidden states; per tile K = the j in that down-closure
-//    below some state of the tile, ascending, padded to whole pipeline
-//    chunks (row 0, C = 0), and per (K entry, state) the byte offset of the
-//    item Pc[j][B] in the column's Pg row (its zero slot, nitems, for j not
-//    below B, padded states and padded entries);
-//  * the states' cube positions in tile order (~0: padding), the free 16-row
-//    park blocks (no state of the year in them), the wave plan.
-// Year 0's positions head dpos.  Refused (hs = false: k_fwd_mmt runs) for a
-// year with a repeated state or an item the direct plan lacks.
-void build_hs_plan(mdp_engine *eng)
-{
-    eng->hs = false;
-    if (eng->nvar > 10 || eng->tmax < 2 || eng->npmax > 1024 || eng->ystate.size() < eng->tmax) return;
-    const uint32_t nb = std::max<uint32_t>(8u, eng->nvar);
-    // waves a block (MDP_HS_WAVES): 8 for 8 variable patches (32 points, a
-    // 64 KiB cube: two blocks a CU, whose phases overlap; measured 5 % faster
-    // on the 256-state series, equal on the 128-state one, profiles/r06/hs),
-    // else 16
-    uint32_t nw = nb == 8 ? 8u : 16u;
-    if (const char *wv = eng->opts.get("MDP_HS_WAVES")) nw = atoi(wv) == 8 && nb == 8 ? 8u : 16u;
-    const uint32_t rt = nb == 8 ? (nw == 8 ? 2u : 4u) : nb == 9 ? 2u : 1u, pts = mmt_pts(rt);
-    const uint32_t ncube = 1u << nb, tmaxit = ncube / 16 > nw ? ncube / 16 / nw : 1u, cw = 4 * mmt_u(rt);
-    const uint32_t zero = eng->nitems;  // the Pg row's zero slot
-    if ((uint64_t)zero * 8u >= 0xffffffffull) return;
-    // patches per v Pe pass (MDP_HS_RADIX, 1 .. kHsRadix; default 4, the
-    // measured best: profiles/r06/hs -- 1 024 cosets x points fill the block
-    // in one sweep; 5 left half the threads idle on 1 024-state years)
-    uint32_t radix = kHsRadix;
-    if (const char *rv = eng->opts.get("MDP_HS_RADIX")) radix = std::min<uint32_t>(kHsRadix, std::max(1, atoi(rv)));
-    std::unordered_map<uint64_t, uint32_t> item;  // (j, B) -> item
-    for (uint32_t js = 0; js < eng->nj; ++js)
-        for (uint32_t i = eng->cj_item0[js]; i < eng->cj_item0[js + 1]; ++i)
-            item.emplace(((uint64_t)eng->cj_bits[js] << 32) | eng->itemB[i], i);
-    std::vector<uint32_t> yoff(eng->tmax + 1, 0);
-    for (uint32_t t = 0; t < eng->tmax; ++t) yoff[t + 1] = yoff[t] + eng->np[t];
-    auto st = [&](uint32_t t, uint32_t l) { return eng->ystate[yoff[t] + l]; };
-    eng->hs_kt.clear();
-    eng->hs_cidx.clear();
-    eng->hs_pass.clear();
-    eng->hs_ppos.clear();
-    eng->hs_dpos.clear();
-    std::vector<uint2> ktile(kMmtMaxTiles), wtmp(nw * tmaxit);
-    eng->hs_wplan.assign((size_t)(eng->tmax + 1) * nw * tmaxit, make_uint4(0u, 0u, 0u, 1u));
-    eng->hs_pk.assign((size_t)(eng->tmax + 1) * 16, 0u);
-    eng->hs_pbase.assign(eng->tmax + 1, 0u);
-    eng->hs_dbase.assign(eng->tmax + 1, 0u);
-    std::vector<uint8_t> seen(ncube, 0);
-    auto distinct = [&](uint32_t t) {
-        bool ok = true;
-        for (uint32_t l = 0; l < eng->np[t]; ++l) {
-            const uint32_t b = st(t, l);
-            if (b >= ncube || seen[b]) ok = false;
-            else seen[b] = 1;
-        }
-        for (uint32_t l = 0; l < eng->np[t]; ++l)
-            if (st(t, l) < ncube) seen[st(t, l)] = 0;
-        return ok;
-    };
-    if (!distinct(0)) return;
-    for (uint32_t l = 0; l < (eng->np[0] + 15) / 16 * 16; ++l) eng->hs_dpos.push_back(l < eng->np[0] ? st(0, l) : ~0u);
-    double fb = 0.0, fm = 0.0;
-    std::vector<uint8_t> live(ncube);
-    std::vector<uint32_t> lv;
-    for (uint32_t t = 1; t < eng->tmax; ++t) {
-        const uint32_t npp = eng->np[t - 1], npc = eng->np[t], ncol = (npc + 15) / 16;
-        if (!distinct(t)) return;
-        // butterfly passes
-        std::fill(live.begin(), live.end(), 0);
-        lv.clear();
-        uint32_t W = 0;
-        for (uint32_t k = 0; k < npp; ++k) {
-            W |= st(t - 1, k);
-            live[st(t - 1, k)] = 1;
-            lv.push_back(st(t - 1, k));
-        }
-        // D: the hidden states below some state of year t - 1 (U's
-        // support); N: those below some state of year t (U's reads, the
-        // union of the year's K lists); M(rem): the positions whose value
-        // still reaches N by the butterflies over the patches rem (N's
-        // up-closure over rem) -- a pass reads live positions in M(before)
-        // and writes positions in M(after) only
-        std::vector<uint8_t> Dm(ncube, 0), Nm(ncube, 0), Mb(ncube), Ma(ncube);
-        for (uint32_t k = 0; k < npp; ++k) Dm[st(t - 1, k)] = 1;
-        for (uint32_t bit = 1; bit < ncube; bit <<= 1)
-            for (uint32_t q = 0; q < ncube; ++q)
-                if ((q & bit) && Dm[q]) Dm[q ^ bit] = 1;
-        uint32_t nused = 0;  // patches set in some j of N
-        for (uint32_t l = 0; l < npc; ++l) {
-            const uint32_t key = st(t, l) & W;
-            for (uint32_t j = key;; j = (j - 1) & key) {
-                if (Dm[j] && !Nm[j]) {
-                    Nm[j] = 1;
-                    nused |= j;
-                }
-                if (!j) break;
-            }
-        }
-        auto upclose = [&](uint32_t rem, std::vector<uint8_t> &M) {
-            M = Nm;
-            for (uint32_t bit = 1; bit < ncube; bit <<= 1)
-                if (rem & bit)
-                    for (uint32_t q = 0; q < ncube; ++q)
-                        if (!(q & bit) && M[q]) M[q | bit] = 1;
-        };
-        // the patches of W: first those set in no j of N (each halves what
-        // later passes touch), then greedily the one adding the fewest new
-        // positions (ties: fewest values to move)
-        std::vector<uint32_t> border;
-        {
-            std::vector<uint8_t> lt(live);
-            std::vector<uint32_t> l2(lv);
-            for (int phase = 0; phase < 2; ++phase)
-                for (uint32_t rem = W & (phase ? nused : ~nused); rem;) {
-                    uint32_t best = 0, bnew = ~0u, bpairs = ~0u;
-                    for (uint32_t rr = rem; rr; rr &= rr - 1) {
-                        const uint32_t bit = rr & (0u - rr);
-                        uint32_t nw = 0, pr = 0;
-                        for (uint32_t a : l2)
-                            if (a & bit) {
-                                ++pr;
-                                nw += !lt[a ^ bit];
-                            }
-                        if (nw < bnew || (nw == bnew && pr < bpairs)) {
-                            best = bit;
-                            bnew = nw;
-                            bpairs = pr;
-                        }
-                    }
-                    rem &= ~best;
-                    border.push_back((uint32_t)__builtin_ctz(best));
-                    const size_t n2 = l2.size();
-                    for (size_t i = 0; i < n2; ++i)
-                        if ((l2[i] & best) && !lt[l2[i] ^ best]) {
-                            lt[l2[i] ^ best] = 1;
-                            l2.push_back(l2[i] ^ best);
-                        }
-                }
-        }
-        eng->hs_pbase[t] = (uint32_t)eng->hs_pass.size();
-        const size_t npass = (border.size() + radix - 1) / radix;
-        uint32_t remw = W;
-        for (size_t ip = 0, b0 = 0; ip < npass; ++ip) {
-            // passes of near-equal size (radix 4: 10 patches 4 + 3 + 3)
-            const uint32_t r = (uint32_t)((border.size() - b0 + (npass - ip) - 1) / (npass - ip));
-            uint32_t bp[kHsRadix] = {}, mask = 0, bits = 0;
-            for (uint32_t k = 0; k < r; ++k) {
-                bp[k] = border[b0 + k];
-                mask |= 1u << bp[k];
-                bits |= bp[k] << (5 * k);
-            }
-            b0 += r;
-            upclose(remw, Mb);
-            remw &= ~mask;
-            upclose(remw, Ma);
-            auto dep = [&](uint32_t q) {
-                uint32_t o = 0;
-                for (uint32_t k = 0; k < r; ++k)
-                    if (q & (1u << k)) o |= 1u << bp[k];
-                return o;
-            };
-            std::map<uint32_t, uint32_t> cos;  // g -> mask of positions read
-            for (uint32_t a : lv) {
-                if (!Mb[a]) continue;
-                uint32_t q = 0;
-                for (uint32_t k = 0; k < r; ++k)
-                    if (a & (1u << bp[k])) q |= 1u << k;
-                cos[a & ~mask] |= 1u << q;
-            }
-            const uint32_t base = (uint32_t)eng->hs_ppos.size();
-            std::map<uint32_t, std::vector<uint32_t>> bymask;  // read | write << 16 -> its cosets
-            for (auto &kv : cos) {
-                uint32_t cl = kv.second;  // the read positions' subsets
-                cl |= (cl & 0xaaaau) >> 1;
-                cl |= (cl & 0xccccu) >> 2;
-                cl |= (cl & 0xf0f0u) >> 4;
-                cl |= (cl & 0xff00u) >> 8;
-                uint32_t outm = 0;
-                for (uint32_t q = 0; q < (1u << r); ++q)
-                    if (((cl >> q) & 1u) && Ma[kv.first | dep(q)]) outm |= 1u << q;
-                bymask[kv.second | outm << 16].push_back(kv.first);
-            }
-            // cosets grouped by masks, pts / 64 ... a wave's worth at a time
-            // (64 / pts cosets a wave), each wave padded with copies of its
-            // first coset (a lane of the same wave: identical values)
-            const uint32_t cpw = 64u / pts;
-            for (auto &mv : bymask)
-                for (size_t i = 0; i < mv.second.size(); i += cpw)
-                    for (uint32_t k = 0; k < cpw; ++k)
-                        eng->hs_ppos.push_back(make_uint2(i + k < mv.second.size() ? mv.second[i + k] : mv.second[i],
-                                                          mv.first));
-            for (auto &kv : cos) {
-                uint32_t cl = kv.second;
-                cl |= (cl & 0xaaaau) >> 1;
-                cl |= (cl & 0xccccu) >> 2;
-                cl |= (cl & 0xf0f0u) >> 4;
-                cl |= (cl & 0xff00u) >> 8;
-                uint32_t outm = 0;
-                for (uint32_t q = 0; q < (1u << r); ++q)
-                    if (((cl >> q) & 1u) && Ma[kv.first | dep(q)]) outm |= 1u << q;
-                fb += 2.0 * (double)r * (double)(1u << (r - 1)) + (ip + 1 == npass ? (double)(1u << r) : 0.0);
-                for (uint32_t q = 0; q < (1u << r); ++q)
-                    if (((outm >> q) & 1u) && !live[kv.first | dep(q)]) {
-                        live[kv.first | dep(q)] = 1;
-                        lv.push_back(kv.first | dep(q));
-                    }
-            }
-            eng->hs_pass.push_back(make_uint4(bits, r, (uint32_t)eng->hs_ppos.size() - base, base));
-        }
-        // the year's states in tile order
-        std::vector<uint32_t> ord(npc);
-        for (uint32_t l = 0; l < npc; ++l) ord[l] = l;
-        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
-            const uint32_t bx = st(t, x), by = st(t, y);
-            return (bx & W) != (by & W) ? (bx & W) < (by & W) : bx < by;
-        });
-        eng->hs_dbase[t] = (uint32_t)eng->hs_dpos.size();
-        for (uint32_t i = 0; i < ncol * 16; ++i) eng->hs_dpos.push_back(i < npc ? st(t, ord[i]) : ~0u);
-        std::vector<uint32_t> nch(ncol);
-        std::vector<uint32_t> K;
-        for (uint32_t tile = 0; tile < ncol; ++tile) {
-            K.clear();
-            for (uint32_t i = 16 * tile; i < std::min(16 * tile + 16, npc); ++i) {
-                const uint32_t key = st(t, ord[i]) & W;
-                for (uint32_t j = key;; j = (j - 1) & key) {  // subsets of key (with j = 0 last)
-                    if (Dm[j]) K.push_back(j);
-                    if (!j) break;
-                }
-            }
-            std::sort(K.begin(), K.end());
-            K.erase(std::unique(K.begin(), K.end()), K.end());
-            const size_t start = eng->hs_kt.size();
-            for (uint32_t j : K) {
-                eng->hs_kt.push_back(j * pts * 8u);
-                for (uint32_t i = 16 * tile; i < 16 * tile + 16; ++i) {
-                    uint32_t o = zero;
-                    if (i < npc && !(j & ~st(t, ord[i]))) {
-                        auto it = item.find(((uint64_t)j << 32) | st(t, ord[i]));
-                        if (it == item.end()) return;
-                        o = it->second;
-                    }
-                    eng->hs_cidx.push_back(o * 8u);
-                }
-            }
-            while ((eng->hs_kt.size() - start) % cw) {
-                eng->hs_kt.push_back(0u);
-                for (uint32_t l = 0; l < 16; ++l) eng->hs_cidx.push_back(zero * 8u);
-            }
-            nch[tile] = (uint32_t)((eng->hs_kt.size() - start) / cw);
-            ktile[tile] = make_uint2((uint32_t)start, nch[tile]);
-            fm += 2.0 * 16.0 * (double)(eng->hs_kt.size() - start);
-        }
-        // free park blocks
-        std::vector<uint8_t> used(ncube / 16, 0);
-        for (uint32_t l = 0; l < npc; ++l) used[st(t, l) / 16] = 1;
-        uint32_t room = 0;
-        for (uint32_t b = 0; b < ncube / 16 && room < 16; ++b)
-            if (!used[b]) eng->hs_pk[(size_t)t * 16 + room++] = b * 16;
-        plan_waves(nch, tmaxit, 1u, room, wtmp.data(), nw);
-        for (uint32_t i = 0; i < nw * tmaxit; ++i) {
-            const uint2 kt2 = ktile[wtmp[i].y & 0xffu];
-            eng->hs_wplan[(size_t)t * nw * tmaxit + i] =
-                (wtmp[i].y >> 24) ? make_uint4(wtmp[i].x, wtmp[i].y, kt2.x, kt2.y) : make_uint4(wtmp[i].x, wtmp[i].y, 0u, 1u);
-        }
-    }
-    eng->hs_pbase[eng->tmax] = (uint32_t)eng->hs_pass.size();
-    // the store positions per (16 positions of dpos, lane group kk): entries
-    // kk + 4 r, r = 0 .. 3, 16 bits each (0xffff: padding)
-    eng->hs_dpk.assign(eng->hs_dpos.size() / 16 * 4, make_uint2(0u, 0u));
-    for (size_t b = 0; b < eng->hs_dpos.size() / 16; ++b)
-        for (uint32_t kq = 0; kq < 4; ++kq) {
-            uint32_t w[4];
-            for (uint32_t r = 0; r < 4; ++r) {
-                const uint32_t ps = eng->hs_dpos[b * 16 + kq + 4 * r];
-                w[r] = ps == ~0u ? 0xffffu : ps;
-            }
-            eng->hs_dpk[b * 4 + kq] = make_uint2(w[0] | w[1] << 16, w[2] | w[3] << 16);
-        }
-    if (eng->hs_kt.empty()) eng->hs_kt.push_back(0u);
-    if (eng->hs_ppos.empty()) eng->hs_ppos.push_back(make_uint2(0u, 0u));
-    if (eng->hs_pass.empty()) eng->hs_pass.push_back(make_uint4(0u, 0u, 0u, 0u));
-    eng->hs_mfma_pt = fm;
-    eng->hs_flops_pt = fb + fm + (double)eng->np[eng->tmax - 1];
-    eng->hs_rt = rt;
-    eng->hs_nb = nb;
-    eng->hs_nw = nw;
-    if (const char *pv = eng->opts.get("MDP_HS_PROBE")) eng->hs_probe = (uint32_t)atoi(pv) & 7u;
-    eng->hs = hs_lds(eng) <= device_lds_max() && eng->hs_kt.size() < (1u << 26);
-}
-
-int build_wide_plan(mdp_engine *eng, const mdp_problem *p)
-{
-    int rc = build_direct_plan(eng, p);
-    if (rc) return rc;
-    // Q rows with at least one zero slot past the coefficients (slot ncoef:
-    // k_fwd_mma's gathers of absent coefficients read it)
-    eng->ldQ = ((size_t)eng->ncoef_d + 2) & ~(size_t)1;
-    double f = 2.0 * (eng->maxA + 1) + 2.0 * eng->np[eng->tmax - 1];
-    for (uint32_t d : eng->udesc_d) f += 3.0 * (((d >> kOffBits) & 31u) + 1.0) + 2.0;
-    eng->wide_flops_pt = f;
-    // k_fwd_mma's tables (c-independent): years of at most 256 states; per
-    // year its K entries (k, |A_k|, m), padded to whole pipeline chunks with
-    // entries naming the descriptor row npp (every transition absent), and the
-    // transition descriptors [k][2^sh >= npcp] (Q-row offset | nX << kOffBits;
-    // an absent transition names the zero slot with nX = 0)
-    // MDP_WIDE_MMA: 0 -> k_fwd_wide; 1 -> round 5's k_fwd_mma (<= 256
-    // states); 2 -> k_fwd_mmt (<= 1 024 states); 3 -> k_fwd_hs (nvar <= 10;
-    // else k_fwd_mmt); unset -> k_fwd_hs for years of more than 64 states,
-    // else k_fwd_mmt (measured, profiles/r06/hs: k_fwd_hs 1.3x / 4.4x / 5.2x
-    // / 5.8x faster on 128 / 256 / 512 / 1 024 states, 1.27x slower on 64)
-    const char *mv = eng->opts.get("MDP_WIDE_MMA");
-    const int mmode = mv ? atoi(mv) : (eng->npmax > 64 ? 3 : 2);
-    eng->mmt = false;
-    eng->hs = false;
-    if (mmode == 3) build_hs_plan(eng);
-    if (mmode == 2 || (mmode == 3 && !eng->hs)) build_mmt_plan(eng);
-    eng->mma = false;
-    if (eng->npmax <= 256 && eng->maxA <= 24) {
-        if (mmode == 1) {
-            const uint32_t npm = eng->npmax <= 64 ? 64u : eng->npmax <= 128 ? 128u : 256u;
-            const uint32_t pts = mma_pts(npm), ps = mma_ps(npm);
-            const uint32_t none = (uint32_t)eng->ncoef_d;  // the zero slot, nX = 0
-            eng->mma_npm = npm;
-            eng->mma_kt.clear();
-            eng->mma_desc.clear();
-            eng->mma_kbase.assign(eng->tmax + 1, 0u);
-            eng->mma_dbase.assign(eng->tmax + 1, 0u);
-            eng->mma_ktmax = 16;
-            size_t ub = 0;
-            bool pad_overflow = false;
-            for (uint32_t t = 1; t < eng->tmax; ++t) {
-                const uint32_t npp = eng->np[t - 1], npc = eng->np[t], npcp = (npc + 15) / 16 * 16;
-                uint32_t ld = 16;
-                while (ld < npcp) ld *= 2;
-                eng->mma_kbase[t] = (uint32_t)eng->mma_kt.size();
-                eng->mma_dbase[t] = (uint32_t)eng->mma_desc.size();
-                for (uint32_t k = 0; k < npp; ++k) {
-                    const uint32_t a = eng->udesc_d[ub + k] >> 27;  // |A_k| (any use from k; l = 0)
-                    for (uint32_t m = 0; m <= a; ++m)  // Va row k, xp row a - m, yp row m (bytes); m; k
-                        eng->mma_kt.push_back(make_uint2((k * pts * 8u) | (((a - m) * ps * 8u) << 16),
-                                                         (m * ps * 8u) | (m << 16) | (k * kMmaDummy)));
-                }
-                // padding names descriptor row npp through the 8-bit k field:
-                // row 256 would wrap to row 0 (the advisor's round-5 finding),
-                // so a 256-state year that needs padding leaves k_fwd_mma
-                if (eng->mma_kt.size() % (4 * kMmaU) && npp > 255) pad_overflow = true;
-                while (eng->mma_kt.size() % (4 * kMmaU)) eng->mma_kt.push_back(make_uint2(0u, npp * kMmaDummy));
-                eng->mma_ktmax = std::max<uint32_t>(eng->mma_ktmax, (uint32_t)eng->mma_kt.size() - eng->mma_kbase[t]);
-                for (uint32_t k = 0; k <= npp; ++k)
-                    for (uint32_t l = 0; l < ld; ++l) {
-                        uint32_t dv = none;
-                        if (k < npp && l < npc) {
-                            const uint32_t dsc = eng->udesc_d[ub + (size_t)l * npp + k];
-                            dv = (dsc & kOffMask) | (((dsc >> kOffBits) & 31u) << kOffBits);
-                        }
-                        eng->mma_desc.push_back(dv);
-                    }
-                ub += (size_t)npp * npc;
-            }
-            eng->mma_kbase[eng->tmax] = (uint32_t)eng->mma_kt.size();
-            eng->mma_dbase[eng->tmax] = (uint32_t)eng->mma_desc.size();
-            // per year and wave its work item (k_fwd_mma): column tile, K
-            // slice of S (at most 16 waves; slice 1 in the destination rows,
-            // later ones in the rows past the year's column tiles; at least
-            // two chunks each), chunk range
-            eng->mma_wplan.assign((size_t)(eng->tmax + 1) * 16, make_uint2(0u, 0u));
-            for (uint32_t t = 1; t < eng->tmax; ++t) {
-                const uint32_t ncol = (eng->np[t] + 15) / 16, npcp = ncol * 16;
-                const uint32_t nch = (eng->mma_kbase[t + 1] - eng->mma_kbase[t]) / (4 * kMmaU);
-                const uint32_t room = 2 + (mma_rows(npm) - npcp) / npcp;
-                const uint32_t S = std::min(std::min(16 / ncol, room), std::max(1u, nch / 2));
-                for (uint32_t wv = 0; wv < 16; ++wv) {
-                    const uint32_t item = wv % ncol, ks = wv / ncol;
-                    const uint32_t cb = nch * ks / S, ce = nch * (ks + 1) / S;
-                    eng->mma_wplan[(size_t)t * 16 + wv] =
-                        make_uint2(cb | ce << 16, item | ks << 8 | S << 16 | (wv < ncol * S ? 1u : 0u) << 24);
-                }
-            }
-            // (chunk reads past a year's entries are clamped into it; one
-            // chunk of slack keeps the last year's clamp in the table)
-            for (uint32_t i = 0; i < 4 * kMmaU; ++i) eng->mma_kt.push_back(make_uint2(0u, 0u));
-            if (eng->mma_desc.empty()) eng->mma_desc.push_back(none);
-            const size_t lmax = device_lds_max();
-            eng->mma = mma_lds(eng) <= lmax && none <= kOffMask && !pad_overflow;
-        }
-    }
-    return MDP_OK;
-}
-
-
-constexpr size_t kQrowsLdsMax = 160 * 1024;
-constexpr size_t kFusedLdsMax = 64 * 1024;  // fused forward kernel: every table of one column
-
-// k_qrows LDS for cb c values per workgroup: Z, var-column S, Pc, Q CSR
-size_t qrows_lds(const mdp_engine *eng, uint32_t cb)
-{
-    const size_t nv = eng->nvar <= 8 ? 8 : eng->nvar <= 16 ? 16 : 24;  // k_qrows NV
-    return ((((size_t)cb * eng->nj + 1) & ~(size_t)1) + (size_t)eng->nj * (cb * nv + 2) + (size_t)cb * eng->npl_slots) *
-               sizeof(double) +
-           ((size_t)eng->ncoef_d + 1 + eng->qitem.size()) * sizeof(uint32_t);  // (items stay in registers)
-}
-
-// Z rows for a grid whose |c| <= cmax.  Z_j(c) = prod over the always-zero
-// columns k of max(0, 1 - c S[j][k]) splits by the size of |c| S:
-//  * |c| S <= 2^-55: the factor is exactly 1.0 -- dropped;
-//  * 2^-55 < |c| S <= kZTau ("small"): never clamped, and their product is
-//    exp(sum log(1 - c S)) = exp(-sum_i c^i P_i / i) with the power sums
-//    P_i = sum_small S^i.  The series stops after kZTerms terms: the rest is
-//    below sum_small (c S)^(kZTerms+1) / (kZTerms+1) <= 256 * 2^-63 / 9
-//    < 2^-58 relative per 256 small columns (exp: ~1 ulp), so Z keeps
-//    double precision while a row costs kZTerms FMAs and one exp instead of
-//    an FMA and a multiply per column (config 3: 248 -> <= 24 columns a row);
-//  * the rest ("large", |c| S > kZTau or not finite) stay explicit factors,
-//    the largest first (the clamp test reads it).
-// zs[k][row] / zsT[row][k] hold the large columns (kmax = the longest row
-// rounded up to 8, zero padding = factor 1.0); zc[row][kZTerms] the series
-// coefficients P_i / i (zero for a row without small columns: exp(0) = 1).
-constexpr double kZTau = 0x1p-7;
-constexpr int kZTerms = kZTermsDev;
-
-void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
-             std::vector<uint32_t> *cols = nullptr)
-{
-    const uint32_t n = eng->n;
-    large.clear();
-    if (cols) cols->clear();
-    size_t imax = 0;
-    double pw[kZTerms] = {};
-    for (uint32_t k = 0; k < n; ++k) {
-        if (eng->isvar[k]) continue;
-        const double sv = eng->Sj[(size_t)js * n + k];
-        const double x = cmax * sv;
-        if (x <= 0x1p-55) continue;  // false for NaN / inf: kept
-        if (x <= kZTau) {
-            double t = sv;
-            for (int i = 0; i < kZTerms; ++i, t *= sv) pw[i] += t;
-            continue;
-        }
-        if (!large.empty() && sv > large[imax]) imax = large.size();
-        large.push_back(sv);
-        if (cols) cols->push_back(k);
-    }
-    if (!large.empty()) std::swap(large[0], large[imax]);
-    if (cols && !cols->empty()) std::swap((*cols)[0], (*cols)[imax]);
-    if (coef)
-        for (int i = 0; i < kZTerms; ++i) coef[i] = pw[i] / (double)(i + 1);
 }
 
 int upload_qrows_tables(const mdp_engine *eng, DevCtx &d, double cmax)
@@ -3642,117 +2333,6 @@ int upload_qrows_tables(const mdp_engine *eng, DevCtx &d, double cmax)
     if ((rc = dev_reserve(&d.coltab, &d.cap_coltab, ct))) return rc;
     HIP_TRY(hipMemcpy(d.coltab, img.data(), ct * sizeof(double), hipMemcpyHostToDevice));
     d.ct_len = (uint32_t)ct;
-    return MDP_OK;
-}
-
-// Compile (hipRTC, cached) the engine's forward kernel: variant 0 reading,
-// 1 fused, 2 reading at kJitKblockTall threads (a column of a tall grid in
-// half the blocks: its Q row staged half as often).
-constexpr int kJitKblockTall = 512;
-int jit_build(mdp_engine *eng, int variant)
-{
-    const bool fused = variant == 1;
-    if (!eng->jit_code[variant].empty()) return MDP_OK;
-    MdpJitPlan plan = eng->jit_plan;
-    plan.fused = fused;
-    if (variant == 2) {  // the reading kernel's points per lane, more threads
-        plan.epl = eng->jit_epl > 0 ? eng->jit_epl : mdp_jit_default_epl(plan.udesc);
-        plan.kblock = kJitKblockTall;
-        const std::string src = mdp_jit_forward_source(plan);
-        if (mdp_jit_compile(src, eng->jit_code[2], eng->jit_log) != 0)
-            return mdp_set_error(MDP_EHIP, "hipRTC compilation of the forward kernel failed: %s", eng->jit_log.c_str());
-        eng->jit_src[2] = src;
-        return MDP_OK;
-    }
-    // the reading variant's shape (e rows per block = kblock x epl, which
-    // set_grid_dev's block count uses before it picks the variant)
-    const int epl_r = plan.epl > 0 ? plan.epl : mdp_jit_default_epl(plan.udesc);
-    const int kb_r = plan.kblock > 0 ? plan.kblock : kBlock;
-    eng->jit_epl = epl_r;
-    eng->jit_kblock = (uint32_t)kb_r;
-    if (fused && !eng->jit_shape_env) {
-        // the same e rows per block as the reading variant (kb_r x epl_r, the
-        // grid shape is shared), the forward at its points per lane, and
-        // twice the threads for the column-table prologue (pro 2): a
-        // forward at one point per lane was LDS-bound (each broadcast pair
-        // read feeds half the FMAs), while the prologue wants every thread
-        plan.kblock = kb_r;
-        plan.epl = epl_r;
-        plan.pro = 2;
-    }
-    if (fused) {  // at most 1 024 threads a workgroup: fewer prologue threads, then fewer columns
-        const int fc = std::max(1, plan.fused_cols);
-        if (plan.kblock * fc * std::max(1, plan.pro) > 1024) plan.pro = 1;
-        if (plan.kblock * fc > 1024) plan.fused_cols = std::max(1, 1024 / std::max(1, plan.kblock));
-        eng->jit_plan.fused_cols = plan.fused_cols;  // the launch's columns per workgroup
-    }
-    const std::string src = mdp_jit_forward_source(plan);
-    if (fused) {
-        eng->jit_epl_fused = plan.epl;
-        eng->jit_kblock_fused = (uint32_t)plan.kblock;
-        eng->jit_pro_fused = (uint32_t)std::max(1, plan.pro);
-    }
-    eng->jit_flops_pt = plan.flops_pt;
-    if (const char *dump = eng->opts.get("MDP_JIT_DUMP")) {  // <path>.hip (reading) / <path>.fused.hip
-        if (FILE *f = fopen((std::string(dump) + (fused ? ".fused.hip" : ".hip")).c_str(), "w")) {
-            fputs(src.c_str(), f);
-            fclose(f);
-        }
-    }
-    if (mdp_jit_compile(src, eng->jit_code[variant], eng->jit_log) != 0)
-        return mdp_set_error(MDP_EHIP, "hipRTC compilation of the forward kernel failed: %s",
-                             eng->jit_log.c_str());
-    eng->jit_src[variant] = src;
-    return MDP_OK;
-}
-
-// Compile every chunk kernel of a long series (threads: hipRTC programs are
-// independent).
-int jit_build_chunks(mdp_engine *eng)
-{
-    const size_t nch = eng->chunks.size();
-    if (eng->chunk_code.size() == nch) return MDP_OK;
-    std::vector<std::vector<char>> code(nch);
-    std::vector<std::string> logs(nch);
-    std::vector<int> rcs(nch, 0);
-    std::vector<std::string> srcs(nch);
-    double flops = 0.0;
-    for (size_t i = 0; i < nch; ++i) {
-        srcs[i] = mdp_jit_forward_source(eng->chunks[i]);
-        flops += eng->chunks[i].flops_pt;
-        if (const char *dump = eng->opts.get("MDP_JIT_DUMP"))
-            if (FILE *f = fopen((std::string(dump) + ".chunk" + std::to_string(i) + ".hip").c_str(), "w")) {
-                fputs(srcs[i].c_str(), f);
-                fclose(f);
-            }
-    }
-    {
-        std::vector<std::thread> th;
-        size_t nt = std::min<size_t>(8, nch);
-        if (const char *tv = eng->opts.get("MDP_JIT_THREADS")) nt = std::max<size_t>(1, std::min<size_t>(nch, atoi(tv)));
-        const bool verbose = eng->opts.get("MDP_JIT_VERBOSE") != nullptr;
-        for (size_t t = 0; t < nt; ++t)
-            th.emplace_back([&, t]() {
-                for (size_t i = t; i < nch; i += nt) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    rcs[i] = mdp_jit_compile(srcs[i], code[i], logs[i]);
-                    if (verbose)
-                        fprintf(stderr, "chunk %zu: %zu uses, %.2f s\n", i, eng->chunks[i].udesc.size(),
-                                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-                }
-            });
-        for (auto &x : th) x.join();
-    }
-    for (size_t i = 0; i < nch; ++i)
-        if (rcs[i]) {
-            eng->jit_log = logs[i];
-            return mdp_set_error(MDP_EHIP, "hipRTC compilation of forward chunk %zu failed: %s", i, logs[i].c_str());
-        }
-    eng->chunk_code = std::move(code);
-    eng->chunk_src = std::move(srcs);
-    eng->jit_epl = eng->chunks[0].epl;
-    eng->jit_kblock = (uint32_t)eng->chunks[0].kblock;
-    eng->jit_flops_pt = flops;
     return MDP_OK;
 }
 
@@ -3829,20 +2409,9 @@ int jit_load(mdp_engine *eng, DevCtx &d, int variant)
     return MDP_OK;
 }
 
-// The fused forward kernel keeps its column's tables (ct_len doubles,
-// dynamic LDS), Z, Pc and Q in LDS.
-size_t fused_lds(const mdp_engine *eng, size_t ct_len)
-{
-    const size_t fc = (size_t)eng->jit_plan.fused_cols;
-    return (ct_len + 2 + fc * (eng->nj + eng->nitems + 2 * eng->ldQ)) * sizeof(double);  // + staging scratch
-}
-
 constexpr size_t kWidePgBytes = 256ull << 20;  // wide path: item-factor chunk
 constexpr size_t kHsPgBytes = 2048ull << 20;   // k_fwd_hs: item factors of the columns of one launch
 constexpr size_t kWideVBytes = 1ull << 30;     // wide path: state-vector scratch
-
-// k_fwd_wide: per-lane x^r, y^r tables, r <= maxA
-size_t wide_lds(const mdp_engine *eng) { return 2 * ((size_t)eng->maxA + 1) * kBlock * sizeof(double); }
 
 int upload_binomials()  // into the current device's constant bank
 {
@@ -4005,11 +2574,6 @@ void free_device(DevCtx &d)
     if (d.vscr) (void)hipFree(d.vscr);
     if (d.stream) (void)hipStreamDestroy(d.stream);
 }
-
-// per-c coefficient stride: every forward use (deg+1 coefficients padded to
-// an even count) plus two zero transitions of prefetch padding
-size_t rsp_of(const mdp_engine *eng) { return (eng->deg + 2) & ~1u; }
-size_t ldR_of(const mdp_engine *eng) { return ((size_t)eng->nuses + 2) * rsp_of(eng); }
 
 // The point list of forward kernels with `epl` points per lane: the e rows
 // whose ratio form is s (x < y, x = min(e, 1), y = 1 - x, as the kernel
@@ -4562,82 +3126,6 @@ int collect_times(mdp_engine *eng, DevCtx &d)
     return MDP_OK;
 }
 
-// Split a long series into chunks of whole years for the hipRTC forward
-// kernel: at most `U` uses per chunk (straight-line code stays a bounded
-// size), preferring a boundary year with one state (the smallest hand-over)
-// in the last quarter of a chunk.  With `gather`, each chunk stages only the
-// Q groups its uses read (at most kJitChunkQ doubles, a chunk-local layout of
-// even-aligned groups) instead of the whole Q row.
-int plan_chunks(mdp_engine *eng, uint32_t U, bool gather, size_t qlimit)
-{
-    const MdpJitPlan &base = eng->jit_plan;
-    const std::vector<uint32_t> &np = eng->np;
-    const std::vector<uint32_t> &ud = eng->udesc_d;
-    const uint32_t T = eng->tmax;
-    const int epl = base.epl > 0 ? base.epl : mdp_jit_default_epl(ud);
-    auto gsize = [](uint32_t d) { return (((d >> kOffBits) & 31u) + 2u) & ~1u; };  // nX + 1, even
-    eng->chunks.clear();
-    uint32_t t0 = 0;
-    size_t u0 = 0;
-    uint32_t e0 = 0;  // pending exponent of B at the chunk boundary (spom_jit.cpp)
-    while (t0 + 1 < T) {
-        size_t cur = 0, qloc = 0, u1 = u0, best_u1 = 0;
-        uint32_t t1 = t0, best_t1 = 0;
-        std::set<uint32_t> loc;
-        while (t1 + 1 < T) {
-            const size_t nu = (size_t)np[t1] * np[t1 + 1];
-            size_t addq = 0;
-            std::set<uint32_t> fresh;
-            if (gather)
-                for (size_t u = u1; u < u1 + nu; ++u) {
-                    const uint32_t off = ud[u] & kOffMask;
-                    if (!loc.count(off) && fresh.insert(off).second) addq += gsize(ud[u]);
-                }
-            if (cur > 0 && (cur + nu > U || (gather && qloc + addq > qlimit))) break;
-            cur += nu;
-            qloc += addq;
-            loc.insert(fresh.begin(), fresh.end());
-            u1 += nu;
-            ++t1;
-            if (np[t1] == 1 && 4 * cur >= 3 * (size_t)U) {
-                best_t1 = t1;
-                best_u1 = u1;
-            }
-        }
-        if (t1 + 1 < T && best_t1 && best_t1 < t1) {
-            t1 = best_t1;
-            u1 = best_u1;
-        }
-        MdpJitPlan c = base;
-        c.fused = false;
-        c.epl = epl;
-        c.np.assign(np.begin() + t0, np.begin() + t1 + 1);
-        c.udesc.assign(ud.begin() + u0, ud.begin() + u1);
-        c.first = t0 == 0;
-        c.last = t1 + 1 == T;
-        c.e0 = e0;
-        e0 = mdp_jit_end_exp(c);
-        if (gather) {  // chunk-local Q layout, groups in first-use order
-            std::map<uint32_t, uint32_t> lo;
-            c.qidx.clear();
-            for (uint32_t &d : c.udesc) {
-                const uint32_t off = d & kOffMask;
-                auto it = lo.find(off);
-                if (it == lo.end()) {
-                    it = lo.emplace(off, (uint32_t)c.qidx.size()).first;
-                    for (uint32_t m = 0; m < gsize(d); ++m) c.qidx.push_back(off + std::min(m, (d >> kOffBits) & 31u));
-                }
-                d = (d & ~kOffMask) | it->second;
-            }
-            c.ldq_row = base.ldQ;
-        }
-        eng->chunks.push_back(std::move(c));
-        t0 = t1;
-        u0 = u1;
-    }
-    return eng->chunks.empty() ? mdp_set_error(MDP_EUNSUPPORTED, "no forward chunks") : MDP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -4657,9 +3145,9 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
     const bool st_on = getenv("MDP_SETUP_TIMING") && atoi(getenv("MDP_SETUP_TIMING")) != 0;
     auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double st0 = st_now();
-    double st_jit0 = st0, st_jit1 = st0;
+    double st_jit[2] = {st0, st0};  // around the hipRTC step (mdp_plan_engine)
     EngineOpts opts;
-    if (int orc = parse_engine_opts(options, opts)) return orc;
+    if (int orc = parse_engine_opts(options, opts, kDiagBuild)) return orc;
     if (p->n == 0 || p->tmax == 0 || !p->M || !p->year_off || !p->year_ids || !p->prior ||
         !p->short_state || (p->nvar && !p->var_cols))
         return mdp_set_error(MDP_EINVAL, "incomplete problem description");
@@ -4676,188 +3164,12 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
     mdp_engine *eng = new (std::nothrow) mdp_engine();
     if (!eng) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     eng->opts = std::move(opts);
-    int rc = build_plan(eng, p);
+    const bool offline_check = jit_check && ndev == 0;
+    int rc = mdp_plan_engine(eng, p, device_lds_max(), offline_check ? MdpPlanMode::OfflineCheck : MdpPlanMode::Compile,
+                             st_jit);
     if (rc) {
         delete eng;
         return rc;
-    }
-    eng->fwd_lds_bytes = ldR_of(eng) * sizeof(double) + (eng->prog.size() + 1) * sizeof(uint32_t);
-    eng->fwd_lds = eng->fwd_lds_bytes <= kFwdLds;
-    if (const char *ev = eng->opts.get("MDP_FWD"))
-        if (!strcmp(ev, "scalar")) eng->fwd_lds = false;
-    if (const char *ev = eng->opts.get("MDP_EPL")) {
-        const int v = atoi(ev);
-        if (v == 1 || v == 2 || v == 4) eng->epl = v;
-    }
-    if (const char *ev = eng->opts.get("MDP_DIAG")) eng->diag = atoi(ev) != 0;
-    {
-        const char *jv = eng->opts.get("MDP_JIT");
-        const bool jit_off = jv && !strcmp(jv, "0");
-        // years of 17-64 states: the specialised forward kernel with its
-        // state vectors in LDS (plan.vlds), unless the series is so long that
-        // hipRTC would take minutes; MDP_WIDE=1 forces the wide kernels
-        const char *wv0 = eng->opts.get("MDP_WIDE");
-        const bool wide_forced = wv0 && atoi(wv0) != 0;
-        bool vlds = false;
-        uint32_t vlds_max_uses = kVldsMaxUses;
-        if (const char *mv = eng->opts.get("MDP_VLDS_MAXUSES")) vlds_max_uses = (uint32_t)std::max(0, atoi(mv));
-        const uint32_t vkb = kBlock;  // points per workgroup (their states: npmax x vkb doubles of LDS)
-        if (eng->wide && !wide_forced && !jit_off && eng->npmax <= kVldsMaxStates && eng->nuses <= vlds_max_uses) {
-            eng->wide = false;
-            vlds = true;
-        }
-        const bool want = !eng->wide && !jit_off;
-        bool want_jit = want && build_direct_plan(eng, p) == MDP_OK;
-        // k_qrows keeps every table of its c values in LDS; larger problems
-        // build their Q rows in HBM (k_zrows + k_witems + k_wq, the same bits)
-        const char *qg = eng->opts.get("MDP_QGLOBAL");
-        eng->qglobal = want_jit && (qrows_lds(eng, 1) > kQrowsLdsMax || (qg && atoi(qg) != 0));
-        eng->ldQ = ((size_t)eng->ncoef_d + 1) & ~(size_t)1;
-        // a series longer than kJitMaxUses uses (or a Q row past the LDS) runs
-        // as chunks of years (MDP_JIT_CHUNK / MDP_JIT_GATHER force them)
-        uint32_t chunk_uses = kJitChunkUses;
-        const char *cv = eng->opts.get("MDP_JIT_CHUNK");
-        if (cv) chunk_uses = (uint32_t)std::max(1, atoi(cv));
-        const char *gv = eng->opts.get("MDP_JIT_GATHER");
-        // coefficients a forward kernel may stage: what the LDS leaves beside
-        // the wide years' state vectors (npmax x 256 lanes) when they are there
-        // (halved: the forward kernel keeps each Q row twice, in stored and in
-        // reversed group order -- spom_jit.cpp, the ratio forms)
-        const size_t qlimit = (vlds ? std::min(kJitChunkQ, (kQrowsLdsMax - (size_t)eng->npmax * vkb * sizeof(double) -
-                                                          2048) / sizeof(double))
-                                    : kJitChunkQ) / 2;
-        const bool gather = eng->ldQ > qlimit || (gv && atoi(gv) != 0);
-        const bool chunked = eng->nuses > kJitMaxUses || gather || (cv && eng->nuses > chunk_uses);
-        if (want_jit && eng->nuses > 0) {
-            MdpJitPlan &plan = eng->jit_plan;
-            if (vlds) {  // the wide years' states in LDS: one point per lane, never fused
-                plan.vlds = true;
-                // points per lane: 1, or 2 (MDP_VLDS_EPL=2: 128 lanes per wave
-                // group, each Q read shared by two points)
-                const char *ve = eng->opts.get("MDP_VLDS_EPL");
-                plan.epl = ve && atoi(ve) == 2 ? 2 : 1;
-                plan.kblock = (int)vkb / plan.epl;
-                plan.window = 16;
-                eng->fused_mode = 0;
-                if (const char *sv = eng->opts.get("MDP_VSPLIT")) plan.vsplit = atoi(sv) == 1 ? 1 : atoi(sv) == 2 ? 2 : 4;
-            }
-            plan.np = eng->np;
-            plan.udesc = eng->udesc_d;
-            plan.ldQ = eng->ldQ;
-            plan.diag = eng->diag;
-            if (const char *cv = eng->opts.get("MDP_JIT_SLOTS")) plan.slots = atoi(cv);
-            if (const char *wv = eng->opts.get("MDP_JIT_WPE")) plan.wpe = atoi(wv);
-            if (const char *xv = eng->opts.get("MDP_JIT_XCD")) plan.xcd = atoi(xv) != 0;
-            if (const char *fv2 = eng->opts.get("MDP_JIT_EFAST")) plan.efast = atoi(fv2) != 0;
-            if (const char *qx = eng->opts.get("MDP_QROWS_XCD")) eng->qrows_xcd = atoi(qx) != 0;
-            if (const char *ev = eng->opts.get("MDP_EPL")) {
-                plan.epl = atoi(ev);
-                eng->jit_shape_env = true;
-            }
-            if (const char *wv = eng->opts.get("MDP_JIT_WINDOW")) plan.window = atoi(wv);
-            // compile the variant a small grid uses now (the other on demand)
-            if (const char *fv = eng->opts.get("MDP_FUSED")) eng->fused_mode = atoi(fv) != 0;
-            if (const char *cv = eng->opts.get("MDP_FUSED_COLS")) plan.fused_cols = std::max(1, std::min(4, atoi(cv)));
-            if (const char *cv = eng->opts.get("MDP_JIT_HACK")) plan.hack = atoi(cv);
-            if (const char *cv = eng->opts.get("MDP_FAST_LOG")) plan.fast_log = atoi(cv) != 0;
-            if (const char *cv = eng->opts.get("MDP_JIT_KBLOCK"); cv && !vlds) {
-                plan.kblock = atoi(cv) == 512 ? 512 : 256;
-                eng->jit_shape_env = true;
-            }
-            plan.nj = eng->nj;
-            plan.nvar = eng->nvar;
-            plan.nitems = eng->nitems;
-            plan.ncoef = eng->ncoef_d;
-            plan.nqi = (uint32_t)eng->qitem.size();
-            {   // zs rows compiled into the fused kernel: the longest row of
-                // explicit columns at |c| <= 1 (the default grid); a grid
-                // with more (|c| > 1) runs k_zrows + k_qrows instead
-                size_t kz = 0;
-                std::vector<double> large;
-                for (uint32_t js = 0; js < eng->nj; ++js) {
-                    z_split(eng, js, 1.0, large, nullptr);
-                    kz = std::max(kz, large.size());
-                }
-                plan.kzmax = (uint32_t)std::max<size_t>(8, (kz + 7) & ~(size_t)7);
-            }
-            plan.qmaxlen = 0;
-            for (size_t q = 0; q + 1 < eng->qstart.size(); ++q)
-                plan.qmaxlen = std::max(plan.qmaxlen, eng->qstart[q + 1] - eng->qstart[q]);
-            auto even = [](size_t v) { return (uint32_t)((v + 1) & ~(size_t)1); };
-            if (const char *sv = eng->opts.get("MDP_JIT_SPLIT")) plan.split_forms = atoi(sv) != 0;
-            if (const char *sv = eng->opts.get("MDP_JIT_ROT")) plan.rot = atoi(sv) != 0;
-            {
-                plan.off_it = even((size_t)eng->nj * eng->nvar);
-                plan.off_qs = even(plan.off_it + eng->nitems);
-                plan.off_qi = even(plan.off_qs + (eng->ncoef_d + 2) / 2);
-                plan.off_rq = even(plan.off_qi + (eng->qitem.size() + 1) / 2);
-                plan.off_zc = even(plan.off_rq + (eng->ldQ + 1) / 2);
-                plan.off_zs = even(plan.off_zc + (size_t)eng->nj * kZTerms);
-                const size_t kmax_max = plan.kzmax;
-                plan.ct_max = (uint32_t)std::min<size_t>(((plan.off_zs + kmax_max * eng->nj) + 127) & ~(size_t)127,
-                                                         kFusedLdsMax / sizeof(double));
-                // zero-padded zs image when the largest one fits the fused kernel's LDS
-                const size_t kz = std::max<size_t>(8, kmax_max);
-                plan.zpad = fused_lds(eng, ((plan.off_zs + kz * eng->nj) + 127) & ~(size_t)127) <= kFusedLdsMax;
-            }
-            if (chunked && (rc = plan_chunks(eng, chunk_uses, gather, qlimit))) {
-                delete eng;
-                return rc;
-            }
-            if (jit_check && ndev == 0 && chunked) {
-                const int r = jit_build_chunks(eng);
-                if (!r)
-                    mdp_set_error(MDP_ENODEV, "no HIP device available (forward kernels compiled; %zu chunks%s; "
-                                  "nj %u nitems %u ldQ %zu qglobal %d)", eng->chunks.size(), gather ? ", gathered Q" : "",
-                                  plan.nj, plan.nitems, (size_t)plan.ldQ, (int)eng->qglobal);
-                delete eng;
-                return r ? r : MDP_ENODEV;
-            }
-            if (jit_check && ndev == 0) {
-                const int r0 = jit_build(eng, false), r1 = r0 ? r0 : jit_build(eng, true);
-                uint32_t ipr = 0;  // most items of one row
-                for (uint32_t js = 0; js + 1 < eng->cj_item0.size(); ++js)
-                    ipr = std::max(ipr, eng->cj_item0[js + 1] - eng->cj_item0[js]);
-                if (!r1)
-                    mdp_set_error(MDP_ENODEV,
-                                  "no HIP device available (forward kernels compiled; nj %u nitems %u "
-                                  "items/row %u ldQ %zu qitems %u qmaxlen %u kzmax %u qrows slots %u conflicts %u + %u fused LDS %zu)",
-                                  plan.nj, plan.nitems, ipr, (size_t)plan.ldQ, plan.nqi, plan.qmaxlen, plan.kzmax,
-                                  eng->npl_slots, eng->slot_conflicts, eng->slot_store_conflicts,
-                                  fused_lds(eng, ((plan.off_zs + (size_t)plan.kzmax * eng->nj) + 127) & ~(size_t)127));
-                delete eng;
-                return r1 ? r1 : MDP_ENODEV;
-            }
-            // compile now the variant the first grid most likely runs (the
-            // fused kernel wherever its tables fit: every grid of at most one
-            // e block per column takes it), the other on demand (set_grid_dev)
-            const bool fused_first = eng->fused_mode == 1 ||
-                                     (eng->fused_mode == -1 && !vlds && !eng->qglobal &&
-                                      fused_lds(eng, plan.ct_max) <= kFusedLdsMax);
-            st_jit0 = st_now();
-            const int jrc = chunked ? jit_build_chunks(eng) : jit_build(eng, fused_first);
-            st_jit1 = st_now();
-            if (jrc == MDP_OK) eng->jit = true;
-            else fprintf(stderr, "midaspom: hipRTC specialisation failed, using the %s kernels:\n%s\n",
-                         vlds ? "wide" : "generic", eng->jit_log.c_str());
-        }
-        if (vlds && !eng->jit) {  // no specialised kernel after all: the wide kernels take the problem
-            eng->wide = true;
-            eng->qglobal = false;
-            eng->chunks.clear();
-        } else if (vlds) {
-            eng->variant = (eng->npmax <= 32 ? 32u : eng->npmax <= 64 ? 64u : 128u) * 100u + eng->deg;
-        }
-    }
-    if (eng->wide) {
-        if ((rc = build_wide_plan(eng, p))) {
-            delete eng;
-            return rc;
-        }
-        if (jit_check && ndev == 0) {
-            delete eng;
-            return mdp_set_error(MDP_ENODEV, "no HIP device available (wide path planned)");
-        }
     }
     std::vector<int> ids;
     if (n_devices == 0) {
@@ -4883,8 +3195,8 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
         }
     }
     if (st_on)
-        fprintf(stderr, "mdp setup (s): plan %.3f jit %.3f plan2 %.3f devices %.3f\n", st_jit0 - st0, st_jit1 - st_jit0,
-                st_dev0 - st_jit1, st_now() - st_dev0);
+        fprintf(stderr, "mdp setup (s): plan %.3f jit %.3f plan2 %.3f devices %.3f\n", st_jit[0] - st0, st_jit[1] - st_jit[0],
+                st_dev0 - st_jit[1], st_now() - st_dev0);
     *out = eng;
     return MDP_OK;
 }
@@ -5171,115 +3483,6 @@ int mdp_engine_launched(const mdp_engine *eng, char *buf, size_t len)
     }
     snprintf(buf, len, "%s", all.c_str());
     return (int)all.size();
-}
-
-int mdp_engine_get_info(const mdp_engine *eng, mdp_engine_info *info)
-{
-    if (!eng || !info) return mdp_set_error(MDP_EINVAL, "null argument");
-    info->n_devices = (int)eng->devs.size();
-    info->npairs = eng->npairs;
-    info->nuses = eng->nuses;
-    info->ncoef = eng->ncoef;
-    info->npmax = eng->npmax;
-    info->variant = eng->variant + (eng->jit ? 10000u : 0u);
-    return MDP_OK;
-}
-
-int mdp_engine_work(const mdp_engine *eng, uint64_t ne, uint64_t nc, double *flop_impl,
-                    double *flop_survey, double *bytes_min)
-{
-    if (!eng) return mdp_set_error(MDP_EINVAL, "null engine");
-    const double pts = (double)ne * (double)nc;
-    // k_forward per point: every use is a (D+1)-term dot product (2(D+1)
-    // flops) and one multiply-add into the state vector (2), plus the
-    // (D+1)-term weight setup and the final prior sum.
-    const double D = (double)eng->deg;
-    double per_pt = (double)eng->nuses * (2.0 * (D + 1.0) + 2.0) + 3.0 * (D + 1.0) +
-                    2.0 * (double)eng->npmax;
-    if (eng->jit) per_pt = eng->jit_flops_pt;  // the generated code's own count
-    if (eng->wide) per_pt = eng->hs ? eng->hs_flops_pt : eng->mmt ? eng->mmt_flops_pt : eng->wide_flops_pt;
-    if (flop_impl) *flop_impl = per_pt * pts;
-    // SURVEY.md §8(d) F_alg (dense-in-j formulation)
-    double fwd = 0;
-    for (uint32_t t = 1; t < eng->tmax; ++t) fwd += (double)eng->np[t - 1] * eng->np[t];
-    const double falg = 2.0 * eng->n * eng->nstates + (double)eng->nvar * eng->nstates * eng->nextid +
-                        2.0 * eng->nstates * eng->npairs + 2.0 * eng->np[0] * fwd;
-    if (flop_survey) *flop_survey = falg * pts;
-    // compulsory bytes of k_forward: its coefficient stream once per c, the
-    // e values, the output
-    if (bytes_min)
-        *bytes_min = 8.0 * ((double)nc * (eng->jit || eng->wide ? eng->ldQ : ldR_of(eng)) + (double)ne + pts);
-    return MDP_OK;
-}
-
-
-int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_work *w)
-{
-    if (!eng || !w) return mdp_set_error(MDP_EINVAL, "null argument");
-    *w = mdp_work{};
-    // per c value (the direct plan's tables; zero on the generic path, which
-    // has none): Z rows, var-column pressures, item factors, Q sums
-    double cmax = eng->devs.empty() ? 1.0 : eng->devs[0].zs_cmax;
-    if (!(cmax >= 0.0)) cmax = 1.0;  // no grid yet: the default [0, 1]
-    std::vector<double> large;
-    double coef[kZTerms];
-    for (uint32_t js = 0; js < eng->nj; ++js) {
-        z_split(eng, js, cmax, large, coef);
-        // fma(-c, s, 1) and one multiply per explicit column; the small
-        // columns' series: kZTerms FMAs, a multiply, the exp (counted 1)
-        w->z_c += 3.0 * (double)large.size() + (coef[0] != 0.0 ? 2.0 * kZTerms + 2.0 : 0.0);
-        w->pc_c += (double)eng->nvar;  // pC = c S[j][b] per var column
-    }
-    const uint32_t vmask = eng->nvar >= 32 ? ~0u : (1u << eng->nvar) - 1u;
-    for (uint32_t i = 0; i < eng->nitems; ++i) {
-        const uint32_t j = eng->cj_bits[eng->itemRow[i]], B = eng->itemB[i];
-        const uint32_t free = (uint32_t)__builtin_popcount(~j & vmask);
-        // 1 - pC where B_b = 0, one multiply per free column (the last one by Z)
-        w->item_c += (double)__builtin_popcount(~B & ~j & vmask) + (double)free;
-    }
-    for (size_t q = 0; q + 1 < eng->qstart.size(); ++q) {
-        const uint32_t len = eng->qstart[q + 1] - eng->qstart[q];
-        if (len > 1) w->q_c += (double)(len - 1);
-    }
-    // per grid point: the weight table, every use's (nX+1)-term dot product
-    // and its multiply-add into the state vector, the final prior sum
-    std::vector<int> wmax(kMaxDeg + 1, -1);
-    const std::vector<uint32_t> &ud = eng->udesc_d.empty() ? eng->udesc : eng->udesc_d;
-    std::set<uint32_t> distinct;  // one descriptor = one transition value P(e, c)
-    for (uint32_t d : ud) {
-        const uint32_t nX = (d >> kOffBits) & 31u, nA = d >> 27;
-        wmax[nA] = std::max(wmax[nA], (int)nX);
-        w->use_pt += 2.0 * nX + 3.0;
-        if (distinct.insert(d).second) w->use_pt_min += 2.0 * nX + 1.0;  // the dot product, once
-    }
-    // the state updates v'[l] = sum_k v[k] P[k][l]: npc (2 npp - 1) per year
-    for (uint32_t t = 1; t < eng->tmax; ++t) w->use_pt_min += (double)eng->np[t] * (2.0 * eng->np[t - 1] - 1.0);
-    w->weight_pt = 2.0 * eng->maxA;
-    for (int a = 0; a <= kMaxDeg; ++a)
-        if (wmax[a] >= 0) w->weight_pt += (double)(wmax[a] + 1);
-    w->final_pt = 2.0 * eng->np[eng->tmax - 1] - 1.0;
-    const double per_c = w->z_c + w->pc_c + w->item_c + w->q_c;
-    const double per_pt = w->weight_pt + w->use_pt + w->final_pt;
-    w->flop = (double)nc * per_c + (double)ne * (double)nc * per_pt;
-    w->flop_min_direct = (double)nc * per_c + (double)ne * (double)nc * (w->weight_pt + w->use_pt_min + w->final_pt);
-    // the ratio forms (ABI 8): per form from the plan, then the mean over the
-    // current grid's e rows (half s-form before a grid is set)
-    MdpJitPlan pl;
-    pl.np = eng->np;
-    pl.udesc = ud;
-    const MdpRatioWork rw = mdp_jit_ratio_work(pl);
-    double ns = 0.0, nall = 0.0;
-    for (const DevCtx &d : eng->devs) {
-        ns += d.ne_sform;
-        nall += d.ne;
-    }
-    const double fs = nall > 0.0 ? ns / nall : 0.5;
-    w->setup_pt = fs * rw.setup_s + (1.0 - fs) * rw.setup_t;
-    w->use_pt_ratio = fs * rw.use_s + (1.0 - fs) * rw.use_t;
-    w->final_pt_ratio = rw.final_pt;
-    w->pt_min = w->setup_pt + w->use_pt_ratio + w->final_pt_ratio;
-    w->flop_min = (double)nc * per_c + (double)ne * (double)nc * w->pt_min;
-    return MDP_OK;
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
  * occupancy-file parser, state enumeration, (e,c) grid, trapezoid
  * normalisation and the posterior writer.  These keep the reference's file
  * formats and numerics; the likelihood itself runs on
- * the GPU (spom_engine.hip).
+ * the GPU (spom_plan.cpp plans it, spom_engine.hip runs it).
  *
  * Reference regions (/root/reference/sources/main_MIDASPOM.c):
  *   mdp_model_load / parse_occupancy   :141-167  (n from line-1 separators,

@@ -37,6 +37,12 @@
 
 #include "spom_jit.h"
 
+// The HIP runtime's version query, as a weak reference: libmidaspom.so links
+// the runtime, so it resolves there as ever; a host-only program that links
+// this object without the runtime (plan_check, which never compiles) gets a
+// null address instead of an undefined symbol.
+extern "C" hipError_t hipRuntimeGetVersion(int *) __attribute__((weak));
+
 namespace {
 
 const char *kPrelude = R"SRC(
@@ -264,7 +270,7 @@ std::string power_expr(const std::string &base, uint32_t E, const std::string &t
 // here, so the bits are those of the canonical order.  Sets `a`.
 std::string qsum_flat_code(uint32_t qml, uint32_t qun)
 {
-    const uint32_t G = 8, ngm = (qml + G - 1) / G;  // = kQGroup (spom_engine.hip)
+    const uint32_t G = 8, ngm = (qml + G - 1) / G;  // = kQGroup (spom_engine.h)
     uint32_t ngp = 1;
     while (ngp < ngm) ngp *= 2;
     std::ostringstream o;
@@ -1087,7 +1093,7 @@ const std::string &toolchain_identity()
     std::call_once(once, [] {
         Dl_info di{};
         std::string dir;
-        if (dladdr((const void *)&hipRuntimeGetVersion, &di) && di.dli_fname) {
+        if (hipRuntimeGetVersion && dladdr((const void *)&hipRuntimeGetVersion, &di) && di.dli_fname) {
             dir = di.dli_fname;
             const size_t sl = dir.rfind('/');
             dir = sl == std::string::npos ? std::string(".") : dir.substr(0, sl);
@@ -1117,7 +1123,7 @@ const std::string &toolchain_identity()
 uint64_t jit_key(const std::string &src)
 {
     int rt = 0;
-    (void)hipRuntimeGetVersion(&rt);
+    if (hipRuntimeGetVersion) (void)hipRuntimeGetVersion(&rt);
     std::string k = src;
     k += '\0';
     for (const char *o : kJitOpts) (k += o) += ' ';

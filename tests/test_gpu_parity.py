@@ -417,8 +417,9 @@ def _big_obs(rng, missing, full=()):
 def test_big_years_vs_oracle(missing, full, path, monkeypatch):
     """Years of 512 and 1 024 states (9 and 10 unvisited patches; the
     reference expands any number, main_MIDASPOM.c:222-255, and propagates
-    them by dgemm, :371-384): k_fwd_mmt<2> / <1> on the matrix cores by
-    default (a wave takes 2 or 4 column tiles a year), k_fwd_wide when asked;
+    them by dgemm, :371-384): k_fwd_hs<2,9> / <1,10> through the hidden
+    states by default, k_fwd_mmt<2> / <1> on the matrix cores (a wave takes 2
+    or 4 column tiles a year) or k_fwd_wide when asked;
     one year, consecutive years, year 0 (Q3: ones over its states) and the
     last year, against the oracle on a whole 6 x 5 grid."""
     rng = np.random.default_rng(17 + sum(100 * y + k for y, k in missing.items()) + 7 * sum(full))

@@ -83,7 +83,7 @@ def test_wide_years_plan_offline(row0, wide, expect):
 
 @pytest.mark.skipif(gpu_available(), reason="offline planning check runs on CPU-only hosts")
 def test_qrows_slot_colouring_offline(tmp_path):
-    """k_qrows' Pc slots (spom_engine.hip build_direct_plan): coloured so the
+    """k_qrows' Pc slots (spom_plan.cpp build_direct_plan): coloured so the
     phase-3 gathers (16-lane groups, slots distinct mod 16) and the phase-2
     stores (8 consecutive items, distinct mod 8) meet few bank conflicts, in
     about as many slots as items.  Config 3: 416 gather groups, 236 store
