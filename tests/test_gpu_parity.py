@@ -417,10 +417,12 @@ def _big_obs(rng, missing, full=()):
 def test_big_years_vs_oracle(missing, full, path, monkeypatch):
     """Years of 512 and 1 024 states (9 and 10 unvisited patches; the
     reference expands any number, main_MIDASPOM.c:222-255, and propagates
-    them by dgemm, :371-384): k_fwd_hs<2,9> / <1,10> through the hidden
-    states by default, k_fwd_mmt<2> / <1> on the matrix cores (a wave takes 2
-    or 4 column tiles a year) or k_fwd_wide when asked;
-    one year, consecutive years, year 0 (Q3: ones over its states) and the
+    them by dgemm, :371-384).  The default ("default") is k_fwd_hs<2,9> /
+    <1,10> through the hidden states (at most 10 variable patches); only when
+    asked do k_fwd_mmt<2,512,1buf> / <1,1024,1buf> on the matrix cores
+    ("wide-mmt", MDP_WIDE_MMA=2: a wave takes 2 or 4 column tiles a year) or
+    k_fwd_wide ("wide-plain", MDP_WIDE_MMA=0) run; _wide_engine_run checks
+    which kernel was launched.  One year, consecutive years, year 0 (Q3: ones over its states) and the
     last year, against the oracle on a whole 6 x 5 grid."""
     rng = np.random.default_rng(17 + sum(100 * y + k for y, k in missing.items()) + 7 * sum(full))
     obs = _big_obs(rng, missing, full)
@@ -574,8 +576,12 @@ def test_config3_full_grid_sampled(golden):
 
 
 def test_grid_split_invariance(golden):
-    """Row slabs computed separately equal the full grid (the multi-GPU and
-    multi-rank partition relies on it)."""
+    """The same-variant row-slab case: row slabs computed separately equal the
+    full grid where every slab and the full grid (129 rows: one e block a
+    column) take the same fused kernel.  The slabs that change the kernel
+    choice -- fused, tall, the k_qrows width, chunk seams, the point list,
+    the block order -- and the column slabs under a c bound are
+    tests/test_gpu_partition.py's."""
     model = mdp.Model.load(golden / "config2_64x50.txt")
     g, _ = mdp.grid(129)
     with mdp.Engine(model) as eng:
