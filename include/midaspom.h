@@ -285,7 +285,9 @@ typedef struct mdp_scenario mdp_scenario;
 int mdp_scenario_create(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
                         mdp_scenario **out);
 /* Same with options (ABI 7): "MDP_SCN_BIG=1" / "MDP_SCN_ROW=1" force the
- * HBM-state / row-parallel kernel for any n they support (tests). */
+ * HBM-state / row-parallel kernel for any n they support (tests);
+ * "MDP_SCN_LAUNCH_PTS=N" caps the grid points per launch of those two
+ * kernels (tests: launch boundaries on small grids; 0 or unset = no cap). */
 int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
                              const char *options, mdp_scenario **out);
 void mdp_scenario_destroy(mdp_scenario *scenario);

@@ -208,7 +208,7 @@ ENGINE_OPTION_NAMES = (
     "MDP_WIDE_MMA", "MDP_HS_RADIX", "MDP_HS_WAVES",
     # measurement-only: accepted by the diag build alone
     "MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")
-SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW")
+SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW", "MDP_SCN_LAUNCH_PTS")
 
 
 DIAG_OPTION_NAMES = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")

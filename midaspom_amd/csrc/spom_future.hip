@@ -435,8 +435,8 @@ int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, u
             pcum[i] = acc;
             if (std::isnan(acc) && lv == pcum.size()) lv = i;
         }
-    for (size_t i = 1; i < lv; ++i)
-        if (pcum[i] < pcum[i - 1]) {
+    for (size_t i = 0; i < lv; ++i)
+        if (pcum[i] < (i ? pcum[i - 1] : 0.0)) {
             delete f;
             return mdp_set_error(MDP_EUNSUPPORTED, "posterior with negative entries (cell %zu): the sampler "
                                  "needs a non-decreasing cumulative sum", i);

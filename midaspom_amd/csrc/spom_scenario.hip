@@ -47,6 +47,7 @@ constexpr uint32_t kBigMaxN = 16;      // k_scn_big: state vectors in HBM
 constexpr int kBigBlock = 256;
 constexpr size_t kBigScratch = 1ull << 30;  // k_scn_big state-vector scratch per launch (bytes)
 constexpr int kRowBlock = 256;              // k_scn_row: one grid point per workgroup
+constexpr size_t kRowPer = (size_t)1 << 22;  // k_scn_row: points per launch
 constexpr uint32_t kRowMaxN = 12;           // k_scn_row: 2 x 2^n states + 3 n x 256 per-lane values in LDS
 
 #define SCN_TRY(expr)                                                                        \
@@ -96,6 +97,17 @@ __host__ __device__ constexpr int sup_rank(int NL, int jl, int bl)
     for (int b = NL - 1; b >= 0; --b)
         if (!((jl >> b) & 1)) r = 2 * r + ((bl >> b) & 1);
     return r;
+}
+
+// Colonisation pressure of the loss scenario before the cap, loss.c:95-98:
+// s1 += M[n][k] * Ksource; pC = c * s1 -- the product is rounded before it is
+// added (the reference is built without FMA contraction), so that pC, and
+// with it 1 - pC, is the reference's own double
+__device__ __forceinline__ double loss_pc(double c, double s, double src, double K)
+{
+#pragma clang fp contract(off)
+    const double sk = src * K;
+    return c * (s + sk);
 }
 
 // acc + (lane K of this lane's row of 16)'s f * x: v_fmac_f64 with a DPP
@@ -211,7 +223,7 @@ __global__ __launch_bounds__(kScnBlock) void k_scn(ScnArgs a, const double *__re
             const uint32_t i = tid + u * kScnBlock, j = i / N, k = i - j * N;
             double v = 0.0;
             if (!((j >> (N - 1 - k)) & 1u)) {
-                v = src ? c * (sv[u] + sr[u] * K) : c * sv[u] * Kpc;
+                v = src ? loss_pc(c, sv[u], sr[u], K) : c * sv[u] * Kpc;
                 v = v > 1.0 ? 1.0 : v;
             }
             if (i < (uint32_t)(NS * N)) pc[i] = v;
@@ -537,7 +549,7 @@ __global__ __launch_bounds__(kBigBlock) void k_scn_big(ScnArgs a, const double *
                     const uint32_t k = n - 1 - (uint32_t)__builtin_ctz(fb);
                     fb &= fb - 1;
                     const double sv = Sc[(size_t)j * n + k];
-                    double p = src ? c * (sv + src[k] * K) : c * sv * Kpc;  // dieoff.c:78, loss.c:98
+                    double p = src ? loss_pc(c, sv, src[k], K) : c * sv * Kpc;  // dieoff.c:78, loss.c:98
                     p = p > 1.0 ? 1.0 : p;
                     w1[L] = p;
                     w0[L] = 1.0 - p;
@@ -634,7 +646,7 @@ __global__ __launch_bounds__(kRowBlock) void k_scn_row(ScnArgs a, const double *
                     const uint32_t k = n - 1 - (uint32_t)__builtin_ctz(fb);
                     fb &= fb - 1;
                     const double sv = S[(size_t)j * n + k];
-                    double p = src ? c * (sv + src[k] * K) : c * sv * Kpc;  // dieoff.c:78, loss.c:98
+                    double p = src ? loss_pc(c, sv, src[k], K) : c * sv * Kpc;  // dieoff.c:78, loss.c:98
                     p = p > 1.0 ? 1.0 : p;
                     w1[L * kRowBlock] = p;
                     w0[L * kRowBlock] = 1.0 - p;
@@ -741,6 +753,8 @@ struct mdp_scenario {
     // k_scn_row (8 < n <= 12, or MDP_SCN_ROW=1): rows by decreasing free-patch count
     bool row = false;
     uint32_t *djord = nullptr;
+    // MDP_SCN_LAUNCH_PTS: cap on the points per k_scn_big / k_scn_row launch (0: none)
+    size_t launch_pts = 0;
 };
 
 namespace {
@@ -771,9 +785,10 @@ int scn_launch(mdp_scenario *sc, double *dout, hipStream_t st, int which)
             const double *y0 = mode ? sc->dV : sc->dw;
             double *o = mode ? dout : sc->dV;
             const size_t tot = mode ? (size_t)sc->ne * sc->nc * sc->nK * sc->nd : (size_t)sc->nc * sc->ne;
-            constexpr size_t kPer = (size_t)1 << 22;  // points per launch (grid of < 2^32 threads)
-            for (size_t p0 = 0; p0 < tot; p0 += kPer) {  // one workgroup per point
-                const uint32_t nb = (uint32_t)std::min(kPer, tot - p0);
+            // points per launch (grid of < 2^32 threads), or the MDP_SCN_LAUNCH_PTS cap
+            const size_t per = sc->launch_pts ? std::min(sc->launch_pts, kRowPer) : kRowPer;
+            for (size_t p0 = 0; p0 < tot; p0 += per) {  // one workgroup per point
+                const uint32_t nb = (uint32_t)std::min(per, tot - p0);
                 hipLaunchKernelGGL(k_scn_row, dim3(nb), dim3(kRowBlock), row_lds(sc->n), st, a, sc->dS, y0, sc->de,
                                    sc->dc, sc->dK, sc->dsr, sc->djord, p0, o);
             }
@@ -846,14 +861,17 @@ int mdp_scenario_create(const int32_t *row, uint32_t n, double m, float p, doubl
 }
 
 // options (ABI 7): "MDP_SCN_BIG=1" / "MDP_SCN_ROW=1" force the HBM-state or
-// the row-parallel kernel (tests pin the kernels against each other); the
-// library reads no environment
+// the row-parallel kernel (tests pin the kernels against each other);
+// "MDP_SCN_LAUNCH_PTS=N" caps the grid points per launch of those two kernels
+// (tests cross launch boundaries on small grids; 0 = no cap).  The library
+// reads no environment
 int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
                              const char *options, mdp_scenario **out)
 {
     if (!row || !out || n == 0) return mdp_set_error(MDP_EINVAL, "null argument");
     *out = nullptr;
     bool force_big = false, force_row = false;
+    long launch_pts = 0;
     if (options) {
         std::string cur;
         for (const char *c = options;; ++c) {
@@ -864,6 +882,8 @@ int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, 
                     const bool on = eq == std::string::npos || atoi(cur.c_str() + eq + 1) != 0;
                     if (k == "MDP_SCN_BIG") force_big = on;
                     else if (k == "MDP_SCN_ROW") force_row = on;
+                    else if (k == "MDP_SCN_LAUNCH_PTS")
+                        launch_pts = eq == std::string::npos ? 0 : atol(cur.c_str() + eq + 1);
                     else return mdp_set_error(MDP_EINVAL, "unknown scenario option '%s'", k.c_str());
                     cur.clear();
                 }
@@ -889,6 +909,7 @@ int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, 
     sc->m = m;
     sc->d = d;
     sc->device = device;
+    sc->launch_pts = launch_pts > 0 ? std::min((size_t)launch_pts, (size_t)1 << 32) : 0;
     // n > 8: the LDS-resident k_scn does not fit; 8 < n <= 12: k_scn_row
     // (option MDP_SCN_ROW=1 forces it for any n <= 12); n > 12: k_scn_big
     // (MDP_SCN_BIG=1 forces it for any n)
@@ -1048,6 +1069,8 @@ int mdp_scenario_set_grid(mdp_scenario *sc, int ts, int tdis, const double *e, u
         const size_t tot = std::max((size_t)ne * nc * nK * nd, (size_t)nc * ne);
         size_t pts = kBigScratch / (2 * (size_t)ns * sizeof(double));
         pts = std::max<size_t>(kBigBlock, std::min(pts, tot + kBigBlock - 1) / kBigBlock * kBigBlock);
+        if (sc->launch_pts)  // the cap, rounded up to whole blocks
+            pts = std::min(pts, (sc->launch_pts + kBigBlock - 1) / kBigBlock * kBigBlock);
         sc->big_pts = (uint32_t)std::min<size_t>(pts, (size_t)65535 * kBigBlock);
         if (hipMalloc((void **)&sc->dY, 2 * (size_t)ns * sc->big_pts * sizeof(double)) != hipSuccess) {
             scn_free_grid(sc);
