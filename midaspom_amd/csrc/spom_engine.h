@@ -62,8 +62,16 @@ constexpr int kJitKblockTall = 512;  // threads of the reading kernel's tall var
 // ---------------------------------------------------------------------------
 // types
 // ---------------------------------------------------------------------------
+// a kernel instantiation a context has noted (note_launch): the launch
+// site's format string, by address, and its arguments
+struct LaunchNote {
+    const char *fmt;
+    uint64_t a[4];
+};
+
 struct DevCtx {
     int device = 0;
+    mutable std::vector<LaunchNote> noted;  // what this context has reported to mdp_engine::launched
     hipStream_t stream = nullptr;
     double *S = nullptr;
     uint32_t *var_cols = nullptr, *row_col = nullptr;
@@ -77,6 +85,11 @@ struct DevCtx {
     // (bit 31: a duplicate that is computed, not stored), grouped by ratio form
     uint32_t *plist = nullptr;
     size_t cap_plist = 0;
+    // e by list position, then e[0] (what a position past the list reads): a
+    // listed kernel loads its e values by position, beside the list, instead
+    // of through it (position -> row -> e would be two round trips in series)
+    double *elist = nullptr;
+    size_t cap_elist = 0;
     uint32_t nlist = 0, nlist_epl = 0;  // list length (a multiple of nlist_epl, its points per lane)
     bool plist_identity = true;          // the list is 0, 1, ... (nothing uploaded; plist passed as null)
     double *ZPV = nullptr, *R = nullptr, *out = nullptr, *gpart = nullptr;

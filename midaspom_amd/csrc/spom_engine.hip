@@ -2222,19 +2222,37 @@ const char *const kKernelNames[3][3] = {{"k_zpv", "k_coefs", "k_forward"},
                                         {"k_zrows", "k_qrows", "k_forward"},
                                         {"k_zrows", "k_witems+k_wq", "k_fwd_wide"}};
 
-// record a launched kernel instantiation ("k_qrows<16,0,2>", ...)
-void note_launch(const mdp_engine *eng, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-void note_launch(const mdp_engine *eng, const char *fmt, ...)
+// record a launched kernel instantiation ("k_qrows<16,0,2>", ...): the name
+// is formatted and looked up in the engine's set (fmt is a launch site's
+// literal, handed on by note_launch)
+void note_launch_fmt(const mdp_engine *eng, const char *fmt, ...)
 {
     char b[96];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(b, sizeof b, fmt, ap);
     va_end(ap);
-    // look up before inserting: the hot path re-launches the same kernels, so
-    // after the first launch of each this allocates nothing
     std::lock_guard<std::mutex> lk(eng->launched_mu);
     if (eng->launched.find(b) == eng->launched.end()) eng->launched.emplace(b);
+}
+
+inline uint64_t note_arg(const char *s) { return (uint64_t)(uintptr_t)s; }  // (a string literal: by address)
+template <typename T>
+inline uint64_t note_arg(T v) { return (uint64_t)v; }
+
+// Every launch site notes its instantiation, so on the hot path this runs
+// once per kernel launch: a context remembers the (format, arguments) it has
+// noted -- a few words compared in place, no formatting, lock or allocation
+// -- and only one it has not seen yet goes through note_launch_fmt.
+template <typename... A>
+inline void note_launch(const mdp_engine *eng, const DevCtx &d, const char *fmt, A... a)
+{
+    static_assert(sizeof...(A) <= 4, "LaunchNote holds four arguments");
+    const LaunchNote n{fmt, {note_arg(a)...}};
+    for (const LaunchNote &m : d.noted)
+        if (m.fmt == n.fmt && memcmp(m.a, n.a, sizeof n.a) == 0) return;
+    d.noted.push_back(n);
+    note_launch_fmt(eng, fmt, a...);
 }
 
 // the k_fwd_mma instantiation of the engine's plan
@@ -2557,7 +2575,7 @@ void free_device(DevCtx &d)
     void *ptrs[] = {d.S, d.var_cols, d.row_col, d.pairA, d.pairB, d.pairOff, d.udesc, d.prog,
                     d.pairPart0, d.partP, d.partK0, d.e, d.c, d.ZPV, d.R, d.out, d.gpart,
                     d.zs, d.zsq, d.sv, d.Qrow, d.Zg, d.coltab, d.items, d.itemB, d.qstart, d.qitem,
-                    d.Pg, d.V, d.np_d, d.udesc_w, d.zc, d.plist, d.qslot, d.qlane, d.islot,
+                    d.Pg, d.V, d.np_d, d.udesc_w, d.zc, d.plist, d.elist, d.qslot, d.qlane, d.islot,
                     d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan,
                     d.mmt_kt, d.mmt_ktile, d.mmt_wplan, d.mmt_cidx,
                     d.hs_kt, d.hs_cidx, d.hs_pbase, d.hs_ppos, d.hs_dpos, d.hs_dbase, d.hs_pk,
@@ -2671,6 +2689,11 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
             if (!d.plist_identity) {  // an identity list is not uploaded: the kernels use the position
                 if ((rc = dev_reserve(&d.plist, &d.cap_plist, pl.size()))) return rc;
                 HIP_TRY(hipMemcpy(d.plist, pl.data(), pl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+                std::vector<double> el(pl.size() + 1);
+                for (size_t i = 0; i < pl.size(); ++i) el[i] = ne ? e[pl[i] & 0x7fffffffu] : 0.0;  // (no rows: never run)
+                el[pl.size()] = ne ? e[0] : 0.0;
+                if ((rc = dev_reserve(&d.elist, &d.cap_elist, el.size()))) return rc;
+                HIP_TRY(hipMemcpy(d.elist, el.data(), el.size() * sizeof(double), hipMemcpyHostToDevice));
             }
             d.nlist = (uint32_t)pl.size();
         } else {
@@ -2739,7 +2762,7 @@ void launch_fwd_epl(const mdp_engine *eng, const DevCtx &d, double *out, OutStri
     uint32_t se = os.se, sc = os.sc;
     dim3 grid(d.nc, (d.ne + kBlock * EPL - 1) / (kBlock * EPL));
     const uint32_t nprog = (uint32_t)eng->prog.size() - 1;
-    note_launch(eng, "%s<%d,%d,%d>", eng->fwd_lds ? "k_forward_lds" : "k_forward", NP, DEG, EPL);
+    note_launch(eng, d, "%s<%d,%d,%d>", eng->fwd_lds ? "k_forward_lds" : "k_forward", NP, DEG, EPL);
     if (eng->fwd_lds)
         MDP_LAUNCH((k_forward_lds<NP, DEG, EPL>), grid, dim3(kBlock), eng->fwd_lds_bytes, s,
                            d.R, ldR_of(eng), d.prog, nprog, eng->np[0], eng->prior0, d.e, d.ne, out, se,
@@ -2798,15 +2821,21 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
         uint32_t nlist = epl > 1 ? d.nlist : d.ne;
         if (epl > 1 && ((!plist && !d.plist_identity) || d.nlist_epl % epl))
             return mdp_set_error(MDP_EINVAL, "no point list for %u points per lane", epl);
-        void *args[] = {(void *)&Qrow, (void *)&prior0, (void *)&ev,  (void *)&ne,   (void *)&nc,
-                        (void *)&out,  (void *)&se,     (void *)&one, (void *)&st,   (void *)&cv,
-                        (void *)&ctab, (void *)&ctl,    (void *)&kmax, (void *)&vscr, (void *)&ldv,
-                        (void *)&qidx, (void *)&sc,     (void *)&plist, (void *)&nlist};
         const uint64_t gy = (nlist + kb * epl - 1) / (kb * epl);
         const uint32_t fc = d.fused ? (uint32_t)eng->jit_plan.fused_cols : 1u;
         const uint64_t nb = gy * ((d.nc + fc - 1) / fc);  // e blocks x column groups
         if (nb * kb * fc * spl > 0xffffffffull)
             return mdp_set_error(MDP_EUNSUPPORTED, "grid %u x %u too large", d.ne, d.nc);
+        // mdp_fwd_jit's signature (spom_jit.cpp): the table the variant
+        // stages first, then what its front reads, the workgroup count, the
+        // chunk's gather list and what only its end reads
+        const double *tab = d.fused ? ctab : Qrow;
+        if (plist) ev = d.elist;  // a listed kernel reads e by list position
+        uint32_t nblk = (uint32_t)nb;
+        void *args[] = {(void *)&tab,   (void *)&cv,   (void *)&ev,  (void *)&ctl,  (void *)&nlist,
+                        (void *)&ne,    (void *)&nc,   (void *)&plist, (void *)&nblk, (void *)&kmax,
+                        (void *)&one,   (void *)&qidx, (void *)&out, (void *)&se,   (void *)&sc,
+                        (void *)&prior0, (void *)&vscr, (void *)&ldv, (void *)&st};
         if (!eng->chunks.empty()) {  // a long series: its chunks in order on the stream
             const size_t nch = d.cfn.size();
             if (nch != eng->chunks.size() || d.cqidx.size() != nch)
@@ -2817,15 +2846,15 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
                                                  nullptr, i == 0 ? t_kev.start : nullptr,
                                                  i + 1 == nch ? t_kev.stop : nullptr, 0));
             }
-            note_launch(eng, "mdp_fwd_jit<reading,maxA%u,chunks%zu%s>", eng->maxA, nch,
+            note_launch(eng, d, "mdp_fwd_jit<reading,maxA%u,chunks%zu%s>", eng->maxA, nch,
                         eng->chunks[0].qidx.empty() ? "" : ",gather");
             return MDP_OK;
         }
         const uint32_t dyn = d.fused ? (d.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
         HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[d.fused ? 1 : d.tall ? 2 : 0], (uint32_t)(nb * kb * fc * spl * pro), 1, 1,
                                          kb * fc * spl * pro, 1, 1, dyn, s, args, nullptr, t_kev.start, t_kev.stop, 0));
-        note_launch(eng, "mdp_fwd_jit<%s,maxA%u>", d.fused ? "fused" : "reading", eng->maxA);
-        if (d.tall) note_launch(eng, "mdp_fwd_jit<reading,kb%d>", kJitKblockTall);
+        note_launch(eng, d, "mdp_fwd_jit<%s,maxA%u>", d.fused ? "fused" : "reading", eng->maxA);
+        if (d.tall) note_launch(eng, d, "mdp_fwd_jit<reading,kb%d>", kJitKblockTall);
         return MDP_OK;
     }
     switch (eng->variant / 100) {
@@ -2844,7 +2873,7 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
 template <bool LDSZ, bool LDSP, int NV>
 void launch_coefs_nv(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
 {
-    note_launch(eng, "k_coefs<%d,%d,%d>", (int)LDSZ, (int)LDSP, NV);
+    note_launch(eng, d, "k_coefs<%d,%d,%d>", (int)LDSZ, (int)LDSP, NV);
     MDP_LAUNCH((k_coefs<LDSZ, LDSP, NV>), dim3(d.nc), dim3(kBlock), eng->coef_lds, s, d.ZPV,
                        eng->nstates, eng->nvar, d.pairA, d.pairB, d.pairOff, d.pairPart0, eng->npairs,
                        d.partP, d.partK0, (uint32_t)eng->partP.size(), eng->ncoef, d.udesc,
@@ -2880,7 +2909,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
     auto witems = [&](uint32_t c0, uint32_t n, uint32_t ldp) {
         const dim3 gi((eng->nitems + kBlock - 1) / kBlock, n);
 #define MDP_WITEMS(NV) \
-    do { note_launch(eng, "k_witems<%d>", NV); \
+    do { note_launch(eng, d, "k_witems<%d>", NV); \
     hipLaunchKernelGGL((k_witems<NV>), gi, dim3(kBlock), 0, s, d.c, d.nc, c0, eng->nvar, d.Zg, d.sv, eng->nitems, d.items, d.Pg, ldp); } while (0)
         if (eng->nvar <= 8) MDP_WITEMS(8);
         else if (eng->nvar <= 16) MDP_WITEMS(16);
@@ -2902,7 +2931,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
                 if (!one && eng->nitems) witems(c0, n, ldp);
                 const uint64_t nbk = (uint64_t)npb * n;
                 if (nbk > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_hs workgroups", (unsigned long long)nbk);
-                note_launch(eng, "k_fwd_hs<%u,%u>", rt, nb);
+                note_launch(eng, d, "k_fwd_hs<%u,%u>", rt, nb);
 #define MDP_HS(RT, NB, NW) \
     hipLaunchKernelGGL((k_fwd_hs<RT, NB, NW>), dim3((uint32_t)nbk), dim3(NW * 64), hs_lds(eng), s, d.Pg, ldp, c0, d.np_d, \
                        d.hs_kt, d.hs_cidx, d.hs_wplan, d.hs_pass, d.hs_pbase, d.hs_ppos, d.hs_dpos, \
@@ -2920,7 +2949,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
             const uint32_t n = std::min(cb, d.nc - c0);
             witems(c0, n, eng->nitems);
             const dim3 gq((uint32_t)((eng->ldQ + kBlock - 1) / kBlock), n);
-            note_launch(eng, "k_wq");
+            note_launch(eng, d, "k_wq");
             hipLaunchKernelGGL(k_wq, gq, dim3(kBlock), 0, s, c0, eng->nitems, d.Pg, eng->ncoef_d, d.qstart, d.qitem,
                                d.Qrow, (uint32_t)eng->ldQ);
         }
@@ -2929,7 +2958,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
         const bool db = mmt_shape(eng).db;
         const uint64_t nb = (uint64_t)npb * d.nc;
         if (nb > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_mmt workgroups", (unsigned long long)nb);
-        note_launch(eng, "k_fwd_mmt<%u,%u,%s>", rt, rows, db ? "2buf" : "1buf");
+        note_launch(eng, d, "k_fwd_mmt<%u,%u,%s>", rt, rows, db ? "2buf" : "1buf");
 #define MDP_MMT(RT, ROWS, DB) \
     hipLaunchKernelGGL((k_fwd_mmt<RT, ROWS, DB>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, \
                        d.np_d, d.mmt_kt, d.mmt_cidx, d.mmt_ktile, d.mmt_wplan, eng->tmax, eng->prior0, d.e, d.ne, \
@@ -2945,7 +2974,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
             const uint32_t n = std::min(65535u, d.nc - c0);
             const uint32_t pts = mma_pts(eng->mma_npm);
             const dim3 g((d.ne + pts - 1) / pts, n);
-            note_launch(eng, "k_fwd_mma<%u>", eng->mma_npm);
+            note_launch(eng, d, "k_fwd_mma<%u>", eng->mma_npm);
 #define MDP_MMA(NPM) \
     hipLaunchKernelGGL((k_fwd_mma<NPM>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, d.np_d, \
                        d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan, eng->tmax, eng->prior0, d.e, d.ne, c0, eng->maxA, \
@@ -2961,7 +2990,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
         for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
             const uint32_t n = std::min(cb, d.nc - c0);
             const dim3 g((d.ne + kBlock - 1) / kBlock, n);
-            note_launch(eng, "k_fwd_wide");
+            note_launch(eng, d, "k_fwd_wide");
             hipLaunchKernelGGL(k_fwd_wide, g, dim3(kBlock), wide_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, d.udesc_w,
                                d.np_d, eng->tmax, eng->prior0, d.e, d.ne, c0, eng->maxA, d.V, eng->npmax, out, se, sc);
         }
@@ -2989,7 +3018,7 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
     if ((eng->jit || eng->wide) && k == 0) {  // Z rows
         const uint32_t kmax = d.zs_kmax;
         const dim3 grid((d.nc + 64 * kZC - 1) / (64 * kZC), (eng->nj + kZRows - 1) / kZRows);
-        note_launch(eng, "k_zrows");
+        note_launch(eng, d, "k_zrows");
         MDP_LAUNCH(k_zrows, grid, dim3(kBlock), (size_t)kZRows * kmax * sizeof(double), s, d.c, d.nc, eng->nj,
                    kmax, d.zs, d.zc, d.Zg);
         HIP_TRY(hipGetLastError());
@@ -3002,7 +3031,7 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
         const size_t lds = qrows_lds(eng, cb);
 #define MDP_QROWS_CB(NV, EX, CB)                                                                        \
     do {                                                                                                \
-    note_launch(eng, "k_qrows<%d,%d,%d>", NV, (int)EX, CB);                                              \
+    note_launch(eng, d, "k_qrows<%d,%d,%d>", NV, (int)EX, CB);                                              \
     MDP_LAUNCH((k_qrows<NV, EX, CB>), grid, dim3(kQrowsBlock), lds, s, d.c, d.nc, eng->nvar, eng->nj,         \
                d.zs_kmax, d.zsq, d.zc, d.sv, eng->nitems, d.items, eng->ncoef_d, d.qstart,                     \
                (uint32_t)eng->qitem.size(), d.qitem, d.Qrow, (uint32_t)eng->ldQ, d.stamps[1],                 \
@@ -3029,7 +3058,7 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
     }
     if (k == 0) {
         dim3 grid((eng->nstates + kZpvJ - 1) / kZpvJ, (d.nc + kZpvCT - 1) / kZpvCT);
-        note_launch(eng, "k_zpv");
+        note_launch(eng, d, "k_zpv");
         MDP_LAUNCH(k_zpv, grid, dim3(kBlock), 0, s, d.S, eng->nstates, eng->n - eng->nvar, eng->nvar, d.c,
                    d.nc, d.ZPV, d.stamps[0]);
         HIP_TRY(hipGetLastError());

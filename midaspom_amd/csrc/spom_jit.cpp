@@ -385,6 +385,12 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
     // stored as one 16-byte store per row through LDS) was measured slower on
     // configs 2 and 3, so the reading variant takes one.
     const int FC = pl.fused ? (pl.fused_cols > 0 ? pl.fused_cols : 1) : 1;
+    // 16-byte staging loads per thread of the fused kernel's table image (NSTG)
+    const uint32_t nstg_nt = (uint32_t)(pl.kblock * pl.fused_cols * std::max(1, pl.pro));
+    const uint32_t nt_all = (uint32_t)((pl.kblock > 0 ? pl.kblock : 256) * FC *
+                                       (pl.vlds && (pl.vsplit == 2 || pl.vsplit == 4) ? pl.vsplit : 1) *
+                                       (pl.fused && pl.pro > 1 ? pl.pro : 1));  // NT
+    const uint32_t nstg = pl.fused ? std::max<uint32_t>(1u, (pl.ct_max / 2 + nstg_nt - 1) / nstg_nt) : 0u;
     // target split (vlds): SPL waves per 64 points, wave group `half`
     // accumulating the new states l with l % SPL == half
     const int SPL = pl.vlds && (pl.vsplit == 2 || pl.vsplit == 4) ? pl.vsplit : 1;
@@ -403,20 +409,42 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
     }
     o << "extern \"C\" __global__ __launch_bounds__(NT) "
       << (pl.wpe > 0 ? "__attribute__((amdgpu_waves_per_eu(" + std::to_string(pl.wpe) + "))) " : std::string())
+      // Everything read ahead of the first barrier comes first and contiguous
+      // -- 14 SGPRs, the kernel-argument preload's reach, so with the preload
+      // the front of the kernel waits for no scalar load: the table the
+      // variant stages (the fused kernel's column tables, else the Q rows),
+      // c, e, the sizes, the point list, the workgroup count (an argument: the
+      // hidden gridDim.x is one more scalar round trip) and kmax; then one,
+      // the gather list and what only the end of the kernel reads.  Every
+      // pointer the kernel only reads stays const __restrict__: the code
+      // object then marks the argument read-only, and the runtime launches a
+      // kernel with a writable table argument measurably slower (config 2:
+      // 8.4 -> 11.0 us a step, the first phase 2 250 -> 6 130 cycles with the
+      // same instructions; profiles/r07).
       << "void mdp_fwd_jit(\n"
-         "    const double *__restrict__ Qrow, double prior0, const double *__restrict__ evals, u32 ne, u32 nc,\n"
-         "    double *__restrict__ out, u32 ld_out, u32 one, unsigned long long *__restrict__ stamps,\n"
-         "    const double *__restrict__ cvals, const double *__restrict__ coltab, u32 ct_len, u32 kmax,\n"
-         "    double *__restrict__ vscr, u32 ldv, const u32 *__restrict__ qidx, u32 out_cs,\n"
-         "    const u32 *__restrict__ plist, u32 nlist)\n{\n"
+         "    const double *__restrict__ " << (pl.fused ? "coltab" : "Qrow") << ", const double *__restrict__ cvals,\n"
+         "    const double *__restrict__ evals, u32 ct_len, u32 nlist, u32 ne, u32 nc,\n"
+         "    const u32 *__restrict__ plist, u32 nblk, u32 kmax, u32 one, const u32 *__restrict__ qidx,\n"
+         "    double *__restrict__ out, u32 ld_out, u32 out_cs, double prior0,\n"
+         "    double *__restrict__ vscr, u32 ldv, unsigned long long *__restrict__ stamps)\n{\n"
          // the Q rows in stored order, then the same rows with every group
          // reversed (read by t-form lanes; see the ratio forms above)
       << "    __shared__ __attribute__((aligned(16))) double Ql[2 * FC * LDQ + 2];\n"
-      << stamp(6) << stamp(0) <<
+      << stamp(6) << stamp(0);
+    // The fused kernel's table image: the kernel's first loads, all in flight,
+    // ahead even of the block's place in the grid.
+    if (pl.fused) {
+        o << "    extern __shared__ __attribute__((aligned(16))) double ct[];\n"
+             "    const u32 n2 = ct_len / 2;\n";
+        for (uint32_t k = 0; k < nstg; ++k)
+            o << "    const u32 si" << k << "_ = threadIdx.x + " << k << " * NT;\n"
+              << "    const double2 stg" << k << "_ = ((const double2 *)coltab)[si" << k << "_ < n2 ? si" << k << "_ : 0];\n";
+    }
+    o <<
          // XCD-aware order: the dispatcher deals blocks round-robin over the 8
          // XCDs, so consecutive logical blocks (adjacent c columns of the
          // output rows) are given to one XCD and its L2 assembles whole lines
-         "    const u32 nb = gridDim.x, full = nb & ~7u;\n"
+         "    const u32 nb = nblk, full = nb & ~7u;\n"
       << (pl.xcd ? "    const u32 lb = blockIdx.x < full ? (blockIdx.x & 7u) * (full >> 3) + (blockIdx.x >> 3) : blockIdx.x;\n"
                  : "    const u32 lb = blockIdx.x + 0 * full;\n") <<
          // FC columns per workgroup (fused variant): KBLOCK threads each
@@ -431,27 +459,62 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
       << (pl.efast ? "    const u32 gy = (nlist + KBLOCK * EPL - 1) / (KBLOCK * EPL), ic0 = lb / gy * FC, by = lb % gy;\n"
                    : "    const u32 ncb = (nc + FC - 1) / FC, ic0 = lb % ncb * FC, by = lb / ncb;\n")
       << (SPL > 1 || FC == 1 ? "    const u32 ic = ic0;\n" : "    const u32 ic = ic0 + half;\n")
-      << (SPL > 1 ? "    const double *Qh = Ql;\n" : "    const double *Qh = Ql + half * LDQ;\n") <<
-         // this lane's points: issued first, their latency hides under the
-         // prologue.  One point per lane: e row by * KBLOCK + tid.  Several:
-         // list positions pp = by * KBLOCK * EPL + tid * EPL + i, each naming
-         // an e row (plist; bit 31: a duplicate that computes but does not
-         // store), the host's list putting only points of one ratio form in a
-         // lane (set_grid_dev) so that they share their coefficient reads
-         "    u32 ie[EPL], pp[EPL];\n    bool st[EPL];\n    double ev[EPL];\n"
+      << (SPL > 1 ? "    const double *Qh = Ql;\n" : "    const double *Qh = Ql + half * LDQ;\n");
+    // The front of the kernel is one dependent chain of memory round trips if
+    // it is written the obvious way, so its order is fixed here: each
+    // variant issues the loads its first barrier waits for (the staging
+    // loads) first, then `front` below, then its stores.  No load ahead of
+    // the first barrier sits in an exec-masked branch (the compiler drains
+    // vmcnt at each one's join): an index past the end is clamped and the
+    // value selected afterwards.
+    //
+    // front: (1) this lane's points.  One point per lane: e row
+    // by * KBLOCK + tid.  Several: list positions
+    // pp = by * KBLOCK * EPL + tid * EPL + i, each naming an e row (plist;
+    // bit 31: a duplicate that computes but does not store), the host's list
+    // putting only points of one ratio form in a lane (set_grid_dev) so that
+    // they share their coefficient reads.  No list is the identity, which a
+    // sorted grid with an even number of s-form rows is.  With a list `evals`
+    // holds e by list position (set_grid_dev), so the e load never waits for
+    // the list's: the rows (needed for the flags and the final store) are
+    // read beside it in a workgroup-uniform branch.  (2) What only the rest
+    // of the kernel reads, held in registers from here on, while the staging
+    // loads are in flight: an argument first read after a barrier is a scalar
+    // round trip every wave of the block waits for.
+    const std::string front = std::string(
+         "    u32 ie[EPL], pp[EPL];\n    bool st[EPL];\n    double ev[EPL];\n") +
+         (EPL == 1 ? "    pp[0] = by * KBLOCK + tip;\n"
+                     "    ie[0] = pp[0];\n"
+                     "    st[0] = ie[0] < ne;\n"
+                     "    ev[0] = evals[st[0] ? ie[0] : 0u];\n"
+                   : "    u32 q_[EPL];\n"
+                     "#pragma unroll\n"
+                     "    for (int i = 0; i < EPL; ++i) {\n"
+                     "        pp[i] = by * (KBLOCK * EPL) + tip * EPL + i;\n"
+                     "        q_[i] = pp[i] < nlist ? pp[i] : 0x80000000u;\n"
+                     // with a list `evals` is e by list position, then e[0]
+                     // (what the row 0 of a position past the list reads)
+                     "        const u32 j_ = q_[i] & 0x7fffffffu;\n"
+                     "        ev[i] = evals[plist ? (pp[i] < nlist ? pp[i] : nlist) : (j_ < ne ? j_ : 0u)];\n"
+                     "    }\n"
+                     "    if (plist) {\n"
+                     "#pragma unroll\n"
+                     "        for (int i = 0; i < EPL; ++i) {\n"
+                     "            const u32 l_ = plist[pp[i] < nlist ? pp[i] : 0u];\n"
+                     "            q_[i] = pp[i] < nlist ? l_ : 0x80000000u;\n"
+                     "        }\n"
+                     "    }\n"
+                     "#pragma unroll\n"
+                     "    for (int i = 0; i < EPL; ++i) {\n"
+                     "        ie[i] = q_[i] & 0x7fffffffu;\n"
+                     "        st[i] = !(q_[i] >> 31) && ie[i] < ne;\n"
+                     "    }\n") +
          "#pragma unroll\n"
-         "    for (int i = 0; i < EPL; ++i) {\n"
-      << (EPL == 1 ? "        pp[i] = by * KBLOCK + tip;\n"
-                     "        ie[i] = pp[i];\n"
-                     "        st[i] = ie[i] < ne;\n"
-                   : "        pp[i] = by * (KBLOCK * EPL) + tip * EPL + i;\n"
-                     // (no list: the identity, which a sorted grid with an even
-                     // number of s-form rows is -- no dependent load then)
-                     "        const u32 q_ = pp[i] < nlist ? (plist ? plist[pp[i]] : pp[i]) : 0x80000000u;\n"
-                     "        ie[i] = q_ & 0x7fffffffu;\n"
-                     "        st[i] = !(q_ >> 31) && ie[i] < ne;\n")
-      << "        ev[i] = ie[i] < ne ? evals[ie[i]] : 0.0;\n"
-         "    }\n";
+         "    for (int i = 0; i < EPL; ++i) ev[i] = ie[i] < ne ? ev[i] : 0.0;\n"
+         // (inputs only: a pointer that came out of an asm statement would
+         // lose its address space, and its loads and stores would turn flat)
+         "    asm volatile(\"\" :: \"s\"(kmax), \"s\"(one), \"s\"(out), \"s\"(ld_out), \"s\"(out_cs), \"s\"(prior0), "
+         "\"s\"(vscr), \"s\"(ldv));\n";
     // per point: the ratio form (lane-uniform), the ratio z, the deferred
     // base B, g, and the power tables bp[k] = B^k (source pre-scales, k <= DP)
     // and gp[d] = g^d (d <= DG); then the state vector (emitted before the
@@ -489,6 +552,10 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
         w << "    }\n";
         wblock = w.str();
     }
+    // a later chunk's hand-over loads (vscr) go out ahead of the staging
+    // stores, so they share the staging loads' round trip
+    const bool w_early = !pl.fused && !pl.first;
+    const std::string early_w = w_early ? wblock : std::string();
     o << "    double xx[EPL], yy[EPL], zz[EPL], bb[EPL], bp[EPL][DP + 1], gp[EPL][DG + 1];\n"
          "    double v[EPL][NPMAX];\n    double n[EPL][(NPMAX + SPL - 1) / SPL];\n";
     if (pl.vlds)  // wide years: state k of point i of lane tid at Vl[k][i][tid]
@@ -501,58 +568,62 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
         // this column's Q row (k_qrows), in stored order and, through REVQ,
         // with every group reversed: every load in flight before the
         // (unconditional, past the end into a scratch slot) stores, as in stage()
-        o << "    {\n"
-             "        const double2 *src_ = (const double2 *)(Qrow + (size_t)ic * LDQ);\n"
-             "        double2 *dst_ = (double2 *)Ql;\n"
-             "        constexpr u32 N2 = LDQ / 2, NK = (N2 + NT - 1) / NT;\n"
-             "        double2 t_[NK];\n"
-             "        u32 r0_[NK], r1_[NK];\n"
-             "#pragma unroll\n"
-             "        for (u32 k = 0; k < NK; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             "            t_[k] = src_[i < N2 ? i : 0];\n"
-             "            r0_[k] = i < N2 ? LDQ + REVQ[2 * i] : 2 * LDQ;\n"
-             "            r1_[k] = i < N2 ? LDQ + REVQ[2 * i + 1] : 2 * LDQ;\n"
-             "        }\n"
-             "#pragma unroll\n"
-             "        for (u32 k = 0; k < NK; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             "            dst_[i < N2 ? i : LDQ] = t_[k];\n"
-             "            Ql[r0_[k]] = t_[k].x;\n"
-             "            Ql[r1_[k]] = t_[k].y;\n"
-             "        }\n"
-             "    }\n"
-          << stamp(1);
+        // (one named register per staging load, emitted unrolled, as the fused kernel's)
+        const uint32_t nk = (uint32_t)((ldq_local / 2 + nt_all - 1) / nt_all);
+        o << "    const double2 *src_ = (const double2 *)(Qrow + (size_t)ic * LDQ);\n"
+             "    constexpr u32 N2 = LDQ / 2;\n";
+        for (uint32_t k = 0; k < nk; ++k) {
+            const std::string K = std::to_string(k);
+            o << "    const u32 qi" << K << "_ = threadIdx.x + " << K << " * NT;\n"
+              << "    const double2 qt" << K << "_ = src_[qi" << K << "_ < N2 ? qi" << K << "_ : 0];\n"
+              << "    const u32 ra" << K << "_ = REVQ[qi" << K << "_ < N2 ? 2 * qi" << K << "_ : 0], rb" << K
+              << "_ = REVQ[qi" << K << "_ < N2 ? 2 * qi" << K << "_ + 1 : 0];\n";
+        }
+        o << front << early_w << "    {\n        double2 *dst_ = (double2 *)Ql;\n";
+        for (uint32_t k = 0; k < nk; ++k) {
+            const std::string K = std::to_string(k);
+            o << "        dst_[qi" << K << "_ < N2 ? qi" << K << "_ : LDQ] = qt" << K << "_;\n"
+              << "        Ql[qi" << K << "_ < N2 ? LDQ + ra" << K << "_ : 2 * LDQ] = qt" << K << "_.x;\n"
+              << "        Ql[qi" << K << "_ < N2 ? LDQ + rb" << K << "_ : 2 * LDQ] = qt" << K << "_.y;\n";
+        }
+        o << "    }\n" << stamp(1);
     } else if (!pl.fused) {
         // this chunk's coefficients gathered from the column's Q row: every
         // load in flight before the (unconditional) stores, as in stage()
-        o << "    {\n"
-             "        const double *src_ = Qrow + (size_t)ic * LDQG;\n"
-             "        constexpr u32 NK = (NQG + NT - 1) / NT;\n"
-             "        u32 x_[NK];\n"
-             "        double t_[NK];\n"
-             "#pragma unroll\n"
-             "        for (u32 k = 0; k < NK; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             "            x_[k] = qidx[i < NQG ? i : 0];\n"
-             "        }\n"
-             "#pragma unroll\n"
-             "        for (u32 k = 0; k < NK; ++k) t_[k] = src_[x_[k]];\n"
-             "#pragma unroll\n"
-             "        for (u32 k = 0; k < NK; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             "            Ql[i < NQG ? i : 2 * LDQ] = t_[k];\n"
-             "            Ql[i < NQG ? LDQ + REVQ[i] : 2 * LDQ] = t_[k];\n"
-             "        }\n"
-             "    }\n"
-          << stamp(1);
+        // (the list's loads first; the coefficient loads depend on them)
+        const uint32_t nk = (uint32_t)((pl.qidx.size() + nt_all - 1) / nt_all);
+        o << "    const double *src_ = Qrow + (size_t)ic * LDQG;\n";
+        for (uint32_t k = 0; k < nk; ++k) {
+            const std::string K = std::to_string(k);
+            o << "    const u32 qi" << K << "_ = threadIdx.x + " << K << " * NT;\n"
+              << "    const u32 qx" << K << "_ = qidx[qi" << K << "_ < NQG ? qi" << K << "_ : 0];\n"
+              << "    const u32 qr" << K << "_ = REVQ[qi" << K << "_ < NQG ? qi" << K << "_ : 0];\n";
+        }
+        o << front;
+        for (uint32_t k = 0; k < nk; ++k) o << "    const double qt" << k << "_ = src_[qx" << k << "_];\n";
+        o << early_w;
+        for (uint32_t k = 0; k < nk; ++k) {
+            const std::string K = std::to_string(k);
+            o << "    Ql[qi" << K << "_ < NQG ? qi" << K << "_ : 2 * LDQ] = qt" << K << "_;\n"
+              << "    Ql[qi" << K << "_ < NQG ? LDQ + qr" << K << "_ : 2 * LDQ] = qt" << K << "_;\n";
+        }
+        o << stamp(1);
     } else {
         // the k_qrows phases for this one c value (spom_engine.hip k_qrows):
         // Z per hidden-state row, Pc per item, Q per entry -- all in LDS.
         // The column tables (host-built, 1 KiB-padded: var-column S, items,
         // CSR, then zs as [k/2][row][k%2]) are copied to LDS through registers,
         // all in flight, one barrier.
-        o << "    extern __shared__ __attribute__((aligned(16))) double ct[];\n"
+        // (c ahead of the points: the Z and item phases want it first)
+        // (its value is selected after `front`, so that the scalar loads of c
+        // and of the late arguments wait once, together)
+        o << "    double cc[FC];\n"
+             "#pragma unroll\n"
+             "    for (int f = 0; f < FC; ++f) cc[f] = cvals[ic0 + f < nc ? ic0 + f : 0u];\n"
+          << front <<
+             "#pragma unroll\n"
+             "    for (int f = 0; f < FC; ++f) cc[f] = ic0 + f < nc ? cc[f] : 0.0;\n"
+          <<
              "    __shared__ double Zl[FC * NJ];\n"
              "#define PLS (NITEMS + 1)\n"  // a column's items, then its zero slot (the flat Q sums' padding)
              "    __shared__ double Pl[FC * PLS];\n"
@@ -565,29 +636,12 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
              "    const u32 *Rql = (const u32 *)(ct + OFF_RQ);\n"
              "    const double *zcl = ct + OFF_ZC;\n"
              "    const double *Svl = ct;\n"
-             "    const double *zl = ct + OFF_ZS;\n"
-             "    double cc[FC];\n"
-             "#pragma unroll\n"
-             "    for (int f = 0; f < FC; ++f) cc[f] = ic0 + f < nc ? cvals[ic0 + f] : 0.0;\n"
-             "    {\n"
-             "        const double2 *src = (const double2 *)coltab;\n"
-             "        double2 *dst = (double2 *)ct;\n"
-             "        const u32 n2 = ct_len / 2;\n"
-             "        double2 t[NSTG];\n"
-             "#pragma unroll\n"
-             "        for (int k = 0; k < NSTG; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             "            t[k] = src[i < n2 ? i : 0];\n"
-             "        }\n"
-             "#pragma unroll\n"
-             "        for (int k = 0; k < NSTG; ++k) {\n"
-             "            const u32 i = threadIdx.x + k * NT;\n"
-             // unconditional: lanes past the image write a scratch slot, so the
-             // loads are not sunk into per-load branches (load, wait, store x NSTG)
-             "            dst[i < n2 ? i : n2] = t[k];\n"
-             "        }\n"
-             "    }\n"
-             "    __syncthreads();\n"
+             "    const double *zl = ct + OFF_ZS;\n";
+        // unconditional stores: lanes past the image write a scratch slot, so
+        // the loads are not sunk into per-load branches (load, wait, store x NSTG)
+        for (uint32_t k = 0; k < nstg; ++k)
+            o << "    ((double2 *)ct)[si" << k << "_ < n2 ? si" << k << "_ : n2] = stg" << k << "_;\n";
+        o << "    __syncthreads();\n"
           << stamp(4);
         o <<
              // operands of the Pc and Q phases that do not depend on Z, read
@@ -725,7 +779,7 @@ std::string mdp_jit_forward_source(MdpJitPlan &pl)
              "        }\n"
              "    }\n";
     }
-    o << wblock;
+    if (!w_early) o << wblock;
     o << "    __syncthreads();\n"
       << stamp(2)
       // the prologue's extra threads (PRO > 1) are done: the forward runs on NTF
@@ -1077,9 +1131,17 @@ const RtcApi &rtc()
     return api;
 }
 
+// (kernel-argument preload: the first 14 argument SGPRs -- all that
+// mdp_fwd_jit's front reads -- arrive with the wave instead of through a
+// scalar load; the compiler's compatibility prologue loads them where the
+// firmware does not preload)
+#ifndef MDP_JIT_NO_PRELOAD
+const char *const kJitOpts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-kernarg-preload-count=14"};
+#else
 const char *const kJitOpts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
-constexpr int kJitNOpts = 3;
-constexpr int kJitCacheFormat = 3;  // bump when the cache key or file layout changes
+#endif
+constexpr int kJitNOpts = (int)(sizeof kJitOpts / sizeof kJitOpts[0]);
+constexpr int kJitCacheFormat = 4;  // bump when the cache key or file layout changes
 
 // The compiler's file identity without loading it: the resolved path, size
 // and mtime of libhiprtc and libamd_comgr next to the HIP runtime this
