@@ -352,6 +352,39 @@ int mdp_future_time_kernel(mdp_future *future, uint64_t seed, uint64_t nrep, uin
 /* The generator itself: out[4] = Philox4x32-10(key, ctr[4]) (host). */
 int mdp_future_philox(uint64_t key, const uint32_t *ctr, uint32_t *out);
 
+/* Added after ABI 9 without a version bump (MDP_ABI_VERSION stays 9): detect
+ * the three functions below by symbol lookup.
+ *
+ * mdp_future_create with options, "NAME=VALUE" pairs in the grammar of
+ * mdp_engine_create_opts; NULL or "" is mdp_future_create.  One name:
+ *   MDP_FUT_WIDE=0     (default) the lane kernels k_future<NM> only: one
+ *                      replicate per lane, n <= 64, more is MDP_EUNSUPPORTED
+ *   MDP_FUT_WIDE=auto  k_future<NM> for n <= 64, the patch-parallel
+ *                      k_future_wide<NP> (one replicate per wave, the patches
+ *                      over its lanes) for 65 <= n <= 1024
+ *   MDP_FUT_WIDE=1     k_future_wide<NP> for every 1 <= n <= 1024 (the
+ *                      kernel-variant switch of the tests)
+ * Both kernels draw from the same addressed stream and add the same terms in
+ * the same order: the counts do not depend on the kernel.  An unknown name or
+ * value is MDP_EINVAL, n > 1024 MDP_EUNSUPPORTED under every setting; <= 30
+ * missing patches, tfut <= 12288 and the 65536-replicate look-back hold for
+ * both.  Every refusal comes before the first device call.  simulate,
+ * simulate_device, check and time_kernel take either kind of engine. */
+int mdp_future_create_opts(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
+                           double d, double KD, double KS, double dS, int device, const char *opts,
+                           mdp_future **out);
+/* Name of the simulation kernel the engine launches, e.g. "k_future<16>" or
+ * "k_future_wide<2>" (owned by the engine). */
+const char *mdp_future_kernel(const mdp_future *future);
+/* The ensemble itself: words[r*W + k/64] bit k%64 = patch k occupied after
+ * tfut years in replicate rep0 + r, r < nrep, W = ceil(n/64) (overwritten;
+ * host memory).  tfut = 0 gives the completion of the last survey each
+ * replicate starts from.  Engines running k_future_wide only (the lane
+ * kernels keep no state: MDP_EUNSUPPORTED); nrep * W above 2^20 words per
+ * call is MDP_EUNSUPPORTED. */
+int mdp_future_states(mdp_future *future, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
+                      uint64_t *words);
+
 /* Device-resident form of mdp_scenario_lik (one process per GPU): upload the
  * grid once (set_grid; ts, tdis and the axes as above), then compute into
  * caller-owned device memory d_out[ne*nc*nK*nd] (same layout) on `stream`

@@ -443,18 +443,46 @@ def read_posterior(path) -> np.ndarray:
 
 class Future:
     """GPU replicate loop of MIDASPOM_future (``mdp_future``): per-year counts
-    of replicates with every patch extinct."""
+    of replicates with every patch extinct.
+
+    ``options`` (a dict or "NAME=VALUE;..." string, ``mdp_future_create_opts``):
+    ``MDP_FUT_WIDE`` = 0 (the default: one replicate per lane, at most 64
+    patches), ``auto`` (the patch-parallel kernel beyond 64 patches, up to
+    1024) or 1 (the patch-parallel kernel for every size).  ``None`` is
+    ``mdp_future_create``: the lane kernels alone."""
 
     def __init__(self, row, post, m: float = 400.0, d: float = 200.0, KD: float = 1.0, KS: float = 0.0,
-                 dS: float = 200.0, device: int = 0):
+                 dS: float = 200.0, device: int = 0, options=None):
         row = np.ascontiguousarray(row, dtype=np.int32)
         post = np.ascontiguousarray(post, dtype=np.float64)
         self._post = post
+        self.n = int(row.size)
         h = ctypes.c_void_p()
-        check(lib().mdp_future_create(row.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), row.size, _dptr(post),
-                                      post.shape[0] if post.size else 0, m, d, KD, KS, dS, device,
-                                      ctypes.byref(h)))
+        args = (row.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), row.size, _dptr(post),
+                post.shape[0] if post.size else 0, m, d, KD, KS, dS, device)
+        if options is None:
+            check(lib().mdp_future_create(*args, ctypes.byref(h)))
+        else:
+            if isinstance(options, dict):
+                options = ";".join(f"{k}={v}" for k, v in options.items())
+            check(lib().mdp_future_create_opts(*args, str(options).encode(), ctypes.byref(h)))
         self._h = h
+
+    @property
+    def kernel(self) -> str:
+        """Name of the simulation kernel, e.g. ``k_future<16>`` or ``k_future_wide<2>``."""
+        return lib().mdp_future_kernel(self._h).decode()
+
+    def states(self, nrep: int, tfut: int, seed: int = 0, rep0: int = 0) -> np.ndarray:
+        """bool[nrep, n]: patch k of replicate rep0 + r occupied after ``tfut``
+        years (0: the completion of the last survey it starts from).  Engines
+        running ``k_future_wide`` only."""
+        W = (self.n + 63) // 64
+        words = np.zeros((nrep, W), dtype=np.uint64)
+        check(lib().mdp_future_states(self._h, seed, rep0, nrep, tfut,
+                                      words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        bits = np.unpackbits(words.view(np.uint8).reshape(nrep, W * 8), axis=1, bitorder="little")
+        return bits[:, :self.n].astype(bool)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -166,6 +166,15 @@ SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, c_dbl_p]),
     ("mdp_future_philox", ctypes.c_int,
      [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    # added after ABI 9 without a version bump
+    ("mdp_future_create_opts", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, c_dbl_p, ctypes.c_uint32, ctypes.c_double, ctypes.c_double,
+      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_char_p,
+      ctypes.POINTER(ctypes.c_void_p)]),
+    ("mdp_future_kernel", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("mdp_future_states", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+      ctypes.POINTER(ctypes.c_uint64)]),
 ]
 
 _lib = None
@@ -209,6 +218,7 @@ ENGINE_OPTION_NAMES = (
     # measurement-only: accepted by the diag build alone
     "MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")
 SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW", "MDP_SCN_LAUNCH_PTS")
+FUTURE_OPTION_NAMES = ("MDP_FUT_WIDE",)
 
 
 DIAG_OPTION_NAMES = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")

@@ -4,7 +4,8 @@
  * same getopt string ("n:a:m:p:q:d:i:o:S:s:D:", :140) and code defaults
  * (:123-133; the code's -D 1, not the manual's 0), same stdout lines and
  * output layout ("%d\t" per future year, no newline, :402-404).  The
- * replicate loop runs on the GPU through mdp_future_simulate.
+ * replicate loop runs on the GPU through mdp_future_simulate, for occupancy
+ * files of up to 1024 patches (MDP_FUT_WIDE=auto).
  *
  * Extensions (the reference has no other way to set them):
  *   -g <N>     GPUs (or MIDASPOM_GPUS=N): the replicates in N contiguous
@@ -46,7 +47,9 @@ static void *run_range(void *arg)
 {
     struct range *r = arg;
     mdp_future *f = NULL;
-    r->rc = mdp_future_create(r->pend, r->n, r->post, r->necstep, r->mdisp, r->d, r->KD, r->KS, r->dS, r->dev, &f);
+    /* the lane kernels up to 64 patches, the patch-parallel kernel up to 1024 */
+    r->rc = mdp_future_create_opts(r->pend, r->n, r->post, r->necstep, r->mdisp, r->d, r->KD, r->KS, r->dS, r->dev,
+                                   "MDP_FUT_WIDE=auto", &f);
     if (r->rc == MDP_OK && r->nrep) r->rc = mdp_future_simulate(f, r->seed, r->rep0, r->nrep, r->tfut, r->cnt);
     if (r->rc != MDP_OK) snprintf(r->err, sizeof r->err, "%s", mdp_last_error());
     mdp_future_destroy(f);

@@ -21,6 +21,8 @@
 // the per-year all-extinct counts aggregated by wave ballots into LDS, then
 // per workgroup into a partial table reduced by k_future_sum (integer sums,
 // deterministic).
+// Surveys of more than 64 patches (mdp_future_create_opts, MDP_FUT_WIDE) run
+// the patch-parallel k_future_wide<NP> further down: one wave per replicate.
 //
 // Random numbers: the reference draws rand()/RAND_MAX from one sequential
 // stream per process (srand(time(NULL)), :345).  Here every draw is
@@ -45,6 +47,7 @@
 #include <vector>
 
 #include "mdp_internal.h"
+#include "spom_future_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -271,6 +274,172 @@ __global__ __launch_bounds__(256) void k_future_sum(const uint32_t *__restrict__
     if (threadIdx.x == 0) counts[t] = red[0];
 }
 
+// ---------------------------------------------------------------------------
+// Patch-parallel form for 65..1024 patches (and, by option, any n): one wave
+// per replicate, the patches spread over its lanes.  Lane lambda owns the
+// patch pairs m = lambda + 64*j, j < NP (patches 2m, 2m+1: one Philox call
+// per pair and year gives the four draws), and holds their occupancy in bits
+// 2j, 2j+1 of one word.  The survivors of a year are wave ballots, one
+// 64-bit mask per (j, parity), walked in ascending patch order; every step
+// adds one row of the dispersal table to the lane's 2*NP running sums.  The
+// table is Toeplitz, so a row is a window of the two-sided distance image
+// (spom_future_plan.h) in LDS: consecutive lanes read consecutive 16-byte
+// slots, from the copy whose alignment fits the parity of the survivor.
+// Same stream, same sums in the same order as k_future<NM>: the same counts.
+// ---------------------------------------------------------------------------
+struct FutWideArgs {
+    uint32_t n, nmiss, tfut, lvalid;
+    uint64_t rep0, nrep;
+    uint32_t key0, key1;
+    uint32_t necstep, len;  // len: doubles per copy of the distance image
+    uint32_t ks0, pad;      // ks0: K_S == 0, an extinct replicate stays extinct
+    double pscale;
+    double K;
+};
+
+constexpr int kWideWaves = kFutBlock / 64;  // replicates in flight per workgroup
+
+template <int NP>
+__global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const double *__restrict__ image,
+                                                           const double *__restrict__ src,
+                                                           const double *__restrict__ pcum,
+                                                           const uint32_t *__restrict__ occ0,
+                                                           const uint32_t *__restrict__ miss,
+                                                           uint32_t *__restrict__ partial,
+                                                           uint32_t *__restrict__ states, uint32_t *__restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    // both copies of the distance image first (2*len doubles), then the year counters
+    double2 *G2 = reinterpret_cast<double2 *>(dyn);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(dyn + 2 * a.len);
+    for (uint32_t i = threadIdx.x; i < a.len; i += kFutBlock) G2[i] = reinterpret_cast<const double2 *>(image)[i];
+    for (uint32_t t = threadIdx.x; t < a.tfut; t += kFutBlock) cnt[t] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t npairs = (a.n + 1) >> 1;
+    const uint32_t occ_init = occ0[lane];
+    // bit 2j+p set where patch 2*(lane + 64*j) + p exists
+    uint32_t live = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t k0 = 2 * (lane + 64u * j);
+        if (k0 < a.n) live |= 1u << (2 * j);
+        if (k0 + 1 < a.n) live |= 2u << (2 * j);
+    }
+    for (uint64_t r = (uint64_t)blockIdx.x * kWideWaves + wave; r < a.nrep; r += (uint64_t)gridDim.x * kWideWaves) {
+        const uint64_t rg = a.rep0 + r;  // wave-uniform from here to the state
+        // ---- (e, c) from the posterior, with the reference's carry-over (:361-377)
+        uint32_t idx = a.lvalid, init_w = 0;
+        {
+            uint64_t q = rg;
+            for (uint32_t step = 0;; ++step) {
+                const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)q, (uint32_t)(q >> 32), 0xffffffffu, 0u});
+                if (step == 0) init_w = w.y >> 1;
+                if (a.lvalid == 0) break;  // empty / all-NaN posterior: never found
+                const double pec = a.pscale * (double)(w.x >> 1) / kRandMax;
+                idx = upper_bound(pcum, a.lvalid, pec);
+                if (idx < a.lvalid || q == 0) break;
+                if (step + 1 >= kLookBack) {  // posterior mass too small for an exact look-back
+                    if (lane == 0) atomicOr(err, 1u);
+                    break;
+                }
+                --q;
+            }
+        }
+        uint32_t ie = 0, ic = 0;
+        if (idx < a.lvalid) ie = idx / a.necstep, ic = idx - ie * a.necstep;
+        const double e = (double)ie * 0.01, c = (double)ic * 0.01;
+        double E = e / a.K;  // simpij :67, :74
+        if (E > 1) E = 1;
+        // ---- initial state: missing patches filled from init (first missing = MSB) (:315-321, :378)
+        const uint32_t init = init_w & ((1u << a.nmiss) - 1u);
+        uint32_t occ = occ_init;
+        for (uint32_t q = 0; q < a.nmiss; ++q) {
+            const uint32_t mq = miss[q];
+            if (((init >> (a.nmiss - 1 - q)) & 1u) && lane == (mq >> 8)) occ |= 1u << (mq & 0xffu);
+        }
+        // ---- tfut years (:381-385)
+        for (uint32_t t = 0; t < a.tfut; ++t) {
+            uint64_t bal[NP][2];
+            uint32_t colw[2 * NP];
+            uint32_t surv = 0;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                const uint32_t m = lane + 64u * j;
+                bool s0 = false, s1 = false;
+                colw[2 * j] = colw[2 * j + 1] = 0;
+                if (m < npairs) {
+                    const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
+                    colw[2 * j] = w.y >> 1;
+                    colw[2 * j + 1] = w.w >> 1;
+                    // extinction: an occupied patch survives if u > E (:75-82)
+                    s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
+                    s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
+                }
+                bal[j][0] = __ballot(s0);
+                bal[j][1] = __ballot(s1);
+                surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
+            }
+            // colonisation sums, ascending l for every k (:89-95): patch
+            // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
+            double s[2 * NP];
+#pragma unroll
+            for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                uint64_t both = bal[j][0] | bal[j][1];
+                while (both) {
+                    const uint32_t lam = (uint32_t)__builtin_ctzll(both);
+                    both &= both - 1;
+#pragma unroll
+                    for (uint32_t p = 0; p < 2; ++p) {
+                        if (!((bal[j][p] >> lam) & 1u)) continue;
+                        const uint32_t l = 2 * (lam + 64u * j) + p;
+                        const uint32_t base = a.n - 1 - l;
+                        const uint32_t slot0 = (base & 1u) ? (a.len + base - 1) >> 1 : base >> 1;
+                        const double2 *row = G2 + slot0 + lane;
+#pragma unroll
+                        for (int jj = 0; jj < NP; ++jj) {
+                            const double2 v = row[64 * jj];
+                            s[2 * jj] += v.x;
+                            s[2 * jj + 1] += v.y;
+                        }
+                    }
+                }
+            }
+            uint32_t nw = surv;
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const uint32_t bit = 1u << (2 * j + p);
+                    if ((live & bit) && !(surv & bit)) {
+                        double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
+                        if (pc > 1) pc = 1;
+                        if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
+                    }
+                }
+            }
+            occ = nw;
+            if (__ballot(occ != 0) == 0) {
+                if (!a.ks0) {
+                    if (lane == 0) atomicAdd(&cnt[t], 1u);
+                } else {
+                    // no source: every sum is 0, pC = c*0, and no draw is
+                    // below 0 -- the replicate is extinct in every later year
+                    for (uint32_t tt = t + lane; tt < a.tfut; tt += 64) atomicAdd(&cnt[tt], 1u);
+                    break;
+                }
+            }
+        }
+        if (states) states[r * 64 + lane] = occ;
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < a.tfut; t += kFutBlock) partial[(size_t)blockIdx.x * a.tfut + t] = cnt[t];
+}
+
 template <typename T>
 int dev_up(T **p, const std::vector<T> &h)
 {
@@ -294,13 +463,21 @@ struct mdp_future {
     size_t counts_cap = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // k_future_wide<np> (np > 0): its tables instead of dMK / dmiss / dT
+    uint32_t np = 0, wlen = 0, ks0 = 0;
+    double *dimage = nullptr;
+    uint32_t *docc0 = nullptr, *dwmiss = nullptr, *dstates = nullptr;
+    size_t states_cap = 0;
+    char kname[32] = "";
 };
 
 namespace {
 
-int fut_grid(uint64_t nrep)
+// replicates per workgroup: one per lane, or one per wave (k_future_wide)
+int fut_grid(const mdp_future *f, uint64_t nrep)
 {
-    const uint64_t wg = (nrep + kFutBlock - 1) / kFutBlock;
+    const uint64_t per = f->np ? kWideWaves : kFutBlock;
+    const uint64_t wg = (nrep + per - 1) / per;
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(wg, kFutMaxWG));
 }
 
@@ -324,10 +501,64 @@ int fut_reserve(mdp_future *f, int nwg, uint32_t tfut)
     return MDP_OK;
 }
 
-// one simulation (k_future + k_future_sum) into d_counts on stream st
+size_t fut_wide_lds(const mdp_future *f, uint32_t tfut)
+{
+    return (size_t)2 * f->wlen * sizeof(double) + (size_t)tfut * sizeof(uint32_t);
+}
+
+// k_future_wide<np> over replicates [rep0, rep0 + nrep); d_states: the final
+// lane words of every replicate ([nrep][64]) or null
+int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut, hipStream_t st,
+                    uint32_t *d_states, uint32_t *derr)
+{
+    FutWideArgs a{};
+    a.n = f->n;
+    a.nmiss = f->nmiss;
+    a.tfut = tfut;
+    a.lvalid = f->lvalid;
+    a.rep0 = rep0;
+    a.nrep = nrep;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.necstep = f->necstep;
+    a.len = f->wlen;
+    a.ks0 = f->ks0;
+    a.pscale = f->pscale;
+    a.K = f->K;
+    const int nwg = fut_grid(f, nrep);
+    const size_t lds = fut_wide_lds(f, tfut);
+    switch (f->np) {
+#define FUT_WCASE(NPV)                                                                                  \
+    case NPV:                                                                                            \
+        hipLaunchKernelGGL(k_future_wide<NPV>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage,      \
+                           f->dsrc, f->dpcum, f->docc0, f->dwmiss, f->dpartial, d_states, derr);        \
+        break;
+        FUT_WCASE(1)
+        FUT_WCASE(2)
+        FUT_WCASE(4)
+        FUT_WCASE(8)
+#undef FUT_WCASE
+    default:
+        return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", f->np);
+    }
+    FUT_TRY(hipGetLastError());
+    return MDP_OK;
+}
+
+// one simulation (k_future or k_future_wide, + k_future_sum) into d_counts on stream st
 int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
                unsigned long long *d_counts, hipStream_t st, bool sum, uint32_t *derr)
 {
+    if (f->np) {
+        int rc = fut_launch_wide(f, seed, rep0, nrep, tfut, st, nullptr, derr);
+        if (rc) return rc;
+        if (sum) {
+            hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial, (uint32_t)fut_grid(f, nrep),
+                               tfut, d_counts);
+            FUT_TRY(hipGetLastError());
+        }
+        return MDP_OK;
+    }
     FutArgs a{};
     a.n = f->n;
     a.nmiss = f->nmiss;
@@ -341,7 +572,7 @@ int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint3
     a.necstep = f->necstep;
     a.pscale = f->pscale;
     a.K = f->K;
-    const int nwg = fut_grid(nrep);
+    const int nwg = fut_grid(f, nrep);
     const size_t lds = (size_t)tfut * sizeof(uint32_t) + (f->nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0);
     switch (f->nm) {
 #define FUT_CASE(NMV)                                                                                   \
@@ -378,11 +609,14 @@ int fut_check_args(mdp_future *f, uint64_t nrep, uint32_t tfut)
 
 extern "C" {
 
-int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
-                      double d, double KD, double KS, double dS, int device, mdp_future **out)
+// mdp_future_create (mode kFutWideOff) and mdp_future_create_opts; every
+// refusal of an argument comes before the first HIP call
+static int fut_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m, double d,
+                      double KD, double KS, double dS, int device, FutWideMode mode, mdp_future **out)
 {
     if (!last_row || !out || n == 0) return mdp_set_error(MDP_EINVAL, "empty survey row");
-    if (n > 64) return mdp_set_error(MDP_EUNSUPPORTED, "%u patches: the future engine holds <= 64", n);
+    uint32_t np = 0;
+    if (int rc = fut_select_kernel(n, mode, &np)) return rc;
     if (necstep > 0 && !post) return mdp_set_error(MDP_EINVAL, "null posterior");
     if (!(KD >= 0) || !std::isfinite(KD) || !(KS >= 0) || !std::isfinite(KS))
         return mdp_set_error(MDP_EINVAL, "-D and -S must be finite and >= 0");
@@ -392,11 +626,25 @@ int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, u
     f->device = device;
     f->n = n;
     f->nm = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+    f->np = np;
     f->K = KD;
     f->necstep = necstep;
+    if (np) snprintf(f->kname, sizeof f->kname, "k_future_wide<%u>", np);
+    else snprintf(f->kname, sizeof f->kname, "k_future<%u>", f->nm);
     // last survey row -> occupied bits and missing columns (:292-323)
     std::vector<uint64_t> miss;
-    for (uint32_t j = 0; j < n; ++j) {
+    FutWidePlan wp;
+    if (np) {
+        // the same in the lane-owned layout, with the two-sided distance image
+        if (int rc = fut_wide_plan(last_row, n, np, m, d, KD, KS, dS, &wp)) {
+            delete f;
+            return rc;
+        }
+        f->nmiss = wp.nmiss;
+        f->wlen = wp.len;
+        f->ks0 = KS == 0;
+    }
+    for (uint32_t j = 0; j < n && !np; ++j) {
         if (last_row[j] == 1) f->occ0 |= 1ull << j;
         else if (last_row[j] == -1) miss.push_back(1ull << j);
         else if (last_row[j] != 0) {
@@ -409,17 +657,17 @@ int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, u
         return mdp_set_error(MDP_EUNSUPPORTED, "%zu missing patches (npstates = 2^%zu overflows int)", miss.size(),
                              miss.size());
     }
-    f->nmiss = (uint32_t)miss.size();
+    if (!np) f->nmiss = (uint32_t)miss.size();
     // dispersal (:266-277), a = 1/m; M*K_D and the source term M[n][k]*K_S
     const double a = 1.0 / m;
-    std::vector<double> MK((size_t)f->nm * f->nm, 0.0), src(f->nm, 0.0);
-    for (uint32_t i = 0; i < n; ++i)
+    std::vector<double> MK(np ? 0 : (size_t)f->nm * f->nm, 0.0), src(f->nm, 0.0);
+    for (uint32_t i = 0; i < n && !np; ++i)
         for (uint32_t j = i + 1; j < n; ++j) {
             const double v = exp(-a * (j - i) * d);
             MK[(size_t)i * f->nm + j] = v * KD;
             MK[(size_t)j * f->nm + i] = v * KD;
         }
-    for (uint32_t j = 0; j < n; ++j) src[j] = exp(-a * (j + 1) * dS) * KS;
+    for (uint32_t j = 0; j < n && !np; ++j) src[j] = exp(-a * (j + 1) * dS) * KS;
     // trapezoid-weighted cumulative posterior in the reference's scan order
     // (:362-369); the scan stops matching at the first NaN
     std::vector<double> pcum((size_t)necstep * necstep);
@@ -449,12 +697,27 @@ int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, u
         delete f;
         return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
     }
-    if ((rc = dev_up(&f->dMK, MK)) || (rc = dev_up(&f->dsrc, src)) || (rc = dev_up(&f->dpcum, pcum)) ||
-        (rc = dev_up(&f->dmiss, miss))) {
+    if (np) {
+        if ((rc = dev_up(&f->dimage, wp.image)) || (rc = dev_up(&f->dsrc, wp.src)) || (rc = dev_up(&f->dpcum, pcum)) ||
+            (rc = dev_up(&f->docc0, wp.occ0)) || (rc = dev_up(&f->dwmiss, wp.miss))) {
+            mdp_future_destroy(f);
+            return rc;
+        }
+        // the image and kFutMaxT year counters pass 64 KB of dynamic LDS
+        const void *fn = np == 1 ? (const void *)k_future_wide<1> : np == 2 ? (const void *)k_future_wide<2>
+                       : np == 4 ? (const void *)k_future_wide<4> : (const void *)k_future_wide<8>;
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fut_wide_lds(f, kFutMaxT)) !=
+            hipSuccess) {
+            mdp_future_destroy(f);
+            return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d", f->kname,
+                                 fut_wide_lds(f, kFutMaxT), device);
+        }
+    } else if ((rc = dev_up(&f->dMK, MK)) || (rc = dev_up(&f->dsrc, src)) || (rc = dev_up(&f->dpcum, pcum)) ||
+               (rc = dev_up(&f->dmiss, miss))) {
         mdp_future_destroy(f);
         return rc;
     }
-    if (f->nm == kTabN) {
+    if (!np && f->nm == kTabN) {
         if (hipMalloc((void **)&f->dT, sizeof(double) * (kTabN << kTabN)) != hipSuccess) {
             mdp_future_destroy(f);
             return mdp_set_error(MDP_EHIP, "device allocation failed on device %d", device);
@@ -479,6 +742,63 @@ int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, u
     return MDP_OK;
 }
 
+int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
+                      double d, double KD, double KS, double dS, int device, mdp_future **out)
+{
+    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, kFutWideOff, out);
+}
+
+int mdp_future_create_opts(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
+                           double d, double KD, double KS, double dS, int device, const char *opts,
+                           mdp_future **out)
+{
+    FutWideMode mode;
+    if (int rc = fut_parse_opts(opts, &mode)) return rc;
+    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, mode, out);
+}
+
+const char *mdp_future_kernel(const mdp_future *f) { return f ? f->kname : ""; }
+
+int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut, uint64_t *words)
+{
+    if (!f) return mdp_set_error(MDP_EINVAL, "null future engine");
+    if (!f->np)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%s keeps no replicate states: create the engine with "
+                             "MDP_FUT_WIDE=1 (or auto beyond 64 patches)", f->kname);
+    if (tfut > kFutMaxT) return mdp_set_error(MDP_EUNSUPPORTED, "duration %u outside 0..%u years", tfut, kFutMaxT);
+    const uint32_t W = (f->n + 63) / 64;
+    if (nrep > kFutStatesMaxWords / W)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%llu replicates x %u words: mdp_future_states returns at most %llu "
+                             "words per call", (unsigned long long)nrep, W, (unsigned long long)kFutStatesMaxWords);
+    if (nrep == 0) return MDP_OK;
+    if (!words) return mdp_set_error(MDP_EINVAL, "null states");
+    FUT_TRY(hipSetDevice(f->device));
+    int rc;
+    if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
+    if (nrep > f->states_cap) {
+        if (f->dstates) (void)hipFree(f->dstates);
+        f->dstates = nullptr;
+        f->states_cap = 0;
+        FUT_TRY(hipMalloc((void **)&f->dstates, (size_t)nrep * 64 * sizeof(uint32_t)));
+        f->states_cap = nrep;
+    }
+    FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = fut_launch_wide(f, seed, rep0, nrep, tfut, f->stream, f->dstates, f->derr + 1))) return rc;
+    std::vector<uint32_t> lanes((size_t)nrep * 64);
+    uint32_t err = 0;
+    FUT_TRY(hipMemcpyAsync(lanes.data(), f->dstates, lanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           f->stream));
+    FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    FUT_TRY(hipStreamSynchronize(f->stream));
+    if (err)
+        return mdp_set_error(MDP_EUNSUPPORTED,
+                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
+                             "below the (necstep-1)^2 scale)",
+                             kLookBack);
+    fut_wide_unpack(lanes.data(), nrep, f->n, f->np, words);
+    return MDP_OK;
+}
+
 void mdp_future_destroy(mdp_future *f)
 {
     if (!f) return;
@@ -492,6 +812,10 @@ void mdp_future_destroy(mdp_future *f)
     (void)hipFree(f->dpartial);
     (void)hipFree(f->derr);
     (void)hipFree(f->dcounts);
+    (void)hipFree(f->dimage);
+    (void)hipFree(f->docc0);
+    (void)hipFree(f->dwmiss);
+    (void)hipFree(f->dstates);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -506,7 +830,7 @@ int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint
     if (!d_counts) return mdp_set_error(MDP_EINVAL, "null device counts");
     FUT_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
-    if ((rc = fut_reserve(f, fut_grid(nrep), tfut))) return rc;
+    if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     // the look-back overflow flag is sticky: mdp_future_check reads and
     // clears it, so one check covers every launch since the previous check
     return fut_launch(f, seed, rep0, nrep, tfut, (unsigned long long *)d_counts, st, true, f->derr);
@@ -536,7 +860,7 @@ int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nr
     if (rc) return rc;
     if (!counts) return mdp_set_error(MDP_EINVAL, "null counts");
     FUT_TRY(hipSetDevice(f->device));
-    if ((rc = fut_reserve(f, fut_grid(nrep), tfut))) return rc;
+    if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if (nrep == 0) return MDP_OK;
     FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_launch(f, seed, rep0, nrep, tfut, f->dcounts, f->stream, true, f->derr + 1))) return rc;
@@ -560,7 +884,7 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     FUT_TRY(hipSetDevice(f->device));
-    if ((rc = fut_reserve(f, fut_grid(nrep), tfut))) return rc;
+    if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if ((rc = fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1))) return rc;
     FUT_TRY(hipEventRecord(f->ev0, f->stream));
     for (int i = 0; i < reps; ++i)

@@ -1,0 +1,105 @@
+// midaspom_amd/csrc/spom_future_plan.cpp -- host planning of k_future_wide
+// (spom_future_plan.h): option parsing, kernel selection, the two-sided
+// distance image, the lane-owned layout and its inverse.  Host only.
+#include "spom_future_plan.h"
+
+#include <cmath>
+#include <string>
+
+int fut_parse_opts(const char *s, FutWideMode *mode)
+{
+    *mode = kFutWideOff;
+    if (!s) return MDP_OK;
+    std::string cur;
+    auto flush = [&]() -> int {
+        if (cur.empty()) return MDP_OK;
+        const size_t eq = cur.find('=');
+        const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string("1") : cur.substr(eq + 1);
+        cur.clear();
+        if (k != "MDP_FUT_WIDE") return mdp_set_error(MDP_EINVAL, "unknown future option '%s'", k.c_str());
+        if (v == "0") *mode = kFutWideOff;
+        else if (v == "auto") *mode = kFutWideAuto;
+        else if (v == "1") *mode = kFutWideOn;
+        else return mdp_set_error(MDP_EINVAL, "MDP_FUT_WIDE=%s (expected 0, auto or 1)", v.c_str());
+        return MDP_OK;
+    };
+    for (const char *c = s;; ++c) {
+        if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
+            const int rc = flush();
+            if (rc) return rc;
+            if (*c == 0) break;
+        } else {
+            cur += *c;
+        }
+    }
+    return MDP_OK;
+}
+
+int fut_select_kernel(uint32_t n, FutWideMode mode, uint32_t *np)
+{
+    *np = 0;
+    if (n > kFutWideMaxN)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%u patches: the future engine holds <= %u", n, kFutWideMaxN);
+    if (mode == kFutWideOff || (mode == kFutWideAuto && n <= kFutLaneMaxN)) {
+        if (n > kFutLaneMaxN)
+            return mdp_set_error(MDP_EUNSUPPORTED, "%u patches: the future engine holds <= 64", n);
+        return MDP_OK;
+    }
+    *np = n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8;
+    return MDP_OK;
+}
+
+int fut_wide_plan(const int32_t *last_row, uint32_t n, uint32_t np, double m, double d, double KD, double KS,
+                  double dS, FutWidePlan *plan)
+{
+    if (!last_row || !plan || n == 0 || np == 0 || n > 128 * np)
+        return mdp_set_error(MDP_EINVAL, "internal: wide plan of %u patches with %u pairs per lane", n, np);
+    FutWidePlan &p = *plan;
+    p = FutWidePlan();
+    p.n = n;
+    p.np = np;
+    p.occ0.assign(64, 0u);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t pair = k >> 1, lane = pair & 63u, bit = 2 * (pair >> 6) + (k & 1u);
+        if (last_row[k] == 1) p.occ0[lane] |= 1u << bit;
+        else if (last_row[k] == -1) p.miss.push_back((lane << 8) | bit);
+        else if (last_row[k] != 0)
+            return mdp_set_error(MDP_EINVAL, "survey value %d in column %u (expected -1, 0 or 1)", last_row[k], k);
+    }
+    if (p.miss.size() > kFutMaxMissing)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%zu missing patches (npstates = 2^%zu overflows int)", p.miss.size(),
+                             p.miss.size());
+    p.nmiss = (uint32_t)p.miss.size();
+    // dispersal (future.c:266-277), a = 1/m: the same expressions, so the
+    // same bits, as the n x n table of the lane kernels
+    const double a = 1.0 / m;
+    p.len = (n + 128 * np + 1) & ~1u;
+    std::vector<double> G((size_t)p.len + 1, 0.0);
+    for (uint32_t dist = 1; dist < n; ++dist) {
+        const double v = exp(-a * dist * d) * KD;
+        G[n - 1 - dist] = v;
+        G[n - 1 + dist] = v;
+    }
+    p.image.assign((size_t)2 * p.len, 0.0);
+    for (uint32_t i = 0; i < p.len; ++i) {
+        p.image[i] = G[i];
+        p.image[(size_t)p.len + i] = G[i + 1];
+    }
+    p.src.assign((size_t)128 * np, 0.0);
+    for (uint32_t j = 0; j < n; ++j) p.src[j] = exp(-a * (j + 1) * dS) * KS;
+    return MDP_OK;
+}
+
+void fut_wide_unpack(const uint32_t *lanes, uint64_t nrep, uint32_t n, uint32_t np, uint64_t *words)
+{
+    const uint32_t W = (n + 63) / 64;
+    (void)np;
+    for (uint64_t r = 0; r < nrep; ++r) {
+        uint64_t *w = words + r * W;
+        for (uint32_t i = 0; i < W; ++i) w[i] = 0;
+        for (uint32_t k = 0; k < n; ++k) {
+            const uint32_t pair = k >> 1, lane = pair & 63u, bit = 2 * (pair >> 6) + (k & 1u);
+            if ((lanes[r * 64 + lane] >> bit) & 1u) w[k >> 6] |= 1ull << (k & 63u);
+        }
+    }
+}

@@ -15,6 +15,9 @@ one sum-reduce of the per-year counts to rank 0 (:429-446), and that
 program's per-rank stdout lines (`npstates =` :320, start / end :372, :427,
 send / gather :430-445).  Rank 0 writes the file.
 
+Engines are created with MDP_FUT_WIDE=auto: occupancy files of up to 1024
+patches run (beyond 64 on the patch-parallel kernel).
+
 Replicate r draws from the Philox stream addressed by (seed, r) wherever it
 runs, so the file does not depend on N or on the split (rank 0's seed is
 broadcast).  The reference's rand() stream is matched statistically only
@@ -29,6 +32,8 @@ import time
 
 import numpy as np
 
+# the lane kernels up to 64 patches, the patch-parallel kernel up to 1024
+WIDE_AUTO = "MDP_FUT_WIDE=auto"
 BANNER = "------MIDASPOM, beta MPI version -------\n-> N. Alcala, E. M. Cole, N. A. Rosenberg  <-\n"
 
 
@@ -92,7 +97,8 @@ def _simulate_threads(mdp, mdist, row, post, a, seed, ngpu):
     def run(r):
         r0, r1 = mdist.replicate_range(r, ngpu, a.n)
         try:
-            with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=r % ndev) as f:
+            with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=r % ndev,
+                            options=WIDE_AUTO) as f:
                 parts[r] = f.simulate(r1 - r0, a.a, seed=seed, rep0=r0) if r1 > r0 else np.zeros(a.a, np.uint64)
         except Exception as exc:  # re-raised on the main thread
             errs.append(exc)
@@ -194,7 +200,8 @@ def main(argv=None) -> int:
         r0, r1 = mdist.replicate_range(rank, world, a.n)
         local_counts = np.zeros(max(a.a, 0), np.uint64)
         if a.a > 0 and r1 > r0:
-            with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=dev) as f:
+            with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=dev,
+                            options=WIDE_AUTO) as f:
                 local_counts = f.simulate(r1 - r0, a.a, seed=seed, rep0=r0)
         out(f"end likelihood computation process {rank + 1}/{world}\n", all_ranks=True)
         if not root:
