@@ -16,7 +16,9 @@
  *    or exits across the ABI;
  *  - an engine is not re-entrant; one host thread drives all its devices;
  *  - results are deterministic (no floating-point atomics in any reduction;
- *    the future engine's integer counts use LDS atomics, exact in any order).
+ *    the future engine's integer counts -- the per-year extinct counts and
+ *    the summary tables hist / occ of mdp_future_summary -- use LDS and
+ *    global integer atomics, exact in any order).
  */
 #ifndef MIDASPOM_H
 #define MIDASPOM_H
@@ -384,6 +386,35 @@ const char *mdp_future_kernel(const mdp_future *future);
  * call is MDP_EUNSUPPORTED. */
 int mdp_future_states(mdp_future *future, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
                       uint64_t *words);
+
+/* Also added after ABI 9 without a version bump: the ensemble's summaries.
+ * For replicates r in [rep0, rep0 + nrep) and years t < tfut, on the same
+ * addressed stream (and so the same trajectories) as mdp_future_simulate:
+ *   hist[t*(n+1) + m] += replicates with exactly m occupied patches after
+ *                        year t+1, m = 0..n   (hist[t][0] is counts[t])
+ *   occ[t*n + k]      += replicates with patch k occupied after year t+1
+ * Host memory; either table may be NULL, not both.  Both kinds of engine.
+ * The tables are counted in LDS over windows of years (one launch per window,
+ * the replicates resting in device records in between) with integer atomics:
+ * exact, the same bits for every split and window length.  tfut outside
+ * 1..12288 or tfut*(2n+1) > 2^21 cells is MDP_EUNSUPPORTED, both tables NULL
+ * MDP_EINVAL, before any device call.  The look-back overflow is reported as
+ * by mdp_future_simulate.
+ * One more option of mdp_future_create_opts:
+ *   MDP_FUT_SUM_YEARS=N  at most N years per window (0 or unset: the engine's
+ *                        choice, what fits 16 KB of LDS); any other value than
+ *                        0..12288 is MDP_EINVAL.  The window-boundary switch
+ *                        of the tests; the tables do not depend on it. */
+int mdp_future_summary(mdp_future *future, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
+                       uint64_t *hist, uint64_t *occ);
+/* Same into caller-owned device memory (overwritten, not accumulated) on
+ * `stream`, asynchronously; the look-back flag is the sticky one of
+ * mdp_future_simulate_device, read by mdp_future_check. */
+int mdp_future_summary_device(mdp_future *future, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
+                              uint64_t *d_hist, uint64_t *d_occ, void *stream);
+/* Mean duration (ms) of the summary path (every window's launch and the
+ * table's reset) over `reps` runs of replicates [0, nrep) between two events. */
+int mdp_future_time_summary(mdp_future *future, uint64_t seed, uint64_t nrep, uint32_t tfut, int reps, double *ms);
 
 /* Device-resident form of mdp_scenario_lik (one process per GPU): upload the
  * grid once (set_grid; ts, tdis and the axes as above), then compute into

@@ -27,7 +27,7 @@ from ._lib import MidaspomError, check, lib
 __all__ = [
     "Model", "Engine", "grid", "log_total", "write_posterior", "posterior",
     "run_file", "MidaspomError", "Scenario", "kgrid", "dgrid", "first_row",
-    "Future", "read_survey", "read_posterior", "device_count",
+    "Future", "read_survey", "read_posterior", "device_count", "quasi_extinction", "mean_occupied",
 ]
 
 
@@ -449,7 +449,9 @@ class Future:
     ``MDP_FUT_WIDE`` = 0 (the default: one replicate per lane, at most 64
     patches), ``auto`` (the patch-parallel kernel beyond 64 patches, up to
     1024) or 1 (the patch-parallel kernel for every size).  ``None`` is
-    ``mdp_future_create``: the lane kernels alone."""
+    ``mdp_future_create``: the lane kernels alone.  ``MDP_FUT_SUM_YEARS`` = N
+    caps the years per window of :meth:`summary` (a test switch: the tables do
+    not depend on it)."""
 
     def __init__(self, row, post, m: float = 400.0, d: float = 200.0, KD: float = 1.0, KS: float = 0.0,
                  dS: float = 200.0, device: int = 0, options=None):
@@ -525,6 +527,60 @@ class Future:
         ms = ctypes.c_double()
         check(lib().mdp_future_time_kernel(self._h, seed, nrep, tfut, reps, ctypes.byref(ms)))
         return ms.value
+
+
+    def summary(self, nrep: int, tfut: int = 50, seed: int = 0, rep0: int = 0, hist=True, occ=True):
+        """(hist, occ) over replicates [rep0, rep0 + nrep), uint64 arrays of
+        shape (tfut, n + 1) and (tfut, n): hist[t, m] replicates with exactly m
+        occupied patches after year t + 1 (hist[:, 0] is simulate()'s counts),
+        occ[t, k] replicates with patch k occupied.  A table passed as an array
+        is added to (``mdp_future_summary`` accumulates); ``False`` leaves it
+        out (None is returned in its place)."""
+        def table(x, width):
+            if x is False or x is None:
+                return None
+            if x is True:
+                return np.zeros((tfut, width), dtype=np.uint64)
+            if x.dtype != np.uint64 or x.shape != (tfut, width) or not x.flags.c_contiguous:
+                raise ValueError(f"summary table must be a C-contiguous uint64 array of shape {(tfut, width)}")
+            return x
+        h, o = table(hist, self.n + 1), table(occ, self.n)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        check(lib().mdp_future_summary(self._h, seed, rep0, nrep, tfut,
+                                       h.ctypes.data_as(u64p) if h is not None else None,
+                                       o.ctypes.data_as(u64p) if o is not None else None))
+        return h, o
+
+    def summary_device(self, d_hist: int, d_occ: int, nrep: int, tfut: int, seed: int = 0, rep0: int = 0,
+                       stream: int = 0) -> None:
+        """Into device memory at ``d_hist`` (uint64[tfut, n + 1]) and ``d_occ``
+        (uint64[tfut, n]; either may be 0), overwritten, asynchronously on
+        hipStream ``stream``.  Call check() before trusting the tables."""
+        check(lib().mdp_future_summary_device(self._h, seed, rep0, nrep, tfut, ctypes.c_void_p(d_hist or None),
+                                              ctypes.c_void_p(d_occ or None), ctypes.c_void_p(stream)))
+
+    def time_summary(self, nrep: int, tfut: int, seed: int = 0, reps: int = 10) -> float:
+        ms = ctypes.c_double()
+        check(lib().mdp_future_time_summary(self._h, seed, nrep, tfut, reps, ctypes.byref(ms)))
+        return ms.value
+
+
+def quasi_extinction(hist, m: int) -> np.ndarray:
+    """Replicates with at most ``m`` occupied patches, per year: hist[:, :m+1].sum(1)."""
+    hist = np.asarray(hist)
+    if m < 0:
+        return np.zeros(hist.shape[0], dtype=hist.dtype)
+    return hist[:, :m + 1].sum(axis=1, dtype=hist.dtype)
+
+
+def mean_occupied(hist) -> np.ndarray:
+    """Mean number of occupied patches per year over the replicates of ``hist``
+    (NaN for a year without replicates)."""
+    hist = np.asarray(hist)
+    tot = hist.sum(axis=1).astype(np.float64)
+    w = (hist.astype(np.float64) * np.arange(hist.shape[1], dtype=np.float64)).sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return w / tot
 
 
 def philox(key: int, ctr) -> list:

@@ -1,12 +1,13 @@
 // midaspom_amd/csrc/future_plan_check.cpp -- the future engine's host planner
 // (spom_future_plan.cpp) over one survey row, without a device or the HIP
 // runtime:
-//   future_plan_check ROW M D KD KS DS "OPTIONS"
+//   future_plan_check ROW M D KD KS DS "OPTIONS" [TFUT]
 // ROW is one character per patch: '0' empty, '1' occupied, 'm' missing.
 // Prints the kernel the options select and, for k_future_wide, the layout
 // the kernel is given; checks every entry the kernel can read of the distance
 // image against the n x n table's expression, and the state layout against
-// its inverse.  Exit 0, or mdp_last_error() on stderr and exit 1.
+// its inverse.  With TFUT, one more line: the summary path's window plan for
+// that many years under the options.  Exit 0, or mdp_last_error() on stderr and exit 1.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -28,8 +29,8 @@ uint64_t fnv(const void *p, size_t n)
 
 int main(int argc, char **argv)
 {
-    if (argc != 8) {
-        fprintf(stderr, "usage: future_plan_check ROW M D KD KS DS \"OPTIONS\"\n");
+    if (argc != 8 && argc != 9) {
+        fprintf(stderr, "usage: future_plan_check ROW M D KD KS DS \"OPTIONS\" [TFUT]\n");
         return 2;
     }
     auto fail = []() {
@@ -41,11 +42,37 @@ int main(int argc, char **argv)
     for (uint32_t k = 0; k < n; ++k) row[k] = argv[1][k] == 'm' ? -1 : argv[1][k] - '0';
     const double m = atof(argv[2]), d = atof(argv[3]), KD = atof(argv[4]), KS = atof(argv[5]), dS = atof(argv[6]);
     FutWideMode mode;
-    uint32_t np = 0;
-    if (fut_parse_opts(argv[7], &mode)) return fail();
+    uint32_t np = 0, sum_years = 0;
+    if (fut_parse_opts(argv[7], &mode, &sum_years)) return fail();
     if (fut_select_kernel(n, mode, &np)) return fail();
+    // the summary path's plan (argv[8] years), after everything else
+    auto summary = [&](uint32_t wlen) {
+        if (argc != 9) return 0;
+        FutSumPlan sp;
+        if (fut_sum_plan(n, np, wlen, (uint32_t)strtoul(argv[8], nullptr, 10), sum_years, &sp)) return 1;
+        printf("summary cells %u years %u windows %u lds %u grid %u reps %llu\n", sp.cells, sp.years, sp.windows, sp.lds,
+               sp.maxwg, (unsigned long long)sp.reps);
+        // every LDS cell of a year of k_future_wide lands on its own global cell
+        std::vector<char> hit(2 * (size_t)n + 1, 0);
+        for (uint32_t c = 0; np && c < sp.cells; ++c) {
+            const int32_t g = fut_sum_wide_cell(n, c);
+            if (g < 0) continue;
+            if ((uint32_t)g > 2 * n || hit[g]) {
+                fprintf(stderr, "future_plan_check: LDS cell %u maps to global cell %d\n", c, g);
+                return 2;
+            }
+            hit[g] = 1;
+        }
+        for (size_t g = 0; np && g < hit.size(); ++g)
+            if (!hit[g]) {
+                fprintf(stderr, "future_plan_check: global cell %zu has no LDS cell\n", g);
+                return 2;
+            }
+        return 0;
+    };
     if (np == 0) {
         printf("kernel k_future<%u>\n", n <= 8 ? 8u : n <= 16 ? 16u : n <= 32 ? 32u : 64u);
+        if (const int rc = summary(0)) return rc == 1 ? fail() : 1;
         return 0;
     }
     FutWidePlan p;
@@ -97,5 +124,6 @@ int main(int argc, char **argv)
     printf("states");
     for (uint64_t w : words) printf(" %llx", (unsigned long long)w);
     printf("\ncheck ok\n");
+    if (const int rc = summary(p.len)) return rc == 1 ? fail() : 1;
     return 0;
 }

@@ -18,6 +18,13 @@
  *              (:345), or $MIDASPOM_SEED.  The draws are Philox streams, not
  *              glibc rand(): runs are reproducible per seed and agree with
  *              the reference statistically.
+ *   -H <file>  hist: per future year a line of n+1 cells, the replicates with
+ *              exactly m = 0..n occupied patches after that year
+ *   -O <file>  occ: per future year a line of n cells, the replicates with
+ *              patch k occupied after that year
+ *              Each cell "%llu\t", "\n" per line.  With either flag the run
+ *              goes through mdp_future_summary and -o is written from
+ *              hist[.][0]; without them nothing changes.
  */
 #include <ctype.h>
 #include <math.h>
@@ -39,6 +46,7 @@ struct range {
     unsigned long long seed;
     uint64_t rep0, nrep;
     uint64_t *cnt;  /* [tfut] */
+    uint64_t *hist, *occ;  /* -H / -O: [tfut][n+1] and [tfut][n], else NULL */
     int rc;
     char err[256];
 };
@@ -50,7 +58,14 @@ static void *run_range(void *arg)
     /* the lane kernels up to 64 patches, the patch-parallel kernel up to 1024 */
     r->rc = mdp_future_create_opts(r->pend, r->n, r->post, r->necstep, r->mdisp, r->d, r->KD, r->KS, r->dS, r->dev,
                                    "MDP_FUT_WIDE=auto", &f);
-    if (r->rc == MDP_OK && r->nrep) r->rc = mdp_future_simulate(f, r->seed, r->rep0, r->nrep, r->tfut, r->cnt);
+    if (r->rc == MDP_OK && r->nrep) {
+        if (r->hist) {
+            r->rc = mdp_future_summary(f, r->seed, r->rep0, r->nrep, r->tfut, r->hist, r->occ);
+            for (uint32_t t = 0; t < r->tfut; ++t) r->cnt[t] = r->hist[(size_t)t * (r->n + 1)];
+        } else {
+            r->rc = mdp_future_simulate(f, r->seed, r->rep0, r->nrep, r->tfut, r->cnt);
+        }
+    }
     if (r->rc != MDP_OK) snprintf(r->err, sizeof r->err, "%s", mdp_last_error());
     mdp_future_destroy(f);
     return NULL;
@@ -65,11 +80,12 @@ int main(int argc, char **argv)
     double KS = 0, dS = 200, KD = 1, mdisp = 400.0, d = 200;
     float prioroc = 0.5f;
     const char *finame = "posterior.txt", *fname = "input.txt", *fout = "pext_future.txt";
+    const char *fhist = NULL, *focc = NULL;
     const char *env_seed = getenv("MIDASPOM_SEED");
     unsigned long long seed = env_seed ? strtoull(env_seed, NULL, 0) : (unsigned long long)time(NULL);
     int c;
     opterr = 0;
-    while ((c = getopt(argc, argv, "n:a:m:p:q:d:i:o:S:s:D:g:r:")) != -1) {
+    while ((c = getopt(argc, argv, "n:a:m:p:q:d:i:o:S:s:D:g:r:H:O:")) != -1) {
         switch (c) {
         case 'n': nsimul = atoi(optarg); break;
         case 'a': tfut = atoi(optarg); break;
@@ -84,6 +100,8 @@ int main(int argc, char **argv)
         case 'D': KD = atof(optarg); break;
         case 'g': ngpu = atoi(optarg); break;
         case 'r': seed = strtoull(optarg, NULL, 0); break;
+        case 'H': fhist = optarg; break;
+        case 'O': focc = optarg; break;
         case '?':
             if (optopt == 'c')
                 fprintf(stderr, "Option -%c requires an argument.\n", optopt);
@@ -152,6 +170,11 @@ int main(int argc, char **argv)
         printf("; pr=%lf\n", pr);
     }
     int *lik = calloc(tfut > 0 ? (size_t)tfut : 1, sizeof(int));
+    /* -H / -O: the tables summed over the ranges */
+    const int summary = fhist || focc;
+    const size_t nhist = (size_t)(tfut > 0 ? tfut : 0) * (n + 1), nocc = (size_t)(tfut > 0 ? tfut : 0) * n;
+    uint64_t *hist = summary ? calloc(nhist ? nhist : 1, sizeof(uint64_t)) : NULL;
+    uint64_t *occ = summary ? calloc(nocc ? nocc : 1, sizeof(uint64_t)) : NULL;
     time(&start);
     printf("Starting likelihood computation\n");
     int rc = MDP_OK;
@@ -166,7 +189,9 @@ int main(int argc, char **argv)
         for (int r = 0; r < ngpu; ++r) {
             const uint64_t r0 = r == 0 ? 0 : (uint64_t)r * avg + rem, r1 = (uint64_t)(r + 1) * avg + rem;
             rg[r] = (struct range){pend, post, n, necstep, (uint32_t)tfut, mdisp, d, KD, KS, dS, r % ndev, seed,
-                                   r0, r1 - r0, calloc((size_t)tfut, sizeof(uint64_t)), 0, ""};
+                                   r0, r1 - r0, calloc((size_t)tfut, sizeof(uint64_t)),
+                                   summary ? calloc(nhist, sizeof(uint64_t)) : NULL,
+                                   summary ? calloc(nocc, sizeof(uint64_t)) : NULL, 0, ""};
         }
         for (int r = 1; r < ngpu; ++r) started[r] = pthread_create(&th[r], NULL, run_range, &rg[r]) == 0;
         run_range(&rg[0]);
@@ -180,7 +205,11 @@ int main(int argc, char **argv)
                 fprintf(stderr, "GPU future simulation failed: %s\n", rg[r].err);
             }
             for (int t = 0; t < tfut; ++t) lik[t] += (int)rg[r].cnt[t];
+            for (size_t i = 0; summary && i < nhist; ++i) hist[i] += rg[r].hist[i];
+            for (size_t i = 0; summary && i < nocc; ++i) occ[i] += rg[r].occ[i];
             free(rg[r].cnt);
+            free(rg[r].hist);
+            free(rg[r].occ);
         }
         free(rg), free(th), free(started);
     }
@@ -195,6 +224,26 @@ int main(int argc, char **argv)
     for (int t = 0; t < tfut; ++t) fprintf(fe, "%d\t", lik[t]);
     fclose(fe);
     printf("done\n");
+    for (int which = 0; which < 2; ++which) {
+        const char *name = which ? focc : fhist;
+        if (!name) continue;
+        const uint64_t *tab = which ? occ : hist;
+        const uint32_t width = which ? n : n + 1;
+        printf("Writing on file %s... ", name);
+        FILE *ft = fopen(name, "wb");
+        if (!ft) {
+            fprintf(stderr, "cannot write %s\n", name);
+            return 1;
+        }
+        for (int t = 0; t < tfut; ++t) {
+            for (uint32_t k = 0; k < width; ++k) fprintf(ft, "%llu\t", (unsigned long long)tab[(size_t)t * width + k]);
+            fprintf(ft, "\n");
+        }
+        fclose(ft);
+        printf("done\n");
+    }
+    free(hist);
+    free(occ);
     time(&end);
     printf("Finished. It took  %.2lf min\n", difftime(end, start) / 60.0);
     free(lik);

@@ -23,6 +23,10 @@
 // deterministic).
 // Surveys of more than 64 patches (mdp_future_create_opts, MDP_FUT_WIDE) run
 // the patch-parallel k_future_wide<NP> further down: one wave per replicate.
+// The ensemble's summaries (mdp_future_summary: per-year histograms of the
+// number of occupied patches, per-patch occupancy counts) come from the
+// variants k_future_tab<NM> and k_future_wide_tab<NP>, one launch per window
+// of years; the kernels of the counts path are not touched by them.
 //
 // Random numbers: the reference draws rand()/RAND_MAX from one sequential
 // stream per process (srand(time(NULL)), :345).  Here every draw is
@@ -440,6 +444,397 @@ __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const 
     for (uint32_t t = threadIdx.x; t < a.tfut; t += kFutBlock) partial[(size_t)blockIdx.x * a.tfut + t] = cnt[t];
 }
 
+// ---------------------------------------------------------------------------
+// The summary path (mdp_future_summary): hist[t][m], the replicates with
+// exactly m occupied patches after year t + 1, and occ[t][k], those with
+// patch k occupied.  k_future_tab<NM> and k_future_wide_tab<NP> run the same
+// years on the same draws as k_future<NM> and k_future_wide<NP> (the model is
+// restated in the fut_* functions below, so that the kernels above stay the
+// code they were) over one window [t0, t1) of years per launch, and count
+// into a window table in LDS: 32-bit integer atomics and ballots, exact in
+// any order.  Between launches a replicate rests in a record (its posterior
+// cell and occupancy); the draws are addressed, so resuming is exact.  Every
+// workgroup adds its non-zero cells to the global 64-bit table
+// tab[t][2n+1] (hist, then occ) with integer atomics.
+// ---------------------------------------------------------------------------
+struct FutSumWin {
+    uint32_t t0, t1;   // the launch's years
+    uint32_t cells;    // LDS cells per year (FutSumPlan)
+    uint32_t last;     // t1 == tfut: no record is written
+};
+
+// (e, c) cell of replicate rg from the posterior, with the reference's
+// carry-over (:361-377): idx < lvalid is the cell, lvalid "never found";
+// init_w the replicate's initial-state draw.  overflow() runs when the
+// look-back passes kLookBack replicates.
+template <typename F>
+__device__ __forceinline__ void fut_draw(uint32_t key0, uint32_t key1, uint32_t lvalid, double pscale,
+                                         const double *__restrict__ pcum, uint64_t rg, uint32_t &idx,
+                                         uint32_t &init_w, F overflow)
+{
+    idx = lvalid, init_w = 0;
+    uint64_t q = rg;
+    for (uint32_t step = 0;; ++step) {
+        const u32x4 w = philox(key0, key1, u32x4{(uint32_t)q, (uint32_t)(q >> 32), 0xffffffffu, 0u});
+        if (step == 0) init_w = w.y >> 1;
+        if (lvalid == 0) break;  // empty / all-NaN posterior: never found
+        const double pec = pscale * (double)(w.x >> 1) / kRandMax;
+        idx = upper_bound(pcum, lvalid, pec);
+        if (idx < lvalid || q == 0) break;
+        if (step + 1 >= kLookBack) {  // posterior mass too small for an exact look-back
+            overflow();
+            break;
+        }
+        --q;
+    }
+}
+
+// E = min(1, e/K_D) (simpij :67, :74) and c of posterior cell idx
+__device__ __forceinline__ double fut_rates(uint32_t idx, uint32_t lvalid, uint32_t necstep, double K, double &c)
+{
+    uint32_t ie = 0, ic = 0;
+    if (idx < lvalid) ie = idx / necstep, ic = idx - ie * necstep;
+    const double e = (double)ie * 0.01;
+    c = (double)ic * 0.01;
+    double E = e / K;
+    if (E > 1) E = 1;
+    return E;
+}
+
+// initial state of the lane kernels: missing columns filled from init (first
+// missing = MSB) (:315-321, :378)
+__device__ __forceinline__ uint64_t fut_init(uint64_t occ0, uint32_t nmiss, const uint64_t *__restrict__ missbit,
+                                             uint32_t init_w)
+{
+    const uint32_t init = init_w & ((1u << nmiss) - 1u);
+    uint64_t occ = occ0;
+    for (uint32_t q = 0; q < nmiss; ++q)
+        if ((init >> (nmiss - 1 - q)) & 1u) occ |= missbit[q];
+    return occ;
+}
+
+// one year of replicate rg (simpij :64-110): the occupancy after year t + 1
+template <int NM>
+__device__ __forceinline__ uint64_t fut_year(const FutArgs &a, const double *__restrict__ MK,
+                                             const double *__restrict__ src, const double *Ts, uint64_t rg,
+                                             uint32_t t, uint32_t npairs, uint64_t occ, double E, double c)
+{
+    uint64_t surv = 0;
+    uint32_t colw[NM];
+#pragma unroll
+    for (int m = 0; m < NM / 2; ++m) {
+        if ((uint32_t)m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, (uint32_t)m});
+            const uint32_t k0 = 2 * m, k1 = 2 * m + 1;
+            colw[k0] = w.y >> 1;
+            colw[k1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (:75-82)
+            if (((occ >> k0) & 1u) && u_gt(w.x >> 1, E)) surv |= 1ull << k0;
+            if (((occ >> k1) & 1u) && u_gt(w.z >> 1, E)) surv |= 1ull << k1;
+        } else {
+            colw[2 * m] = colw[2 * m + 1] = 0;
+        }
+    }
+    // colonisation sums, ascending l for every k (:89-95)
+    double s1[NM];
+    if constexpr (NM == kTabN) {
+        const double2 *row = reinterpret_cast<const double2 *>(Ts + (uint32_t)surv * kTabN);
+#pragma unroll
+        for (int k = 0; k < NM; k += 2) {
+            const double2 v = row[k / 2];
+            s1[k] = v.x, s1[k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NM; ++k) s1[k] = 0.0;
+        for (uint32_t l = 0; l < a.n; ++l) {
+            const bool on = (surv >> l) & 1u;
+#pragma unroll
+            for (int k = 0; k < NM; ++k) s1[k] += on ? MK[l * NM + k] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < NM; ++k) s1[k] += src[k];
+    }
+    uint64_t nw = surv;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+        if ((uint32_t)k < a.n && !((surv >> k) & 1u)) {
+            double pc = c * s1[k];  // :95-97
+            if (pc > 1) pc = 1;
+            if (u_lt(colw[k], pc)) nw |= 1ull << k;  // :98-101
+        }
+    }
+    return nw;
+}
+
+template <int NM>
+__global__ __launch_bounds__(kFutBlock) void k_future_tab(FutArgs a, FutSumWin w, const double *__restrict__ MK,
+                                                          const double *__restrict__ src,
+                                                          const double *__restrict__ pcum,
+                                                          const uint64_t *__restrict__ missbit,
+                                                          const double *__restrict__ T,
+                                                          uint64_t *__restrict__ rec_occ,
+                                                          uint32_t *__restrict__ rec_idx,
+                                                          unsigned long long *__restrict__ tab,
+                                                          uint32_t *__restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    // NM == 8: the colonisation table (16 KB) first, then the window table
+    double *Ts = dyn;
+    uint32_t *win = (uint32_t *)(dyn + (NM == kTabN ? (1 << kTabN) * kTabN : 0));
+    const uint32_t ncell = (w.t1 - w.t0) * w.cells;
+    if constexpr (NM == kTabN) {
+        for (uint32_t i = threadIdx.x; i < (1u << kTabN) * kTabN / 2; i += kFutBlock)
+            reinterpret_cast<double2 *>(Ts)[i] = reinterpret_cast<const double2 *>(T)[i];
+    }
+    for (uint32_t i = threadIdx.x; i < ncell; i += kFutBlock) win[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t npairs = (a.n + 1) >> 1;
+    // wave-uniform trip count: the lanes past the last replicate stay in the
+    // ballots (inactive, counted nowhere), so lane k is there to take patch k
+    for (uint64_t rb = (uint64_t)blockIdx.x * kFutBlock + (threadIdx.x & ~63u); rb < a.nrep;
+         rb += (uint64_t)gridDim.x * kFutBlock) {
+        const uint64_t r = rb + lane, rg = a.rep0 + r;
+        const bool act = r < a.nrep;
+        uint32_t idx = a.lvalid;
+        uint64_t occ = 0;
+        if (act) {
+            if (w.t0 == 0) {
+                uint32_t init_w;
+                fut_draw(a.key0, a.key1, a.lvalid, a.pscale, pcum, rg, idx, init_w, [&]() { atomicOr(err, 1u); });
+                occ = fut_init(a.occ0, a.nmiss, missbit, init_w);
+            } else {
+                idx = rec_idx[r];
+                occ = rec_occ[r];
+            }
+        }
+        double c;
+        const double E = fut_rates(idx, a.lvalid, a.necstep, a.K, c);
+        for (uint32_t t = w.t0; t < w.t1; ++t) {
+            if (act) occ = fut_year<NM>(a, MK, src, Ts, rg, t, npairs, occ, E, c);
+            uint32_t *row = win + (t - w.t0) * w.cells;
+            // hist: one LDS atomic per distinct occupied count in the wave
+            const uint32_t m = (uint32_t)__popcll(occ);
+            uint64_t rem = __ballot(act);
+            while (rem) {
+                const uint32_t lead = (uint32_t)__builtin_ctzll(rem);
+                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)m, (int)lead);
+                const uint64_t same = __ballot(act && m == v);
+                if (lane == lead) atomicAdd(&row[v], (uint32_t)__popcll(same));
+                rem &= ~same;
+            }
+            // occ: lane k takes the wave's count of patch k
+            uint32_t mine = 0;
+            for (uint32_t k = 0; k < a.n; ++k) {
+                const uint32_t cnt = (uint32_t)__popcll(__ballot(act && ((occ >> k) & 1u)));
+                if (lane == k) mine = cnt;
+            }
+            if (mine) atomicAdd(&row[a.n + 1 + lane], mine);
+        }
+        if (act && !w.last) {
+            rec_idx[r] = idx;
+            rec_occ[r] = occ;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < ncell; i += kFutBlock) {
+        const uint32_t v = win[i];
+        if (v) atomicAdd(&tab[(size_t)w.t0 * w.cells + i], (unsigned long long)v);
+    }
+}
+
+// bit 2j+p set where patch 2*(lane + 64*j) + p exists
+template <int NP>
+__device__ __forceinline__ uint32_t fut_wide_live(uint32_t n, uint32_t lane)
+{
+    uint32_t live = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t k0 = 2 * (lane + 64u * j);
+        if (k0 < n) live |= 1u << (2 * j);
+        if (k0 + 1 < n) live |= 2u << (2 * j);
+    }
+    return live;
+}
+
+// initial state of a wave's replicate: missing patches filled from init
+// (first missing = MSB) (:315-321, :378)
+__device__ __forceinline__ uint32_t fut_wide_init(uint32_t occ_init, uint32_t nmiss, const uint32_t *__restrict__ miss,
+                                                  uint32_t init_w, uint32_t lane)
+{
+    const uint32_t init = init_w & ((1u << nmiss) - 1u);
+    uint32_t occ = occ_init;
+    for (uint32_t q = 0; q < nmiss; ++q) {
+        const uint32_t mq = miss[q];
+        if (((init >> (nmiss - 1 - q)) & 1u) && lane == (mq >> 8)) occ |= 1u << (mq & 0xffu);
+    }
+    return occ;
+}
+
+// one year of the wave's replicate rg: the lane's occupancy word after year t + 1
+template <int NP>
+__device__ __forceinline__ uint32_t fut_wide_year(const FutWideArgs &a, const double2 *G2,
+                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
+                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
+                                                  double E, double c)
+{
+    uint64_t bal[NP][2];
+    uint32_t colw[2 * NP];
+    uint32_t surv = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t m = lane + 64u * j;
+        bool s0 = false, s1 = false;
+        colw[2 * j] = colw[2 * j + 1] = 0;
+        if (m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
+            colw[2 * j] = w.y >> 1;
+            colw[2 * j + 1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (:75-82)
+            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
+            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
+        }
+        bal[j][0] = __ballot(s0);
+        bal[j][1] = __ballot(s1);
+        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
+    }
+    // colonisation sums, ascending l for every k (:89-95): patch
+    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
+    double s[2 * NP];
+#pragma unroll
+    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        uint64_t both = bal[j][0] | bal[j][1];
+        while (both) {
+            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
+            both &= both - 1;
+#pragma unroll
+            for (uint32_t p = 0; p < 2; ++p) {
+                if (!((bal[j][p] >> lam) & 1u)) continue;
+                const uint32_t l = 2 * (lam + 64u * j) + p;
+                const uint32_t base = a.n - 1 - l;
+                const uint32_t slot0 = (base & 1u) ? (a.len + base - 1) >> 1 : base >> 1;
+                const double2 *row = G2 + slot0 + lane;
+#pragma unroll
+                for (int jj = 0; jj < NP; ++jj) {
+                    const double2 v = row[64 * jj];
+                    s[2 * jj] += v.x;
+                    s[2 * jj + 1] += v.y;
+                }
+            }
+        }
+    }
+    uint32_t nw = surv;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint32_t bit = 1u << (2 * j + p);
+            if ((live & bit) && !(surv & bit)) {
+                double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
+                if (pc > 1) pc = 1;
+                if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
+            }
+        }
+    }
+    return nw;
+}
+
+template <int NP>
+__global__ __launch_bounds__(kFutBlock) void k_future_wide_tab(FutWideArgs a, FutSumWin w,
+                                                               const double *__restrict__ image,
+                                                               const double *__restrict__ src,
+                                                               const double *__restrict__ pcum,
+                                                               const uint32_t *__restrict__ occ0,
+                                                               const uint32_t *__restrict__ miss,
+                                                               uint32_t *__restrict__ rec_occ,
+                                                               uint32_t *__restrict__ rec_idx,
+                                                               unsigned long long *__restrict__ tab,
+                                                               uint32_t *__restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    // both copies of the distance image first (2*len doubles), then the window
+    // table: per year hist[n+1], then occ in lane order -- bit b of lane lam
+    // (patch 2*(lam + 64*(b/2)) + b%2) in cell 64*b + lam, so that the lanes
+    // of a wave hit consecutive banks
+    double2 *G2 = reinterpret_cast<double2 *>(dyn);
+    uint32_t *win = reinterpret_cast<uint32_t *>(dyn + 2 * a.len);
+    const uint32_t ncell = (w.t1 - w.t0) * w.cells;
+    for (uint32_t i = threadIdx.x; i < a.len; i += kFutBlock) G2[i] = reinterpret_cast<const double2 *>(image)[i];
+    for (uint32_t i = threadIdx.x; i < ncell; i += kFutBlock) win[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t npairs = (a.n + 1) >> 1;
+    const uint32_t occ_init = occ0[lane];
+    const uint32_t live = fut_wide_live<NP>(a.n, lane);
+    for (uint64_t r = (uint64_t)blockIdx.x * kWideWaves + wave; r < a.nrep; r += (uint64_t)gridDim.x * kWideWaves) {
+        const uint64_t rg = a.rep0 + r;  // wave-uniform
+        uint32_t idx, occ;
+        if (w.t0 == 0) {
+            uint32_t init_w;
+            fut_draw(a.key0, a.key1, a.lvalid, a.pscale, pcum, rg, idx, init_w, [&]() {
+                if (lane == 0) atomicOr(err, 1u);
+            });
+            occ = fut_wide_init(occ_init, a.nmiss, miss, init_w, lane);
+        } else {
+            idx = rec_idx[r];
+            occ = rec_occ[r * 64 + lane];
+        }
+        double c;
+        const double E = fut_rates(idx, a.lvalid, a.necstep, a.K, c);
+        for (uint32_t t = w.t0; t < w.t1; ++t) {
+            if (a.ks0 && __ballot(occ != 0) == 0) {
+                // no source and nobody left (at a window's start too): every
+                // sum is 0, pC = c*0, and no draw is below 0 -- hist[tt][0]
+                // for the rest of the window, nothing to occ
+                for (uint32_t tt = t + lane; tt < w.t1; tt += 64) atomicAdd(&win[(tt - w.t0) * w.cells], 1u);
+                break;
+            }
+            occ = fut_wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E, c);
+            uint32_t *row = win + (t - w.t0) * w.cells;
+            uint32_t m = 0;
+#pragma unroll
+            for (int b = 0; b < 2 * NP; ++b) {
+                const bool on = (occ >> b) & 1u;
+                m += (uint32_t)__popcll(__ballot(on));
+                if (on) atomicAdd(&row[a.n + 1 + 64 * b + lane], 1u);
+            }
+            if (lane == 0) atomicAdd(&row[m], 1u);
+        }
+        if (!w.last) {
+            if (lane == 0) rec_idx[r] = idx;
+            rec_occ[r * 64 + lane] = occ;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < ncell; i += kFutBlock) {
+        const uint32_t v = win[i];
+        if (!v) continue;
+        const uint32_t y = i / w.cells, cl = i - y * w.cells;
+        const int32_t g = fut_sum_wide_cell(a.n, cl);
+        if (g >= 0) atomicAdd(&tab[(size_t)(w.t0 + y) * (2 * a.n + 1) + (uint32_t)g], (unsigned long long)v);
+    }
+}
+
+// tab[t][2n+1] -> hist[t][n+1] and occ[t][n] (either may be null)
+__global__ __launch_bounds__(256) void k_future_split(const unsigned long long *__restrict__ tab, uint32_t ncell,
+                                                      uint32_t n, unsigned long long *__restrict__ hist,
+                                                      unsigned long long *__restrict__ occ)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ncell) return;
+    const uint32_t t = i / (2 * n + 1), c = i - t * (2 * n + 1);
+    if (c <= n) {
+        if (hist) hist[(size_t)t * (n + 1) + c] = tab[i];
+    } else if (occ) {
+        occ[(size_t)t * n + (c - n - 1)] = tab[i];
+    }
+}
+
 template <typename T>
 int dev_up(T **p, const std::vector<T> &h)
 {
@@ -469,6 +864,14 @@ struct mdp_future {
     uint32_t *docc0 = nullptr, *dwmiss = nullptr, *dstates = nullptr;
     size_t states_cap = 0;
     char kname[32] = "";
+    // the summary path: its window cap (MDP_FUT_SUM_YEARS), the global table
+    // [tfut][2n+1] and the records of a launch's replicates
+    uint32_t sum_years = 0;
+    unsigned long long *dtab = nullptr;
+    size_t tab_cap = 0;
+    void *drec_occ = nullptr;
+    uint32_t *drec_idx = nullptr;
+    uint64_t rec_cap = 0;
 };
 
 namespace {
@@ -605,6 +1008,121 @@ int fut_check_args(mdp_future *f, uint64_t nrep, uint32_t tfut)
     return MDP_OK;
 }
 
+
+// the whole summary of replicates [rep0, rep0 + nrep) into f->dtab on st:
+// the table zeroed, then for every range of p.reps replicates one launch per
+// window of years
+int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
+                    hipStream_t st, uint32_t *derr)
+{
+    const size_t ncell = (size_t)tfut * (2 * f->n + 1);
+    FUT_TRY(hipMemsetAsync(f->dtab, 0, ncell * sizeof(unsigned long long), st));
+    const uint64_t per = f->np ? kWideWaves : kFutBlock;
+    for (uint64_t done = 0; done < nrep; done += p.reps) {
+        const uint64_t cnt = std::min<uint64_t>(p.reps, nrep - done);
+        const int nwg = (int)std::min<uint64_t>((cnt + per - 1) / per, p.maxwg);
+        for (uint32_t t0 = 0; t0 < tfut; t0 += p.years) {
+            FutSumWin w{};
+            w.t0 = t0;
+            w.t1 = std::min(tfut, t0 + p.years);
+            w.cells = p.cells;
+            w.last = w.t1 == tfut;
+            const size_t lds = (size_t)p.lds;
+            if (f->np) {
+                FutWideArgs a{};
+                a.n = f->n;
+                a.nmiss = f->nmiss;
+                a.tfut = tfut;
+                a.lvalid = f->lvalid;
+                a.rep0 = rep0 + done;
+                a.nrep = cnt;
+                a.key0 = (uint32_t)seed;
+                a.key1 = (uint32_t)(seed >> 32);
+                a.necstep = f->necstep;
+                a.len = f->wlen;
+                a.ks0 = f->ks0;
+                a.pscale = f->pscale;
+                a.K = f->K;
+                switch (f->np) {
+#define FUT_WCASE(NPV)                                                                                     \
+    case NPV:                                                                                               \
+        hipLaunchKernelGGL(k_future_wide_tab<NPV>, dim3(nwg), dim3(kFutBlock), lds, st, a, w, f->dimage,  \
+                           f->dsrc, f->dpcum, f->docc0, f->dwmiss, (uint32_t *)f->drec_occ, f->drec_idx,   \
+                           f->dtab, derr);                                                                  \
+        break;
+                    FUT_WCASE(1)
+                    FUT_WCASE(2)
+                    FUT_WCASE(4)
+                    FUT_WCASE(8)
+#undef FUT_WCASE
+                default:
+                    return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", f->np);
+                }
+            } else {
+                FutArgs a{};
+                a.n = f->n;
+                a.nmiss = f->nmiss;
+                a.tfut = tfut;
+                a.lvalid = f->lvalid;
+                a.occ0 = f->occ0;
+                a.rep0 = rep0 + done;
+                a.nrep = cnt;
+                a.key0 = (uint32_t)seed;
+                a.key1 = (uint32_t)(seed >> 32);
+                a.necstep = f->necstep;
+                a.pscale = f->pscale;
+                a.K = f->K;
+                switch (f->nm) {
+#define FUT_CASE(NMV)                                                                                      \
+    case NMV:                                                                                               \
+        hipLaunchKernelGGL(k_future_tab<NMV>, dim3(nwg), dim3(kFutBlock), lds, st, a, w, f->dMK, f->dsrc, \
+                           f->dpcum, f->dmiss, f->dT, (uint64_t *)f->drec_occ, f->drec_idx, f->dtab, derr); \
+        break;
+                    FUT_CASE(8)
+                    FUT_CASE(16)
+                    FUT_CASE(32)
+                    FUT_CASE(64)
+#undef FUT_CASE
+                default:
+                    return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", f->nm);
+                }
+            }
+            FUT_TRY(hipGetLastError());
+        }
+    }
+    return MDP_OK;
+}
+
+// refusals (no device call), then the table and, for more than one window,
+// the records of p.reps replicates at the most
+int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan *p)
+{
+    if (!f) return mdp_set_error(MDP_EINVAL, "null future engine");
+    if (nrep > (1ull << 62)) return mdp_set_error(MDP_EINVAL, "replicate count too large");
+    if (int rc = fut_sum_plan(f->n, f->np, f->wlen, tfut, f->sum_years, p)) return rc;
+    FUT_TRY(hipSetDevice(f->device));
+    const size_t ncell = (size_t)tfut * (2 * f->n + 1);
+    if (ncell > f->tab_cap) {
+        if (f->dtab) (void)hipFree(f->dtab);
+        f->dtab = nullptr;
+        f->tab_cap = 0;
+        FUT_TRY(hipMalloc((void **)&f->dtab, ncell * sizeof(unsigned long long)));
+        f->tab_cap = ncell;
+    }
+    const uint64_t recs = p->windows > 1 ? std::min<uint64_t>(nrep, p->reps) : 0;
+    if (recs > f->rec_cap) {
+        if (f->drec_occ) (void)hipFree(f->drec_occ);
+        if (f->drec_idx) (void)hipFree(f->drec_idx);
+        f->drec_occ = nullptr;
+        f->drec_idx = nullptr;
+        f->rec_cap = 0;
+        FUT_TRY(hipMalloc(&f->drec_occ, (size_t)recs * (f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t))));
+        FUT_TRY(hipMalloc((void **)&f->drec_idx, (size_t)recs * sizeof(uint32_t)));
+        f->rec_cap = recs;
+    }
+    return MDP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -612,7 +1130,8 @@ extern "C" {
 // mdp_future_create (mode kFutWideOff) and mdp_future_create_opts; every
 // refusal of an argument comes before the first HIP call
 static int fut_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m, double d,
-                      double KD, double KS, double dS, int device, FutWideMode mode, mdp_future **out)
+                      double KD, double KS, double dS, int device, FutWideMode mode, uint32_t sum_years,
+                      mdp_future **out)
 {
     if (!last_row || !out || n == 0) return mdp_set_error(MDP_EINVAL, "empty survey row");
     uint32_t np = 0;
@@ -627,6 +1146,7 @@ static int fut_create(const int32_t *last_row, uint32_t n, const double *post, u
     f->n = n;
     f->nm = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
     f->np = np;
+    f->sum_years = sum_years;
     f->K = KD;
     f->necstep = necstep;
     if (np) snprintf(f->kname, sizeof f->kname, "k_future_wide<%u>", np);
@@ -712,6 +1232,15 @@ static int fut_create(const int32_t *last_row, uint32_t n, const double *post, u
             return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d", f->kname,
                                  fut_wide_lds(f, kFutMaxT), device);
         }
+        // the summary kernel: the image and one window's table
+        const void *fs = np == 1 ? (const void *)k_future_wide_tab<1> : np == 2 ? (const void *)k_future_wide_tab<2>
+                       : np == 4 ? (const void *)k_future_wide_tab<4> : (const void *)k_future_wide_tab<8>;
+        const size_t sum_lds = (size_t)2 * f->wlen * sizeof(double) + kFutSumTableBytes;
+        if (hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sum_lds) != hipSuccess) {
+            mdp_future_destroy(f);
+            return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d (summary)", f->kname, sum_lds,
+                                 device);
+        }
     } else if ((rc = dev_up(&f->dMK, MK)) || (rc = dev_up(&f->dsrc, src)) || (rc = dev_up(&f->dpcum, pcum)) ||
                (rc = dev_up(&f->dmiss, miss))) {
         mdp_future_destroy(f);
@@ -745,7 +1274,7 @@ static int fut_create(const int32_t *last_row, uint32_t n, const double *post, u
 int mdp_future_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
                       double d, double KD, double KS, double dS, int device, mdp_future **out)
 {
-    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, kFutWideOff, out);
+    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, kFutWideOff, 0, out);
 }
 
 int mdp_future_create_opts(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m,
@@ -753,8 +1282,9 @@ int mdp_future_create_opts(const int32_t *last_row, uint32_t n, const double *po
                            mdp_future **out)
 {
     FutWideMode mode;
-    if (int rc = fut_parse_opts(opts, &mode)) return rc;
-    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, mode, out);
+    uint32_t sum_years;
+    if (int rc = fut_parse_opts(opts, &mode, &sum_years)) return rc;
+    return fut_create(last_row, n, post, necstep, m, d, KD, KS, dS, device, mode, sum_years, out);
 }
 
 const char *mdp_future_kernel(const mdp_future *f) { return f ? f->kname : ""; }
@@ -816,6 +1346,9 @@ void mdp_future_destroy(mdp_future *f)
     (void)hipFree(f->docc0);
     (void)hipFree(f->dwmiss);
     (void)hipFree(f->dstates);
+    (void)hipFree(f->dtab);
+    (void)hipFree(f->drec_occ);
+    (void)hipFree(f->drec_idx);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
     if (f->stream) (void)hipStreamDestroy(f->stream);
@@ -889,6 +1422,70 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     FUT_TRY(hipEventRecord(f->ev0, f->stream));
     for (int i = 0; i < reps; ++i)
         if ((rc = fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1))) return rc;
+    FUT_TRY(hipEventRecord(f->ev1, f->stream));
+    FUT_TRY(hipEventSynchronize(f->ev1));
+    float t = 0;
+    FUT_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
+    *ms = (double)t / reps;
+    return MDP_OK;
+}
+
+int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
+                              uint64_t *d_hist, uint64_t *d_occ, void *stream)
+{
+    if (!d_hist && !d_occ) return mdp_set_error(MDP_EINVAL, "null hist and occ");
+    FutSumPlan p;
+    int rc = fut_summary_prepare(f, nrep, tfut, &p);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
+    // the sticky look-back flag of the device path (mdp_future_check)
+    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, st, f->derr))) return rc;
+    const uint32_t ncell = tfut * (2 * f->n + 1);
+    hipLaunchKernelGGL(k_future_split, dim3((ncell + 255) / 256), dim3(256), 0, st, f->dtab, ncell, f->n,
+                       (unsigned long long *)d_hist, (unsigned long long *)d_occ);
+    FUT_TRY(hipGetLastError());
+    return MDP_OK;
+}
+
+int mdp_future_summary(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut, uint64_t *hist,
+                       uint64_t *occ)
+{
+    if (!hist && !occ) return mdp_set_error(MDP_EINVAL, "null hist and occ");
+    FutSumPlan p;
+    int rc = fut_summary_prepare(f, nrep, tfut, &p);
+    if (rc) return rc;
+    if (nrep == 0) return MDP_OK;
+    FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, f->stream, f->derr + 1))) return rc;
+    const uint32_t n = f->n, cells = 2 * n + 1;
+    std::vector<unsigned long long> h((size_t)tfut * cells);
+    uint32_t err = 0;
+    FUT_TRY(hipMemcpyAsync(h.data(), f->dtab, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    FUT_TRY(hipStreamSynchronize(f->stream));
+    if (err)
+        return mdp_set_error(MDP_EUNSUPPORTED,
+                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
+                             "below the (necstep-1)^2 scale)",
+                             kLookBack);
+    for (uint32_t t = 0; t < tfut; ++t) {
+        const unsigned long long *row = h.data() + (size_t)t * cells;
+        for (uint32_t m = 0; hist && m <= n; ++m) hist[(size_t)t * (n + 1) + m] += row[m];
+        for (uint32_t k = 0; occ && k < n; ++k) occ[(size_t)t * n + k] += row[n + 1 + k];
+    }
+    return MDP_OK;
+}
+
+int mdp_future_time_summary(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t tfut, int reps, double *ms)
+{
+    FutSumPlan p;
+    int rc = fut_summary_prepare(f, nrep, tfut, &p);
+    if (rc) return rc;
+    if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
+    if ((rc = fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1))) return rc;
+    FUT_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int i = 0; i < reps; ++i)
+        if ((rc = fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1))) return rc;
     FUT_TRY(hipEventRecord(f->ev1, f->stream));
     FUT_TRY(hipEventSynchronize(f->ev1));
     float t = 0;

@@ -6,9 +6,10 @@
 #include <cmath>
 #include <string>
 
-int fut_parse_opts(const char *s, FutWideMode *mode)
+int fut_parse_opts(const char *s, FutWideMode *mode, uint32_t *sum_years)
 {
     *mode = kFutWideOff;
+    if (sum_years) *sum_years = 0;
     if (!s) return MDP_OK;
     std::string cur;
     auto flush = [&]() -> int {
@@ -16,6 +17,19 @@ int fut_parse_opts(const char *s, FutWideMode *mode)
         const size_t eq = cur.find('=');
         const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string("1") : cur.substr(eq + 1);
         cur.clear();
+        if (k == "MDP_FUT_SUM_YEARS") {
+            // 1 to 5 decimal digits, at most kFutSumMaxT
+            uint32_t y = 0;
+            bool ok = !v.empty() && v.size() <= 5;
+            for (size_t i = 0; ok && i < v.size(); ++i) {
+                ok = v[i] >= '0' && v[i] <= '9';
+                y = y * 10 + (uint32_t)(v[i] - '0');
+            }
+            if (!ok || y > kFutSumMaxT)
+                return mdp_set_error(MDP_EINVAL, "MDP_FUT_SUM_YEARS=%s (expected 0..%u)", v.c_str(), kFutSumMaxT);
+            if (sum_years) *sum_years = y;
+            return MDP_OK;
+        }
         if (k != "MDP_FUT_WIDE") return mdp_set_error(MDP_EINVAL, "unknown future option '%s'", k.c_str());
         if (v == "0") *mode = kFutWideOff;
         else if (v == "auto") *mode = kFutWideAuto;
@@ -102,4 +116,28 @@ void fut_wide_unpack(const uint32_t *lanes, uint64_t nrep, uint32_t n, uint32_t 
             if ((lanes[r * 64 + lane] >> bit) & 1u) w[k >> 6] |= 1ull << (k & 63u);
         }
     }
+}
+
+int fut_sum_plan(uint32_t n, uint32_t np, uint32_t wlen, uint32_t tfut, uint32_t cap, FutSumPlan *plan)
+{
+    if (!plan || n == 0 || n > (np ? 128 * np : kFutLaneMaxN))
+        return mdp_set_error(MDP_EINVAL, "internal: summary plan of %u patches with %u pairs per lane", n, np);
+    if (tfut == 0 || tfut > kFutSumMaxT)
+        return mdp_set_error(MDP_EUNSUPPORTED, "duration %u outside 1..%u years", tfut, kFutSumMaxT);
+    if ((uint64_t)tfut * (2 * n + 1) > kFutSumMaxCells)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%u years x %u cells: the summary tables hold at most %llu cells", tfut,
+                             2 * n + 1, (unsigned long long)kFutSumMaxCells);
+    FutSumPlan &p = *plan;
+    p = FutSumPlan();
+    p.cells = np ? n + 1 + 128 * np : 2 * n + 1;
+    p.years = kFutSumTableBytes / (4 * p.cells);  // >= 1: a year is at most 2049 cells
+    if (p.years > tfut) p.years = tfut;
+    if (cap && p.years > cap) p.years = cap;
+    p.windows = (tfut + p.years - 1) / p.years;
+    const uint32_t fixed = np ? 2 * wlen * (uint32_t)sizeof(double) : n <= 8 ? 16384u : 0u;
+    p.lds = fixed + p.years * p.cells * 4;
+    // waves per SIMD of k_future_wide_tab<1|2|4|8>: 7, 7, 5, 3; of k_future_tab<8|16|32|64>: 7, 3, 2, 1
+    p.maxwg = np ? (np <= 2 ? 2048u : np == 4 ? 1280u : 768u) : n <= 8 ? 2048u : n <= 16 ? 1024u : 512u;
+    p.reps = p.windows == 1 ? kFutSumOneWindowReps : np ? kFutSumWideReps : kFutSumLaneReps;
+    return MDP_OK;
 }

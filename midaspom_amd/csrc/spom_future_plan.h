@@ -20,8 +20,10 @@ enum FutWideMode { kFutWideOff = 0, kFutWideAuto = 1, kFutWideOn = 2 };
 
 // "NAME=VALUE" pairs in the grammar of mdp_engine_create_opts (separators
 // ';', ',' or white space); NULL or "" leaves the default, kFutWideOff.
-// MDP_FUT_WIDE = 0 | auto | 1; any other name or value is MDP_EINVAL.
-int fut_parse_opts(const char *s, FutWideMode *mode);
+// MDP_FUT_WIDE = 0 | auto | 1; MDP_FUT_SUM_YEARS = 0..12288 (decimal; the cap
+// on the summary path's years per window, 0 = the planner's own choice); any
+// other name or value is MDP_EINVAL.
+int fut_parse_opts(const char *s, FutWideMode *mode, uint32_t *sum_years = nullptr);
 
 // the kernel a survey row of n patches runs under `mode`: *np = 0 for the
 // lane kernels, else the NP of k_future_wide<NP> (patch pairs per lane:
@@ -62,5 +64,46 @@ int fut_wide_plan(const int32_t *last_row, uint32_t n, uint32_t np, double m, do
 // lanes[r*64 + lambda] (the kernel's output) -> words[r*W + k/64] bit k%64,
 // W = ceil(n/64)
 void fut_wide_unpack(const uint32_t *lanes, uint64_t nrep, uint32_t n, uint32_t np, uint64_t *words);
+
+// ---------------------------------------------------------------------------
+// The summary path (mdp_future_summary): hist[t][m] and occ[t][k] accumulate
+// in LDS over windows of years, one launch per window; between windows every
+// replicate rests in a record in device memory (its posterior cell and its
+// occupancy: 8 bytes of mask, or the 64 lane words of k_future_wide).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kFutSumMaxT = 12288;          // as simulate
+constexpr uint64_t kFutSumMaxCells = 1ull << 21; // tfut * (2n+1): 16 MiB of 64-bit counters
+constexpr uint32_t kFutSumTableBytes = 16384;    // LDS of one window's table
+constexpr uint64_t kFutSumOneWindowReps = 1ull << 31;  // replicates per launch: no 32-bit LDS cell can wrap
+constexpr uint64_t kFutSumLaneReps = 1ull << 20;  // replicates per launch when records are kept:
+constexpr uint64_t kFutSumWideReps = 1ull << 16;  //   12 MiB (lane), 16.25 MiB (wide) of records
+
+struct FutSumPlan {
+    uint32_t cells = 0;    // 32-bit LDS cells per year: n+1 of hist, then n (lane kernels) or
+                           //   128*NP in lane order (k_future_wide) of occ
+    uint32_t years = 0;    // years per window
+    uint32_t windows = 0;  // ceil(tfut / years)
+    uint32_t lds = 0;      // dynamic LDS of a launch: fixed tables + years*cells*4
+    uint32_t maxwg = 0;    // grid cap: the workgroups 256 CUs hold at the kernel's VGPR count (every
+                           //   workgroup flushes its window once per launch)
+    uint64_t reps = 0;     // replicates per launch
+};
+
+// np = 0: the lane kernels (16 KB survivor table when n <= 8), else
+// k_future_wide<np> with `wlen` doubles per copy of the image; cap = the
+// MDP_FUT_SUM_YEARS option.  MDP_EUNSUPPORTED for tfut outside 1..12288 or
+// more than 2^21 cells.
+int fut_sum_plan(uint32_t n, uint32_t np, uint32_t wlen, uint32_t tfut, uint32_t cap, FutSumPlan *plan);
+
+// global cell (of 2n+1 per year: hist, then occ in patch order) of LDS cell c
+// of a year in k_future_wide's layout, or -1 for a padded patch
+// (constexpr: host and device)
+constexpr int32_t fut_sum_wide_cell(uint32_t n, uint32_t c)
+{
+    if (c <= n) return (int32_t)c;
+    const uint32_t b = (c - n - 1) >> 6, lam = (c - n - 1) & 63u;
+    const uint32_t k = 2 * (lam + 64 * (b >> 1)) + (b & 1u);
+    return k < n ? (int32_t)(n + 1 + k) : -1;
+}
 
 #endif

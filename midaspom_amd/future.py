@@ -15,6 +15,14 @@ one sum-reduce of the per-year counts to rank 0 (:429-446), and that
 program's per-rank stdout lines (`npstates =` :320, start / end :372, :427,
 send / gather :430-445).  Rank 0 writes the file.
 
+`-H <file>` and `-O <file>` write the ensemble's summaries (Future.summary):
+per future year a line of n+1 cells of hist (replicates with exactly m
+occupied patches) and of n cells of occ (replicates with patch k occupied),
+each cell followed by a tab.  With either flag the run goes through the
+summary path and -o is written from hist[:, 0]; under torchrun the tables
+reach rank 0 in the same sum-reduce as the counts.  Without them nothing
+changes.
+
 Engines are created with MDP_FUT_WIDE=auto: occupancy files of up to 1024
 patches run (beyond 64 on the patch-parallel kernel).
 
@@ -54,6 +62,8 @@ def parse_args(argv):
     ap.add_argument("-r", default=None, help="seed (default $MIDASPOM_SEED or time(NULL))")
     ap.add_argument("-g", type=int, default=None,
                     help="GPUs (single process): replicate ranges, one thread each (default MIDASPOM_GPUS or 1)")
+    ap.add_argument("-H", default=None, help="write hist: per year, replicates by number of occupied patches")
+    ap.add_argument("-O", default=None, help="write occ: per year, replicates with each patch occupied")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl)")
     return ap.parse_args(argv)
 
@@ -84,7 +94,21 @@ def _completions(row, p):
     return np_, out
 
 
-def _simulate_threads(mdp, mdist, row, post, a, seed, ngpu):
+def _run_range(f, a, seed, r0, r1, summary):
+    """[counts, hist, occ] flattened into one uint64 vector (counts alone
+    without -H / -O): what one range adds, and what the ranks reduce."""
+    if not summary:
+        return f.simulate(r1 - r0, a.a, seed=seed, rep0=r0)
+    hist, occ = f.summary(r1 - r0, a.a, seed=seed, rep0=r0)
+    return np.concatenate([hist[:, 0], hist.ravel(), occ.ravel()])
+
+
+def _empty(a, n, summary):
+    t = max(a.a, 0)
+    return np.zeros(t * (2 * n + 2) if summary else t, np.uint64)
+
+
+def _simulate_threads(mdp, mdist, row, post, a, seed, ngpu, summary=False):
     """Single-process -g N: replicate ranges (the MPI partition), one thread
     and engine each, dealt round-robin over the visible GPUs; the ctypes
     calls release the GIL, so the ranges run together."""
@@ -99,7 +123,7 @@ def _simulate_threads(mdp, mdist, row, post, a, seed, ngpu):
         try:
             with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=r % ndev,
                             options=WIDE_AUTO) as f:
-                parts[r] = f.simulate(r1 - r0, a.a, seed=seed, rep0=r0) if r1 > r0 else np.zeros(a.a, np.uint64)
+                parts[r] = _run_range(f, a, seed, r0, r1, summary) if r1 > r0 else _empty(a, row.size, summary)
         except Exception as exc:  # re-raised on the main thread
             errs.append(exc)
 
@@ -171,14 +195,15 @@ def main(argv=None) -> int:
     for vals, pr in comps:
         out("\t" + "".join(f"{v} " for v in vals) + f"; pr={pr:.6f}\n")
     start = int(time.time())
+    summary = a.H is not None or a.O is not None
     if not mpi:
         out("Starting likelihood computation\n")
         ngpu = a.g if a.g is not None else int(os.environ.get("MIDASPOM_GPUS", "1"))
         ngpu = max(1, min(ngpu, a.n)) if a.n > 0 else 1
         if a.a > 0 and a.n > 0:
-            counts = _simulate_threads(mdp, mdist, row, post, a, seed, ngpu)
+            counts = _simulate_threads(mdp, mdist, row, post, a, seed, ngpu, summary)
         else:
-            counts = np.zeros(max(a.a, 0), np.uint64)
+            counts = _empty(a, n, summary)
         out("end likelihood computation\n")
     else:
         import torch
@@ -198,11 +223,11 @@ def main(argv=None) -> int:
         seed = int(s.item())
         out(f"Starting parallel likelihood computation process {rank + 1}/{world}\n", all_ranks=True)
         r0, r1 = mdist.replicate_range(rank, world, a.n)
-        local_counts = np.zeros(max(a.a, 0), np.uint64)
+        local_counts = _empty(a, n, summary)
         if a.a > 0 and r1 > r0:
             with mdp.Future(row, post, m=a.m, d=a.d, KD=a.D, KS=a.S, dS=a.s, device=dev,
                             options=WIDE_AUTO) as f:
-                local_counts = f.simulate(r1 - r0, a.a, seed=seed, rep0=r0)
+                local_counts = _run_range(f, a, seed, r0, r1, summary)
         out(f"end likelihood computation process {rank + 1}/{world}\n", all_ranks=True)
         if not root:
             out(f"Sending data (proc {rank})... ", all_ranks=True)
@@ -217,10 +242,20 @@ def main(argv=None) -> int:
         dist.destroy_process_group()
         if not root:
             return 0
+    tfut = max(a.a, 0)
     out(f"Writing on file {a.o}... ")
     with open(a.o, "w") as fe:
-        fe.write("".join(f"{int(v)}\t" for v in counts))
+        fe.write("".join(f"{int(v)}\t" for v in counts[:tfut]))
     out("done\n")
+    hist = counts[tfut:tfut * (n + 2)].reshape(tfut, n + 1) if summary else None
+    occ = counts[tfut * (n + 2):].reshape(tfut, n) if summary else None
+    for name, tab in ((a.H, hist), (a.O, occ)):
+        if name is None:
+            continue
+        out(f"Writing on file {name}... ")
+        with open(name, "w") as ft:
+            ft.write("".join("".join(f"{int(v)}\t" for v in r) + "\n" for r in tab))
+        out("done\n")
     out(f"Finished. It took  {(int(time.time()) - start) / 60.0:.2f} min\n")
     return 0
 

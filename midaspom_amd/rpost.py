@@ -11,6 +11,11 @@ reference's pipeline expects:
     hypothesis_test     Rscript/hypothesis_test.R:13-46
     extinction_curve    Rscript/plot_extinction.R:13-22
 
+and, for the forecast's summary files (midaspom_future -H / -O, which the
+reference does not write):
+
+    read_future_table, read_future_summary
+
 R semantics kept: read.table / scan split on any whitespace (the trailing
 tab of every row is harmless), which.max returns the first maximum in
 column-major order, seq(l, u, length.out = n) is l + i (u - l) / (n - 1).
@@ -23,7 +28,7 @@ from pathlib import Path
 import numpy as np
 
 __all__ = ["read_table", "scan", "r_seq", "posterior_summary", "dieoff_summary", "loss_summary",
-           "hypothesis_test", "extinction_curve"]
+           "hypothesis_test", "extinction_curve", "read_future_table", "read_future_summary"]
 
 
 def read_table(path) -> np.ndarray:
@@ -145,3 +150,37 @@ def extinction_curve(prext_file, tmax: int, nrep: int) -> np.ndarray:
     if pext.size != tmax:
         raise ValueError(f"{pext.size} years, expected {tmax}")
     return pext / nrep
+
+
+def read_future_table(path, width: int) -> np.ndarray:
+    """A -H or -O file of midaspom_future: one line per future year, `width`
+    unsigned integer cells per line (n + 1 for -H, n for -O), each followed by
+    a tab.  uint64[tfut, width]; the cells never pass through a float."""
+    rows = [ln.split() for ln in Path(path).read_text().splitlines()]
+    if not rows:
+        raise ValueError(f"{path}: empty table")
+    for t, r in enumerate(rows):
+        if len(r) != width:
+            raise ValueError(f"{path}: {len(r)} cells in year {t}, expected {width}")
+        if not all(x.isdigit() for x in r):
+            raise ValueError(f"{path}: year {t} holds a cell that is not an unsigned integer")
+    return np.array([[int(x) for x in r] for r in rows], dtype=np.uint64)
+
+
+def read_future_summary(hist_file, occ_file, n: int, tfut: int):
+    """(hist[tfut, n+1], occ[tfut, n]) from a -H and a -O file of one run, with
+    the shape checks and the identities the tables hold by construction: every
+    year of hist sums to the same replicate count, and sum_m m hist[t][m] =
+    sum_k occ[t][k]."""
+    hist = read_future_table(hist_file, n + 1)
+    occ = read_future_table(occ_file, n)
+    for name, a in ((hist_file, hist), (occ_file, occ)):
+        if a.shape[0] != tfut:
+            raise ValueError(f"{name}: {a.shape[0]} lines, expected {tfut} years")
+    tot = [sum(int(v) for v in r) for r in hist]
+    for t in range(tfut):
+        if tot[t] != tot[0]:
+            raise ValueError(f"{hist_file}: year {t} counts {tot[t]} replicates, year 0 {tot[0]}")
+        if sum(m * int(v) for m, v in enumerate(hist[t])) != sum(int(v) for v in occ[t]):
+            raise ValueError(f"{occ_file}: occupied patches of year {t} differ from {hist_file}")
+    return hist, occ
