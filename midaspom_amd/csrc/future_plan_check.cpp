@@ -3,10 +3,12 @@
 // runtime:
 //   future_plan_check ROW M D KD KS DS "OPTIONS" [TFUT]
 // ROW is one character per patch: '0' empty, '1' occupied, 'm' missing.
-// Prints the kernel the options select and, for k_future_wide, the layout
-// the kernel is given; checks every entry the kernel can read of the distance
-// image against the n x n table's expression, and the state layout against
-// its inverse.  With TFUT, one more line: the summary path's window plan for
+// Prints the kernel the options select; for a lane kernel one line of its
+// plan (the missing count, the occupied mask, FNV-1a digests of the missing
+// bits, of M*K_D and of the source row); for k_future_wide the layout the
+// kernel is given, after checking every entry the kernel can read of the
+// distance image against the n x n table's expression, and the state layout
+// against its inverse.  With TFUT, one more line: the summary path's window plan for
 // that many years under the options.  Exit 0, or mdp_last_error() on stderr and exit 1.
 #include <cmath>
 #include <cstdio>
@@ -71,7 +73,13 @@ int main(int argc, char **argv)
         return 0;
     };
     if (np == 0) {
-        printf("kernel k_future<%u>\n", n <= 8 ? 8u : n <= 16 ? 16u : n <= 32 ? 32u : 64u);
+        FutLanePlan lp;
+        if (fut_lane_plan(row.data(), n, m, d, KD, KS, dS, &lp)) return fail();
+        printf("kernel k_future<%u>\n", lp.nm);
+        printf("lane nmiss %u occ0 %llx miss %016llx MK %016llx src %016llx\n", lp.nmiss, (unsigned long long)lp.occ0,
+               (unsigned long long)fnv(lp.miss.data(), lp.miss.size() * sizeof(uint64_t)),
+               (unsigned long long)fnv(lp.MK.data(), lp.MK.size() * sizeof(double)),
+               (unsigned long long)fnv(lp.src.data(), lp.src.size() * sizeof(double)));
         if (const int rc = summary(0)) return rc == 1 ? fail() : 1;
         return 0;
     }

@@ -26,7 +26,8 @@
 // The ensemble's summaries (mdp_future_summary: per-year histograms of the
 // number of occupied patches, per-patch occupancy counts) come from the
 // variants k_future_tab<NM> and k_future_wide_tab<NP>, one launch per window
-// of years; the kernels of the counts path are not touched by them.
+// of years.  The model's year is stated in the fut_* device functions, which
+// k_future_tab and both wide kernels call; k_future<NM> holds it inline.
 //
 // Random numbers: the reference draws rand()/RAND_MAX from one sequential
 // stream per process (srand(time(NULL)), :345).  Here every draw is
@@ -47,7 +48,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "mdp_internal.h"
@@ -151,6 +154,117 @@ __global__ __launch_bounds__(256) void k_future_table(const double *__restrict__
     for (uint32_t l = 0; l < n; ++l)
         if (l != k && ((surv >> l) & 1u)) s1 += MK[l * kTabN + k];
     T[i] = s1 + src[k];
+}
+
+// ---------------------------------------------------------------------------
+// The replicate model of the lane kernels as functions: fut_draw and
+// fut_rates (also the wide kernels'), fut_init and fut_year<NM>.
+// k_future_tab<NM> calls them; k_future<NM> below still holds the same text
+// inline, because with the calls k_future<64> measured 0.2-0.4 % slower than
+// its parent build.  A change to the model is made in both.
+// ---------------------------------------------------------------------------
+// (e, c) cell of replicate rg from the posterior, with the reference's
+// carry-over (:361-377): idx < lvalid is the cell, lvalid "never found";
+// init_w the replicate's initial-state draw.  overflow() runs when the
+// look-back passes kLookBack replicates.
+template <typename F>
+__device__ __forceinline__ void fut_draw(uint32_t key0, uint32_t key1, uint32_t lvalid, double pscale,
+                                         const double *__restrict__ pcum, uint64_t rg, uint32_t &idx,
+                                         uint32_t &init_w, F overflow)
+{
+    idx = lvalid, init_w = 0;
+    uint64_t q = rg;
+    for (uint32_t step = 0;; ++step) {
+        const u32x4 w = philox(key0, key1, u32x4{(uint32_t)q, (uint32_t)(q >> 32), 0xffffffffu, 0u});
+        if (step == 0) init_w = w.y >> 1;
+        if (lvalid == 0) break;  // empty / all-NaN posterior: never found
+        const double pec = pscale * (double)(w.x >> 1) / kRandMax;
+        idx = upper_bound(pcum, lvalid, pec);
+        if (idx < lvalid || q == 0) break;
+        if (step + 1 >= kLookBack) {  // posterior mass too small for an exact look-back
+            overflow();
+            break;
+        }
+        --q;
+    }
+}
+
+// E = min(1, e/K_D) (simpij :67, :74) and c of posterior cell idx
+__device__ __forceinline__ double fut_rates(uint32_t idx, uint32_t lvalid, uint32_t necstep, double K, double &c)
+{
+    uint32_t ie = 0, ic = 0;
+    if (idx < lvalid) ie = idx / necstep, ic = idx - ie * necstep;
+    const double e = (double)ie * 0.01;
+    c = (double)ic * 0.01;
+    double E = e / K;
+    if (E > 1) E = 1;
+    return E;
+}
+
+// initial state of the lane kernels: missing columns filled from init (first
+// missing = MSB) (:315-321, :378)
+__device__ __forceinline__ uint64_t fut_init(uint64_t occ0, uint32_t nmiss, const uint64_t *__restrict__ missbit,
+                                             uint32_t init_w)
+{
+    const uint32_t init = init_w & ((1u << nmiss) - 1u);
+    uint64_t occ = occ0;
+    for (uint32_t q = 0; q < nmiss; ++q)
+        if ((init >> (nmiss - 1 - q)) & 1u) occ |= missbit[q];
+    return occ;
+}
+
+// one year of replicate rg (simpij :64-110): the occupancy after year t + 1
+template <int NM>
+__device__ __forceinline__ uint64_t fut_year(const FutArgs &a, const double *__restrict__ MK,
+                                             const double *__restrict__ src, const double *Ts, uint64_t rg,
+                                             uint32_t t, uint32_t npairs, uint64_t occ, double E, double c)
+{
+    uint64_t surv = 0;
+    uint32_t colw[NM];
+#pragma unroll
+    for (int m = 0; m < NM / 2; ++m) {
+        if ((uint32_t)m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, (uint32_t)m});
+            const uint32_t k0 = 2 * m, k1 = 2 * m + 1;
+            colw[k0] = w.y >> 1;
+            colw[k1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (:75-82)
+            if (((occ >> k0) & 1u) && u_gt(w.x >> 1, E)) surv |= 1ull << k0;
+            if (((occ >> k1) & 1u) && u_gt(w.z >> 1, E)) surv |= 1ull << k1;
+        } else {
+            colw[2 * m] = colw[2 * m + 1] = 0;
+        }
+    }
+    // colonisation sums, ascending l for every k (:89-95)
+    double s1[NM];
+    if constexpr (NM == kTabN) {
+        const double2 *row = reinterpret_cast<const double2 *>(Ts + (uint32_t)surv * kTabN);
+#pragma unroll
+        for (int k = 0; k < NM; k += 2) {
+            const double2 v = row[k / 2];
+            s1[k] = v.x, s1[k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NM; ++k) s1[k] = 0.0;
+        for (uint32_t l = 0; l < a.n; ++l) {
+            const bool on = (surv >> l) & 1u;
+#pragma unroll
+            for (int k = 0; k < NM; ++k) s1[k] += on ? MK[l * NM + k] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < NM; ++k) s1[k] += src[k];
+    }
+    uint64_t nw = surv;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+        if ((uint32_t)k < a.n && !((surv >> k) & 1u)) {
+            double pc = c * s1[k];  // :95-97
+            if (pc > 1) pc = 1;
+            if (u_lt(colw[k], pc)) nw |= 1ull << k;  // :98-101
+        }
+    }
+    return nw;
 }
 
 template <int NM>
@@ -303,6 +417,103 @@ struct FutWideArgs {
 
 constexpr int kWideWaves = kFutBlock / 64;  // replicates in flight per workgroup
 
+// bit 2j+p set where patch 2*(lane + 64*j) + p exists
+template <int NP>
+__device__ __forceinline__ uint32_t fut_wide_live(uint32_t n, uint32_t lane)
+{
+    uint32_t live = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t k0 = 2 * (lane + 64u * j);
+        if (k0 < n) live |= 1u << (2 * j);
+        if (k0 + 1 < n) live |= 2u << (2 * j);
+    }
+    return live;
+}
+
+// initial state of a wave's replicate: missing patches filled from init
+// (first missing = MSB) (:315-321, :378)
+__device__ __forceinline__ uint32_t fut_wide_init(uint32_t occ_init, uint32_t nmiss, const uint32_t *__restrict__ miss,
+                                                  uint32_t init_w, uint32_t lane)
+{
+    const uint32_t init = init_w & ((1u << nmiss) - 1u);
+    uint32_t occ = occ_init;
+    for (uint32_t q = 0; q < nmiss; ++q) {
+        const uint32_t mq = miss[q];
+        if (((init >> (nmiss - 1 - q)) & 1u) && lane == (mq >> 8)) occ |= 1u << (mq & 0xffu);
+    }
+    return occ;
+}
+
+// one year of the wave's replicate rg: the lane's occupancy word after year t + 1
+template <int NP>
+__device__ __forceinline__ uint32_t fut_wide_year(const FutWideArgs &a, const double2 *G2,
+                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
+                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
+                                                  double E, double c)
+{
+    uint64_t bal[NP][2];
+    uint32_t colw[2 * NP];
+    uint32_t surv = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t m = lane + 64u * j;
+        bool s0 = false, s1 = false;
+        colw[2 * j] = colw[2 * j + 1] = 0;
+        if (m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
+            colw[2 * j] = w.y >> 1;
+            colw[2 * j + 1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (:75-82)
+            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
+            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
+        }
+        bal[j][0] = __ballot(s0);
+        bal[j][1] = __ballot(s1);
+        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
+    }
+    // colonisation sums, ascending l for every k (:89-95): patch
+    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
+    double s[2 * NP];
+#pragma unroll
+    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        uint64_t both = bal[j][0] | bal[j][1];
+        while (both) {
+            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
+            both &= both - 1;
+#pragma unroll
+            for (uint32_t p = 0; p < 2; ++p) {
+                if (!((bal[j][p] >> lam) & 1u)) continue;
+                const uint32_t l = 2 * (lam + 64u * j) + p;
+                const double2 *row = G2 + fut_wide_slot0(a.n, a.len, l) + lane;
+#pragma unroll
+                for (int jj = 0; jj < NP; ++jj) {
+                    const double2 v = row[64 * jj];
+                    s[2 * jj] += v.x;
+                    s[2 * jj + 1] += v.y;
+                }
+            }
+        }
+    }
+    uint32_t nw = surv;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint32_t bit = 1u << (2 * j + p);
+            if ((live & bit) && !(surv & bit)) {
+                double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
+                if (pc > 1) pc = 1;
+                if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
+            }
+        }
+    }
+    return nw;
+}
+
 template <int NP>
 __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const double *__restrict__ image,
                                                            const double *__restrict__ src,
@@ -323,110 +534,19 @@ __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const 
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t npairs = (a.n + 1) >> 1;
     const uint32_t occ_init = occ0[lane];
-    // bit 2j+p set where patch 2*(lane + 64*j) + p exists
-    uint32_t live = 0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const uint32_t k0 = 2 * (lane + 64u * j);
-        if (k0 < a.n) live |= 1u << (2 * j);
-        if (k0 + 1 < a.n) live |= 2u << (2 * j);
-    }
+    const uint32_t live = fut_wide_live<NP>(a.n, lane);
     for (uint64_t r = (uint64_t)blockIdx.x * kWideWaves + wave; r < a.nrep; r += (uint64_t)gridDim.x * kWideWaves) {
         const uint64_t rg = a.rep0 + r;  // wave-uniform from here to the state
-        // ---- (e, c) from the posterior, with the reference's carry-over (:361-377)
-        uint32_t idx = a.lvalid, init_w = 0;
-        {
-            uint64_t q = rg;
-            for (uint32_t step = 0;; ++step) {
-                const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)q, (uint32_t)(q >> 32), 0xffffffffu, 0u});
-                if (step == 0) init_w = w.y >> 1;
-                if (a.lvalid == 0) break;  // empty / all-NaN posterior: never found
-                const double pec = a.pscale * (double)(w.x >> 1) / kRandMax;
-                idx = upper_bound(pcum, a.lvalid, pec);
-                if (idx < a.lvalid || q == 0) break;
-                if (step + 1 >= kLookBack) {  // posterior mass too small for an exact look-back
-                    if (lane == 0) atomicOr(err, 1u);
-                    break;
-                }
-                --q;
-            }
-        }
-        uint32_t ie = 0, ic = 0;
-        if (idx < a.lvalid) ie = idx / a.necstep, ic = idx - ie * a.necstep;
-        const double e = (double)ie * 0.01, c = (double)ic * 0.01;
-        double E = e / a.K;  // simpij :67, :74
-        if (E > 1) E = 1;
-        // ---- initial state: missing patches filled from init (first missing = MSB) (:315-321, :378)
-        const uint32_t init = init_w & ((1u << a.nmiss) - 1u);
-        uint32_t occ = occ_init;
-        for (uint32_t q = 0; q < a.nmiss; ++q) {
-            const uint32_t mq = miss[q];
-            if (((init >> (a.nmiss - 1 - q)) & 1u) && lane == (mq >> 8)) occ |= 1u << (mq & 0xffu);
-        }
+        uint32_t idx, init_w;
+        fut_draw(a.key0, a.key1, a.lvalid, a.pscale, pcum, rg, idx, init_w, [&]() {
+            if (lane == 0) atomicOr(err, 1u);
+        });
+        double c;
+        const double E = fut_rates(idx, a.lvalid, a.necstep, a.K, c);
+        uint32_t occ = fut_wide_init(occ_init, a.nmiss, miss, init_w, lane);
         // ---- tfut years (:381-385)
         for (uint32_t t = 0; t < a.tfut; ++t) {
-            uint64_t bal[NP][2];
-            uint32_t colw[2 * NP];
-            uint32_t surv = 0;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                const uint32_t m = lane + 64u * j;
-                bool s0 = false, s1 = false;
-                colw[2 * j] = colw[2 * j + 1] = 0;
-                if (m < npairs) {
-                    const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
-                    colw[2 * j] = w.y >> 1;
-                    colw[2 * j + 1] = w.w >> 1;
-                    // extinction: an occupied patch survives if u > E (:75-82)
-                    s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
-                    s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
-                }
-                bal[j][0] = __ballot(s0);
-                bal[j][1] = __ballot(s1);
-                surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
-            }
-            // colonisation sums, ascending l for every k (:89-95): patch
-            // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
-            double s[2 * NP];
-#pragma unroll
-            for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                uint64_t both = bal[j][0] | bal[j][1];
-                while (both) {
-                    const uint32_t lam = (uint32_t)__builtin_ctzll(both);
-                    both &= both - 1;
-#pragma unroll
-                    for (uint32_t p = 0; p < 2; ++p) {
-                        if (!((bal[j][p] >> lam) & 1u)) continue;
-                        const uint32_t l = 2 * (lam + 64u * j) + p;
-                        const uint32_t base = a.n - 1 - l;
-                        const uint32_t slot0 = (base & 1u) ? (a.len + base - 1) >> 1 : base >> 1;
-                        const double2 *row = G2 + slot0 + lane;
-#pragma unroll
-                        for (int jj = 0; jj < NP; ++jj) {
-                            const double2 v = row[64 * jj];
-                            s[2 * jj] += v.x;
-                            s[2 * jj + 1] += v.y;
-                        }
-                    }
-                }
-            }
-            uint32_t nw = surv;
-#pragma unroll
-            for (int j = 0; j < NP; ++j) {
-                const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const uint32_t bit = 1u << (2 * j + p);
-                    if ((live & bit) && !(surv & bit)) {
-                        double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
-                        if (pc > 1) pc = 1;
-                        if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
-                    }
-                }
-            }
-            occ = nw;
+            occ = fut_wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E, c);
             if (__ballot(occ != 0) == 0) {
                 if (!a.ks0) {
                     if (lane == 0) atomicAdd(&cnt[t], 1u);
@@ -448,9 +568,8 @@ __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const 
 // The summary path (mdp_future_summary): hist[t][m], the replicates with
 // exactly m occupied patches after year t + 1, and occ[t][k], those with
 // patch k occupied.  k_future_tab<NM> and k_future_wide_tab<NP> run the same
-// years on the same draws as k_future<NM> and k_future_wide<NP> (the model is
-// restated in the fut_* functions below, so that the kernels above stay the
-// code they were) over one window [t0, t1) of years per launch, and count
+// years on the same draws as k_future<NM> and k_future_wide<NP> (the fut_*
+// functions above) over one window [t0, t1) of years per launch, and count
 // into a window table in LDS: 32-bit integer atomics and ballots, exact in
 // any order.  Between launches a replicate rests in a record (its posterior
 // cell and occupancy); the draws are addressed, so resuming is exact.  Every
@@ -462,110 +581,6 @@ struct FutSumWin {
     uint32_t cells;    // LDS cells per year (FutSumPlan)
     uint32_t last;     // t1 == tfut: no record is written
 };
-
-// (e, c) cell of replicate rg from the posterior, with the reference's
-// carry-over (:361-377): idx < lvalid is the cell, lvalid "never found";
-// init_w the replicate's initial-state draw.  overflow() runs when the
-// look-back passes kLookBack replicates.
-template <typename F>
-__device__ __forceinline__ void fut_draw(uint32_t key0, uint32_t key1, uint32_t lvalid, double pscale,
-                                         const double *__restrict__ pcum, uint64_t rg, uint32_t &idx,
-                                         uint32_t &init_w, F overflow)
-{
-    idx = lvalid, init_w = 0;
-    uint64_t q = rg;
-    for (uint32_t step = 0;; ++step) {
-        const u32x4 w = philox(key0, key1, u32x4{(uint32_t)q, (uint32_t)(q >> 32), 0xffffffffu, 0u});
-        if (step == 0) init_w = w.y >> 1;
-        if (lvalid == 0) break;  // empty / all-NaN posterior: never found
-        const double pec = pscale * (double)(w.x >> 1) / kRandMax;
-        idx = upper_bound(pcum, lvalid, pec);
-        if (idx < lvalid || q == 0) break;
-        if (step + 1 >= kLookBack) {  // posterior mass too small for an exact look-back
-            overflow();
-            break;
-        }
-        --q;
-    }
-}
-
-// E = min(1, e/K_D) (simpij :67, :74) and c of posterior cell idx
-__device__ __forceinline__ double fut_rates(uint32_t idx, uint32_t lvalid, uint32_t necstep, double K, double &c)
-{
-    uint32_t ie = 0, ic = 0;
-    if (idx < lvalid) ie = idx / necstep, ic = idx - ie * necstep;
-    const double e = (double)ie * 0.01;
-    c = (double)ic * 0.01;
-    double E = e / K;
-    if (E > 1) E = 1;
-    return E;
-}
-
-// initial state of the lane kernels: missing columns filled from init (first
-// missing = MSB) (:315-321, :378)
-__device__ __forceinline__ uint64_t fut_init(uint64_t occ0, uint32_t nmiss, const uint64_t *__restrict__ missbit,
-                                             uint32_t init_w)
-{
-    const uint32_t init = init_w & ((1u << nmiss) - 1u);
-    uint64_t occ = occ0;
-    for (uint32_t q = 0; q < nmiss; ++q)
-        if ((init >> (nmiss - 1 - q)) & 1u) occ |= missbit[q];
-    return occ;
-}
-
-// one year of replicate rg (simpij :64-110): the occupancy after year t + 1
-template <int NM>
-__device__ __forceinline__ uint64_t fut_year(const FutArgs &a, const double *__restrict__ MK,
-                                             const double *__restrict__ src, const double *Ts, uint64_t rg,
-                                             uint32_t t, uint32_t npairs, uint64_t occ, double E, double c)
-{
-    uint64_t surv = 0;
-    uint32_t colw[NM];
-#pragma unroll
-    for (int m = 0; m < NM / 2; ++m) {
-        if ((uint32_t)m < npairs) {
-            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, (uint32_t)m});
-            const uint32_t k0 = 2 * m, k1 = 2 * m + 1;
-            colw[k0] = w.y >> 1;
-            colw[k1] = w.w >> 1;
-            // extinction: an occupied patch survives if u > E (:75-82)
-            if (((occ >> k0) & 1u) && u_gt(w.x >> 1, E)) surv |= 1ull << k0;
-            if (((occ >> k1) & 1u) && u_gt(w.z >> 1, E)) surv |= 1ull << k1;
-        } else {
-            colw[2 * m] = colw[2 * m + 1] = 0;
-        }
-    }
-    // colonisation sums, ascending l for every k (:89-95)
-    double s1[NM];
-    if constexpr (NM == kTabN) {
-        const double2 *row = reinterpret_cast<const double2 *>(Ts + (uint32_t)surv * kTabN);
-#pragma unroll
-        for (int k = 0; k < NM; k += 2) {
-            const double2 v = row[k / 2];
-            s1[k] = v.x, s1[k + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < NM; ++k) s1[k] = 0.0;
-        for (uint32_t l = 0; l < a.n; ++l) {
-            const bool on = (surv >> l) & 1u;
-#pragma unroll
-            for (int k = 0; k < NM; ++k) s1[k] += on ? MK[l * NM + k] : 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < NM; ++k) s1[k] += src[k];
-    }
-    uint64_t nw = surv;
-#pragma unroll
-    for (int k = 0; k < NM; ++k) {
-        if ((uint32_t)k < a.n && !((surv >> k) & 1u)) {
-            double pc = c * s1[k];  // :95-97
-            if (pc > 1) pc = 1;
-            if (u_lt(colw[k], pc)) nw |= 1ull << k;  // :98-101
-        }
-    }
-    return nw;
-}
 
 template <int NM>
 __global__ __launch_bounds__(kFutBlock) void k_future_tab(FutArgs a, FutSumWin w, const double *__restrict__ MK,
@@ -642,105 +657,6 @@ __global__ __launch_bounds__(kFutBlock) void k_future_tab(FutArgs a, FutSumWin w
         const uint32_t v = win[i];
         if (v) atomicAdd(&tab[(size_t)w.t0 * w.cells + i], (unsigned long long)v);
     }
-}
-
-// bit 2j+p set where patch 2*(lane + 64*j) + p exists
-template <int NP>
-__device__ __forceinline__ uint32_t fut_wide_live(uint32_t n, uint32_t lane)
-{
-    uint32_t live = 0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const uint32_t k0 = 2 * (lane + 64u * j);
-        if (k0 < n) live |= 1u << (2 * j);
-        if (k0 + 1 < n) live |= 2u << (2 * j);
-    }
-    return live;
-}
-
-// initial state of a wave's replicate: missing patches filled from init
-// (first missing = MSB) (:315-321, :378)
-__device__ __forceinline__ uint32_t fut_wide_init(uint32_t occ_init, uint32_t nmiss, const uint32_t *__restrict__ miss,
-                                                  uint32_t init_w, uint32_t lane)
-{
-    const uint32_t init = init_w & ((1u << nmiss) - 1u);
-    uint32_t occ = occ_init;
-    for (uint32_t q = 0; q < nmiss; ++q) {
-        const uint32_t mq = miss[q];
-        if (((init >> (nmiss - 1 - q)) & 1u) && lane == (mq >> 8)) occ |= 1u << (mq & 0xffu);
-    }
-    return occ;
-}
-
-// one year of the wave's replicate rg: the lane's occupancy word after year t + 1
-template <int NP>
-__device__ __forceinline__ uint32_t fut_wide_year(const FutWideArgs &a, const double2 *G2,
-                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
-                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
-                                                  double E, double c)
-{
-    uint64_t bal[NP][2];
-    uint32_t colw[2 * NP];
-    uint32_t surv = 0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const uint32_t m = lane + 64u * j;
-        bool s0 = false, s1 = false;
-        colw[2 * j] = colw[2 * j + 1] = 0;
-        if (m < npairs) {
-            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
-            colw[2 * j] = w.y >> 1;
-            colw[2 * j + 1] = w.w >> 1;
-            // extinction: an occupied patch survives if u > E (:75-82)
-            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
-            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
-        }
-        bal[j][0] = __ballot(s0);
-        bal[j][1] = __ballot(s1);
-        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
-    }
-    // colonisation sums, ascending l for every k (:89-95): patch
-    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
-    double s[2 * NP];
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        uint64_t both = bal[j][0] | bal[j][1];
-        while (both) {
-            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
-            both &= both - 1;
-#pragma unroll
-            for (uint32_t p = 0; p < 2; ++p) {
-                if (!((bal[j][p] >> lam) & 1u)) continue;
-                const uint32_t l = 2 * (lam + 64u * j) + p;
-                const uint32_t base = a.n - 1 - l;
-                const uint32_t slot0 = (base & 1u) ? (a.len + base - 1) >> 1 : base >> 1;
-                const double2 *row = G2 + slot0 + lane;
-#pragma unroll
-                for (int jj = 0; jj < NP; ++jj) {
-                    const double2 v = row[64 * jj];
-                    s[2 * jj] += v.x;
-                    s[2 * jj + 1] += v.y;
-                }
-            }
-        }
-    }
-    uint32_t nw = surv;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t bit = 1u << (2 * j + p);
-            if ((live & bit) && !(surv & bit)) {
-                double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
-                if (pc > 1) pc = 1;
-                if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
-            }
-        }
-    }
-    return nw;
 }
 
 template <int NP>
@@ -844,7 +760,6 @@ int dev_up(T **p, const std::vector<T> &h)
 }
 
 }  // namespace
-
 struct mdp_future {
     int device = 0;
     uint32_t n = 0, nm = 0, nmiss = 0, necstep = 0, lvalid = 0;
@@ -871,48 +786,96 @@ struct mdp_future {
     size_t tab_cap = 0;
     void *drec_occ = nullptr;
     uint32_t *drec_idx = nullptr;
-    uint64_t rec_cap = 0;
+    size_t rec_occ_cap = 0, rec_idx_cap = 0;
 };
 
 namespace {
 
+// grow-only device buffer of `need` elements of `elem` bytes; after a failed
+// hipMalloc the pointer is null and the capacity 0
+template <typename T>
+int fut_grow(T *&p, size_t &cap, size_t need, size_t elem)
+{
+    if (need <= cap) return MDP_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    FUT_TRY(hipMalloc((void **)&p, need * elem));
+    cap = need;
+    return MDP_OK;
+}
+
+// the one switch over the lane kernels' padded patch count: fn(integral_constant<int, NM>)
+template <typename F>
+int fut_for_nm(uint32_t nm, F &&fn)
+{
+    switch (nm) {
+    case 8: return fn(std::integral_constant<int, 8>());
+    case 16: return fn(std::integral_constant<int, 16>());
+    case 32: return fn(std::integral_constant<int, 32>());
+    case 64: return fn(std::integral_constant<int, 64>());
+    default: return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", nm);
+    }
+}
+
+// and over the patch pairs per lane of k_future_wide
+template <typename F>
+int fut_for_np(uint32_t np, F &&fn)
+{
+    switch (np) {
+    case 1: return fn(std::integral_constant<int, 1>());
+    case 2: return fn(std::integral_constant<int, 2>());
+    case 4: return fn(std::integral_constant<int, 4>());
+    case 8: return fn(std::integral_constant<int, 8>());
+    default: return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", np);
+    }
+}
+
+// the refusal of a look-back overflow, from the flag a finished launch left;
+// device_path: the text of mdp_future_check
+int fut_lookback(uint32_t err, bool device_path)
+{
+    if (!err) return MDP_OK;
+    return mdp_set_error(MDP_EUNSUPPORTED,
+                         "a posterior draw needed more than %u look-back replicates (posterior mass far "
+                         "below the (necstep-1)^2 scale)%s",
+                         kLookBack, device_path ? ": the device counts are not valid" : "");
+}
+
 // replicates per workgroup: one per lane, or one per wave (k_future_wide)
+uint64_t fut_per_wg(const mdp_future *f) { return f->np ? kWideWaves : kFutBlock; }
+
 int fut_grid(const mdp_future *f, uint64_t nrep)
 {
-    const uint64_t per = f->np ? kWideWaves : kFutBlock;
-    const uint64_t wg = (nrep + per - 1) / per;
+    const uint64_t wg = (nrep + fut_per_wg(f) - 1) / fut_per_wg(f);
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(wg, kFutMaxWG));
 }
 
 int fut_reserve(mdp_future *f, int nwg, uint32_t tfut)
 {
-    const size_t need = (size_t)nwg * tfut;
-    if (need > f->partial_cap) {
-        if (f->dpartial) (void)hipFree(f->dpartial);
-        f->dpartial = nullptr;
-        f->partial_cap = 0;
-        FUT_TRY(hipMalloc((void **)&f->dpartial, need * sizeof(uint32_t)));
-        f->partial_cap = need;
-    }
-    if (tfut > f->counts_cap) {
-        if (f->dcounts) (void)hipFree(f->dcounts);
-        f->dcounts = nullptr;
-        f->counts_cap = 0;
-        FUT_TRY(hipMalloc((void **)&f->dcounts, tfut * sizeof(unsigned long long)));
-        f->counts_cap = tfut;
-    }
-    return MDP_OK;
+    if (int rc = fut_grow(f->dpartial, f->partial_cap, (size_t)nwg * tfut, sizeof(uint32_t))) return rc;
+    return fut_grow(f->dcounts, f->counts_cap, tfut, sizeof(unsigned long long));
 }
 
-size_t fut_wide_lds(const mdp_future *f, uint32_t tfut)
+FutArgs fut_args(const mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut)
 {
-    return (size_t)2 * f->wlen * sizeof(double) + (size_t)tfut * sizeof(uint32_t);
+    FutArgs a{};
+    a.n = f->n;
+    a.nmiss = f->nmiss;
+    a.tfut = tfut;
+    a.lvalid = f->lvalid;
+    a.occ0 = f->occ0;
+    a.rep0 = rep0;
+    a.nrep = nrep;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.necstep = f->necstep;
+    a.pscale = f->pscale;
+    a.K = f->K;
+    return a;
 }
 
-// k_future_wide<np> over replicates [rep0, rep0 + nrep); d_states: the final
-// lane words of every replicate ([nrep][64]) or null
-int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut, hipStream_t st,
-                    uint32_t *d_states, uint32_t *derr)
+FutWideArgs fut_wide_args(const mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut)
 {
     FutWideArgs a{};
     a.n = f->n;
@@ -928,22 +891,28 @@ int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, 
     a.ks0 = f->ks0;
     a.pscale = f->pscale;
     a.K = f->K;
+    return a;
+}
+
+size_t fut_wide_lds(const mdp_future *f, uint32_t tfut)
+{
+    return (size_t)2 * f->wlen * sizeof(double) + (size_t)tfut * sizeof(uint32_t);
+}
+
+// k_future_wide<np> over replicates [rep0, rep0 + nrep); d_states: the final
+// lane words of every replicate ([nrep][64]) or null
+int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut, hipStream_t st,
+                    uint32_t *d_states, uint32_t *derr)
+{
+    const FutWideArgs a = fut_wide_args(f, seed, rep0, nrep, tfut);
     const int nwg = fut_grid(f, nrep);
     const size_t lds = fut_wide_lds(f, tfut);
-    switch (f->np) {
-#define FUT_WCASE(NPV)                                                                                  \
-    case NPV:                                                                                            \
-        hipLaunchKernelGGL(k_future_wide<NPV>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage,      \
-                           f->dsrc, f->dpcum, f->docc0, f->dwmiss, f->dpartial, d_states, derr);        \
-        break;
-        FUT_WCASE(1)
-        FUT_WCASE(2)
-        FUT_WCASE(4)
-        FUT_WCASE(8)
-#undef FUT_WCASE
-    default:
-        return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", f->np);
-    }
+    if (int rc = fut_for_np(f->np, [&](auto NP) {
+            hipLaunchKernelGGL(k_future_wide<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage,
+                               f->dsrc, f->dpcum, f->docc0, f->dwmiss, f->dpartial, d_states, derr);
+            return MDP_OK;
+        }))
+        return rc;
     FUT_TRY(hipGetLastError());
     return MDP_OK;
 }
@@ -952,46 +921,20 @@ int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, 
 int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
                unsigned long long *d_counts, hipStream_t st, bool sum, uint32_t *derr)
 {
-    if (f->np) {
-        int rc = fut_launch_wide(f, seed, rep0, nrep, tfut, st, nullptr, derr);
-        if (rc) return rc;
-        if (sum) {
-            hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial, (uint32_t)fut_grid(f, nrep),
-                               tfut, d_counts);
-            FUT_TRY(hipGetLastError());
-        }
-        return MDP_OK;
-    }
-    FutArgs a{};
-    a.n = f->n;
-    a.nmiss = f->nmiss;
-    a.tfut = tfut;
-    a.lvalid = f->lvalid;
-    a.occ0 = f->occ0;
-    a.rep0 = rep0;
-    a.nrep = nrep;
-    a.key0 = (uint32_t)seed;
-    a.key1 = (uint32_t)(seed >> 32);
-    a.necstep = f->necstep;
-    a.pscale = f->pscale;
-    a.K = f->K;
     const int nwg = fut_grid(f, nrep);
-    const size_t lds = (size_t)tfut * sizeof(uint32_t) + (f->nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0);
-    switch (f->nm) {
-#define FUT_CASE(NMV)                                                                                   \
-    case NMV:                                                                                            \
-        hipLaunchKernelGGL(k_future<NMV>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dMK, f->dsrc,    \
-                           f->dpcum, f->dmiss, f->dT, f->dpartial, derr);                               \
-        break;
-        FUT_CASE(8)
-        FUT_CASE(16)
-        FUT_CASE(32)
-        FUT_CASE(64)
-#undef FUT_CASE
-    default:
-        return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", f->nm);
+    if (f->np) {
+        if (int rc = fut_launch_wide(f, seed, rep0, nrep, tfut, st, nullptr, derr)) return rc;
+    } else {
+        const FutArgs a = fut_args(f, seed, rep0, nrep, tfut);
+        const size_t lds = (size_t)tfut * sizeof(uint32_t) + (f->nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0);
+        if (int rc = fut_for_nm(f->nm, [&](auto NM) {
+                hipLaunchKernelGGL(k_future<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dMK,
+                                   f->dsrc, f->dpcum, f->dmiss, f->dT, f->dpartial, derr);
+                return MDP_OK;
+            }))
+            return rc;
+        FUT_TRY(hipGetLastError());
     }
-    FUT_TRY(hipGetLastError());
     if (sum) {
         hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial, (uint32_t)nwg, tfut, d_counts);
         FUT_TRY(hipGetLastError());
@@ -1008,7 +951,6 @@ int fut_check_args(mdp_future *f, uint64_t nrep, uint32_t tfut)
     return MDP_OK;
 }
 
-
 // the whole summary of replicates [rep0, rep0 + nrep) into f->dtab on st:
 // the table zeroed, then for every range of p.reps replicates one launch per
 // window of years
@@ -1017,7 +959,8 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
 {
     const size_t ncell = (size_t)tfut * (2 * f->n + 1);
     FUT_TRY(hipMemsetAsync(f->dtab, 0, ncell * sizeof(unsigned long long), st));
-    const uint64_t per = f->np ? kWideWaves : kFutBlock;
+    const uint64_t per = fut_per_wg(f);
+    const size_t lds = (size_t)p.lds;
     for (uint64_t done = 0; done < nrep; done += p.reps) {
         const uint64_t cnt = std::min<uint64_t>(p.reps, nrep - done);
         const int nwg = (int)std::min<uint64_t>((cnt + per - 1) / per, p.maxwg);
@@ -1027,66 +970,25 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
             w.t1 = std::min(tfut, t0 + p.years);
             w.cells = p.cells;
             w.last = w.t1 == tfut;
-            const size_t lds = (size_t)p.lds;
+            int rc;
             if (f->np) {
-                FutWideArgs a{};
-                a.n = f->n;
-                a.nmiss = f->nmiss;
-                a.tfut = tfut;
-                a.lvalid = f->lvalid;
-                a.rep0 = rep0 + done;
-                a.nrep = cnt;
-                a.key0 = (uint32_t)seed;
-                a.key1 = (uint32_t)(seed >> 32);
-                a.necstep = f->necstep;
-                a.len = f->wlen;
-                a.ks0 = f->ks0;
-                a.pscale = f->pscale;
-                a.K = f->K;
-                switch (f->np) {
-#define FUT_WCASE(NPV)                                                                                     \
-    case NPV:                                                                                               \
-        hipLaunchKernelGGL(k_future_wide_tab<NPV>, dim3(nwg), dim3(kFutBlock), lds, st, a, w, f->dimage,  \
-                           f->dsrc, f->dpcum, f->docc0, f->dwmiss, (uint32_t *)f->drec_occ, f->drec_idx,   \
-                           f->dtab, derr);                                                                  \
-        break;
-                    FUT_WCASE(1)
-                    FUT_WCASE(2)
-                    FUT_WCASE(4)
-                    FUT_WCASE(8)
-#undef FUT_WCASE
-                default:
-                    return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", f->np);
-                }
+                const FutWideArgs a = fut_wide_args(f, seed, rep0 + done, cnt, tfut);
+                rc = fut_for_np(f->np, [&](auto NP) {
+                    hipLaunchKernelGGL(k_future_wide_tab<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a,
+                                       w, f->dimage, f->dsrc, f->dpcum, f->docc0, f->dwmiss,
+                                       (uint32_t *)f->drec_occ, f->drec_idx, f->dtab, derr);
+                    return MDP_OK;
+                });
             } else {
-                FutArgs a{};
-                a.n = f->n;
-                a.nmiss = f->nmiss;
-                a.tfut = tfut;
-                a.lvalid = f->lvalid;
-                a.occ0 = f->occ0;
-                a.rep0 = rep0 + done;
-                a.nrep = cnt;
-                a.key0 = (uint32_t)seed;
-                a.key1 = (uint32_t)(seed >> 32);
-                a.necstep = f->necstep;
-                a.pscale = f->pscale;
-                a.K = f->K;
-                switch (f->nm) {
-#define FUT_CASE(NMV)                                                                                      \
-    case NMV:                                                                                               \
-        hipLaunchKernelGGL(k_future_tab<NMV>, dim3(nwg), dim3(kFutBlock), lds, st, a, w, f->dMK, f->dsrc, \
-                           f->dpcum, f->dmiss, f->dT, (uint64_t *)f->drec_occ, f->drec_idx, f->dtab, derr); \
-        break;
-                    FUT_CASE(8)
-                    FUT_CASE(16)
-                    FUT_CASE(32)
-                    FUT_CASE(64)
-#undef FUT_CASE
-                default:
-                    return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", f->nm);
-                }
+                const FutArgs a = fut_args(f, seed, rep0 + done, cnt, tfut);
+                rc = fut_for_nm(f->nm, [&](auto NM) {
+                    hipLaunchKernelGGL(k_future_tab<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, w,
+                                       f->dMK, f->dsrc, f->dpcum, f->dmiss, f->dT, (uint64_t *)f->drec_occ,
+                                       f->drec_idx, f->dtab, derr);
+                    return MDP_OK;
+                });
             }
+            if (rc) return rc;
             FUT_TRY(hipGetLastError());
         }
     }
@@ -1101,25 +1003,76 @@ int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan 
     if (nrep > (1ull << 62)) return mdp_set_error(MDP_EINVAL, "replicate count too large");
     if (int rc = fut_sum_plan(f->n, f->np, f->wlen, tfut, f->sum_years, p)) return rc;
     FUT_TRY(hipSetDevice(f->device));
-    const size_t ncell = (size_t)tfut * (2 * f->n + 1);
-    if (ncell > f->tab_cap) {
-        if (f->dtab) (void)hipFree(f->dtab);
-        f->dtab = nullptr;
-        f->tab_cap = 0;
-        FUT_TRY(hipMalloc((void **)&f->dtab, ncell * sizeof(unsigned long long)));
-        f->tab_cap = ncell;
+    if (int rc = fut_grow(f->dtab, f->tab_cap, (size_t)tfut * (2 * f->n + 1), sizeof(unsigned long long))) return rc;
+    const size_t recs = p->windows > 1 ? (size_t)std::min<uint64_t>(nrep, p->reps) : 0;
+    if (int rc = fut_grow(f->drec_occ, f->rec_occ_cap, recs, f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t)))
+        return rc;
+    return fut_grow(f->drec_idx, f->rec_idx_cap, recs, sizeof(uint32_t));
+}
+
+// the mean time in ms of `reps` runs of launch() on f->stream, after one
+// warm-up run
+template <typename F>
+int fut_time(mdp_future *f, int reps, double *ms, F launch)
+{
+    int rc;
+    if ((rc = launch())) return rc;
+    FUT_TRY(hipEventRecord(f->ev0, f->stream));
+    for (int i = 0; i < reps; ++i)
+        if ((rc = launch())) return rc;
+    FUT_TRY(hipEventRecord(f->ev1, f->stream));
+    FUT_TRY(hipEventSynchronize(f->ev1));
+    float t = 0;
+    FUT_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
+    *ms = (double)t / reps;
+    return MDP_OK;
+}
+
+// tables, colonisation table, look-back flags, stream and events of an engine
+// whose host fields are set
+int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp, const FutPostPlan &pp)
+{
+    const int device = f->device;
+    if (hipSetDevice(device) != hipSuccess) return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
+    int rc;
+    if ((rc = dev_up(&f->dpcum, pp.pcum))) return rc;
+    if (f->np) {
+        if ((rc = dev_up(&f->dimage, wp.image)) || (rc = dev_up(&f->dsrc, wp.src)) ||
+            (rc = dev_up(&f->docc0, wp.occ0)) || (rc = dev_up(&f->dwmiss, wp.miss)))
+            return rc;
+        // the image and kFutMaxT year counters pass 64 KB of dynamic LDS; the
+        // summary kernel: the image and one window's table
+        const size_t lds[2] = {fut_wide_lds(f, kFutMaxT), (size_t)2 * f->wlen * sizeof(double) + kFutSumTableBytes};
+        const void *fn[2] = {nullptr, nullptr};
+        if ((rc = fut_for_np(f->np, [&](auto NP) {
+                 fn[0] = (const void *)k_future_wide<decltype(NP)::value>;
+                 fn[1] = (const void *)k_future_wide_tab<decltype(NP)::value>;
+                 return MDP_OK;
+             })))
+            return rc;
+        for (int i = 0; i < 2; ++i)
+            if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds[i]) != hipSuccess)
+                return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d%s", f->kname, lds[i], device,
+                                     i ? " (summary)" : "");
+    } else {
+        if ((rc = dev_up(&f->dMK, lp.MK)) || (rc = dev_up(&f->dsrc, lp.src)) || (rc = dev_up(&f->dmiss, lp.miss)))
+            return rc;
+        if (f->nm == kTabN) {
+            if (hipMalloc((void **)&f->dT, sizeof(double) * (kTabN << kTabN)) != hipSuccess)
+                return mdp_set_error(MDP_EHIP, "device allocation failed on device %d", device);
+            hipLaunchKernelGGL(k_future_table, dim3((kTabN << kTabN) / 256), dim3(256), 0, nullptr, f->dMK, f->dsrc,
+                               f->n, f->dT);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+                return mdp_set_error(MDP_EHIP, "colonisation table kernel failed on device %d", device);
+        }
     }
-    const uint64_t recs = p->windows > 1 ? std::min<uint64_t>(nrep, p->reps) : 0;
-    if (recs > f->rec_cap) {
-        if (f->drec_occ) (void)hipFree(f->drec_occ);
-        if (f->drec_idx) (void)hipFree(f->drec_idx);
-        f->drec_occ = nullptr;
-        f->drec_idx = nullptr;
-        f->rec_cap = 0;
-        FUT_TRY(hipMalloc(&f->drec_occ, (size_t)recs * (f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t))));
-        FUT_TRY(hipMalloc((void **)&f->drec_idx, (size_t)recs * sizeof(uint32_t)));
-        f->rec_cap = recs;
-    }
+    // look-back overflow flags: [0] the device path (read and cleared by
+    // mdp_future_check), [1] the host-returning calls (their own)
+    if (hipMalloc((void **)&f->derr, 2 * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(f->derr, 0, 2 * sizeof(uint32_t)) != hipSuccess ||
+        hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&f->ev0) != hipSuccess || hipEventCreate(&f->ev1) != hipSuccess)
+        return mdp_set_error(MDP_EHIP, "device setup failed on device %d", device);
     return MDP_OK;
 }
 
@@ -1127,8 +1080,9 @@ int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan 
 
 extern "C" {
 
-// mdp_future_create (mode kFutWideOff) and mdp_future_create_opts; every
-// refusal of an argument comes before the first HIP call
+// mdp_future_create (mode kFutWideOff) and mdp_future_create_opts: select the
+// kernel, plan, upload, set attributes.  Every refusal of an argument comes
+// before the engine exists and before the first HIP call.
 static int fut_create(const int32_t *last_row, uint32_t n, const double *post, uint32_t necstep, double m, double d,
                       double KD, double KS, double dS, int device, FutWideMode mode, uint32_t sum_years,
                       mdp_future **out)
@@ -1140,134 +1094,37 @@ static int fut_create(const int32_t *last_row, uint32_t n, const double *post, u
     if (!(KD >= 0) || !std::isfinite(KD) || !(KS >= 0) || !std::isfinite(KS))
         return mdp_set_error(MDP_EINVAL, "-D and -S must be finite and >= 0");
     if (!(m > 0) && !(m < 0)) return mdp_set_error(MDP_EINVAL, "mean dispersal -m must be non-zero");
-    mdp_future *f = new (std::nothrow) mdp_future();
+    FutLanePlan lp;
+    FutWidePlan wp;
+    FutPostPlan pp;
+    if (int rc = np ? fut_wide_plan(last_row, n, np, m, d, KD, KS, dS, &wp)
+                    : fut_lane_plan(last_row, n, m, d, KD, KS, dS, &lp))
+        return rc;
+    if (int rc = fut_post_plan(post, necstep, &pp)) return rc;
+    // from here the engine owns what it holds: destroyed on every exit but the last
+    std::unique_ptr<mdp_future, void (*)(mdp_future *)> f(new (std::nothrow) mdp_future(), mdp_future_destroy);
     if (!f) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     f->device = device;
     f->n = n;
-    f->nm = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+    f->nm = fut_lane_nm(n);
     f->np = np;
     f->sum_years = sum_years;
     f->K = KD;
     f->necstep = necstep;
-    if (np) snprintf(f->kname, sizeof f->kname, "k_future_wide<%u>", np);
-    else snprintf(f->kname, sizeof f->kname, "k_future<%u>", f->nm);
-    // last survey row -> occupied bits and missing columns (:292-323)
-    std::vector<uint64_t> miss;
-    FutWidePlan wp;
+    f->lvalid = pp.lvalid;
+    f->pscale = pp.pscale;
     if (np) {
-        // the same in the lane-owned layout, with the two-sided distance image
-        if (int rc = fut_wide_plan(last_row, n, np, m, d, KD, KS, dS, &wp)) {
-            delete f;
-            return rc;
-        }
+        snprintf(f->kname, sizeof f->kname, "k_future_wide<%u>", np);
         f->nmiss = wp.nmiss;
         f->wlen = wp.len;
         f->ks0 = KS == 0;
+    } else {
+        snprintf(f->kname, sizeof f->kname, "k_future<%u>", f->nm);
+        f->nmiss = lp.nmiss;
+        f->occ0 = lp.occ0;
     }
-    for (uint32_t j = 0; j < n && !np; ++j) {
-        if (last_row[j] == 1) f->occ0 |= 1ull << j;
-        else if (last_row[j] == -1) miss.push_back(1ull << j);
-        else if (last_row[j] != 0) {
-            delete f;
-            return mdp_set_error(MDP_EINVAL, "survey value %d in column %u (expected -1, 0 or 1)", last_row[j], j);
-        }
-    }
-    if (miss.size() > 30) {
-        delete f;
-        return mdp_set_error(MDP_EUNSUPPORTED, "%zu missing patches (npstates = 2^%zu overflows int)", miss.size(),
-                             miss.size());
-    }
-    if (!np) f->nmiss = (uint32_t)miss.size();
-    // dispersal (:266-277), a = 1/m; M*K_D and the source term M[n][k]*K_S
-    const double a = 1.0 / m;
-    std::vector<double> MK(np ? 0 : (size_t)f->nm * f->nm, 0.0), src(f->nm, 0.0);
-    for (uint32_t i = 0; i < n && !np; ++i)
-        for (uint32_t j = i + 1; j < n; ++j) {
-            const double v = exp(-a * (j - i) * d);
-            MK[(size_t)i * f->nm + j] = v * KD;
-            MK[(size_t)j * f->nm + i] = v * KD;
-        }
-    for (uint32_t j = 0; j < n && !np; ++j) src[j] = exp(-a * (j + 1) * dS) * KS;
-    // trapezoid-weighted cumulative posterior in the reference's scan order
-    // (:362-369); the scan stops matching at the first NaN
-    std::vector<double> pcum((size_t)necstep * necstep);
-    double acc = 0;
-    size_t lv = pcum.size();
-    for (uint32_t ie = 0; ie < necstep; ++ie)
-        for (uint32_t ic = 0; ic < necstep; ++ic) {
-            double w = 1.0;
-            if (ie == 0 || ie == necstep - 1) w *= 0.5;
-            if (ic == 0 || ic == necstep - 1) w *= 0.5;
-            acc += w * post[(size_t)ie * necstep + ic];
-            const size_t i = (size_t)ie * necstep + ic;
-            pcum[i] = acc;
-            if (std::isnan(acc) && lv == pcum.size()) lv = i;
-        }
-    for (size_t i = 0; i < lv; ++i)
-        if (pcum[i] < (i ? pcum[i - 1] : 0.0)) {
-            delete f;
-            return mdp_set_error(MDP_EUNSUPPORTED, "posterior with negative entries (cell %zu): the sampler "
-                                 "needs a non-decreasing cumulative sum", i);
-        }
-    if (lv > 0 && !(pcum[lv - 1] > 0)) lv = 0;  // no draw is ever below the mass: (0, 0) for all
-    f->lvalid = (uint32_t)lv;
-    f->pscale = (double)((int)(necstep - 1) * (int)(necstep - 1));
-    int rc;
-    if (hipSetDevice(device) != hipSuccess) {
-        delete f;
-        return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
-    }
-    if (np) {
-        if ((rc = dev_up(&f->dimage, wp.image)) || (rc = dev_up(&f->dsrc, wp.src)) || (rc = dev_up(&f->dpcum, pcum)) ||
-            (rc = dev_up(&f->docc0, wp.occ0)) || (rc = dev_up(&f->dwmiss, wp.miss))) {
-            mdp_future_destroy(f);
-            return rc;
-        }
-        // the image and kFutMaxT year counters pass 64 KB of dynamic LDS
-        const void *fn = np == 1 ? (const void *)k_future_wide<1> : np == 2 ? (const void *)k_future_wide<2>
-                       : np == 4 ? (const void *)k_future_wide<4> : (const void *)k_future_wide<8>;
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fut_wide_lds(f, kFutMaxT)) !=
-            hipSuccess) {
-            mdp_future_destroy(f);
-            return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d", f->kname,
-                                 fut_wide_lds(f, kFutMaxT), device);
-        }
-        // the summary kernel: the image and one window's table
-        const void *fs = np == 1 ? (const void *)k_future_wide_tab<1> : np == 2 ? (const void *)k_future_wide_tab<2>
-                       : np == 4 ? (const void *)k_future_wide_tab<4> : (const void *)k_future_wide_tab<8>;
-        const size_t sum_lds = (size_t)2 * f->wlen * sizeof(double) + kFutSumTableBytes;
-        if (hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sum_lds) != hipSuccess) {
-            mdp_future_destroy(f);
-            return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d (summary)", f->kname, sum_lds,
-                                 device);
-        }
-    } else if ((rc = dev_up(&f->dMK, MK)) || (rc = dev_up(&f->dsrc, src)) || (rc = dev_up(&f->dpcum, pcum)) ||
-               (rc = dev_up(&f->dmiss, miss))) {
-        mdp_future_destroy(f);
-        return rc;
-    }
-    if (!np && f->nm == kTabN) {
-        if (hipMalloc((void **)&f->dT, sizeof(double) * (kTabN << kTabN)) != hipSuccess) {
-            mdp_future_destroy(f);
-            return mdp_set_error(MDP_EHIP, "device allocation failed on device %d", device);
-        }
-        hipLaunchKernelGGL(k_future_table, dim3((kTabN << kTabN) / 256), dim3(256), 0, nullptr, f->dMK, f->dsrc, n,
-                           f->dT);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            mdp_future_destroy(f);
-            return mdp_set_error(MDP_EHIP, "colonisation table kernel failed on device %d", device);
-        }
-    }
-    // look-back overflow flags: [0] the device path (read and cleared by
-    // mdp_future_check), [1] the host-returning calls (their own)
-    if (hipMalloc((void **)&f->derr, 2 * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(f->derr, 0, 2 * sizeof(uint32_t)) != hipSuccess ||
-        hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&f->ev0) != hipSuccess || hipEventCreate(&f->ev1) != hipSuccess) {
-        mdp_future_destroy(f);
-        return mdp_set_error(MDP_EHIP, "device setup failed on device %d", device);
-    }
-    *out = f;
+    if (int rc = fut_device_setup(f.get(), lp, wp, pp)) return rc;
+    *out = f.release();
     return MDP_OK;
 }
 
@@ -1305,13 +1162,7 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
     FUT_TRY(hipSetDevice(f->device));
     int rc;
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
-    if (nrep > f->states_cap) {
-        if (f->dstates) (void)hipFree(f->dstates);
-        f->dstates = nullptr;
-        f->states_cap = 0;
-        FUT_TRY(hipMalloc((void **)&f->dstates, (size_t)nrep * 64 * sizeof(uint32_t)));
-        f->states_cap = nrep;
-    }
+    if ((rc = fut_grow(f->dstates, f->states_cap, (size_t)nrep, 64 * sizeof(uint32_t)))) return rc;
     FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_launch_wide(f, seed, rep0, nrep, tfut, f->stream, f->dstates, f->derr + 1))) return rc;
     std::vector<uint32_t> lanes((size_t)nrep * 64);
@@ -1320,11 +1171,7 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
                            f->stream));
     FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     FUT_TRY(hipStreamSynchronize(f->stream));
-    if (err)
-        return mdp_set_error(MDP_EUNSUPPORTED,
-                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
-                             "below the (necstep-1)^2 scale)",
-                             kLookBack);
+    if ((rc = fut_lookback(err, false))) return rc;
     fut_wide_unpack(lanes.data(), nrep, f->n, f->np, words);
     return MDP_OK;
 }
@@ -1378,12 +1225,7 @@ int mdp_future_check(mdp_future *f, void *stream)
     FUT_TRY(hipMemcpyAsync(&err, f->derr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     FUT_TRY(hipMemsetAsync(f->derr, 0, sizeof(uint32_t), st));
     FUT_TRY(hipStreamSynchronize(st));
-    if (err)
-        return mdp_set_error(MDP_EUNSUPPORTED,
-                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
-                             "below the (necstep-1)^2 scale): the device counts are not valid",
-                             kLookBack);
-    return MDP_OK;
+    return fut_lookback(err, true);
 }
 
 int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
@@ -1402,11 +1244,7 @@ int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nr
     FUT_TRY(hipMemcpyAsync(h.data(), f->dcounts, tfut * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
     FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     FUT_TRY(hipStreamSynchronize(f->stream));
-    if (err)
-        return mdp_set_error(MDP_EUNSUPPORTED,
-                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
-                             "below the (necstep-1)^2 scale)",
-                             kLookBack);
+    if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) counts[t] += h[t];
     return MDP_OK;
 }
@@ -1418,16 +1256,9 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     FUT_TRY(hipSetDevice(f->device));
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
-    if ((rc = fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1))) return rc;
-    FUT_TRY(hipEventRecord(f->ev0, f->stream));
-    for (int i = 0; i < reps; ++i)
-        if ((rc = fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1))) return rc;
-    FUT_TRY(hipEventRecord(f->ev1, f->stream));
-    FUT_TRY(hipEventSynchronize(f->ev1));
-    float t = 0;
-    FUT_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
-    *ms = (double)t / reps;
-    return MDP_OK;
+    return fut_time(f, reps, ms, [&]() {
+        return fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1);
+    });
 }
 
 int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
@@ -1463,11 +1294,7 @@ int mdp_future_summary(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nre
     FUT_TRY(hipMemcpyAsync(h.data(), f->dtab, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
     FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     FUT_TRY(hipStreamSynchronize(f->stream));
-    if (err)
-        return mdp_set_error(MDP_EUNSUPPORTED,
-                             "a posterior draw needed more than %u look-back replicates (posterior mass far "
-                             "below the (necstep-1)^2 scale)",
-                             kLookBack);
+    if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) {
         const unsigned long long *row = h.data() + (size_t)t * cells;
         for (uint32_t m = 0; hist && m <= n; ++m) hist[(size_t)t * (n + 1) + m] += row[m];
@@ -1482,16 +1309,7 @@ int mdp_future_time_summary(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
-    if ((rc = fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1))) return rc;
-    FUT_TRY(hipEventRecord(f->ev0, f->stream));
-    for (int i = 0; i < reps; ++i)
-        if ((rc = fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1))) return rc;
-    FUT_TRY(hipEventRecord(f->ev1, f->stream));
-    FUT_TRY(hipEventSynchronize(f->ev1));
-    float t = 0;
-    FUT_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
-    *ms = (double)t / reps;
-    return MDP_OK;
+    return fut_time(f, reps, ms, [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1); });
 }
 
 int mdp_future_philox(uint64_t key, const uint32_t *ctr, uint32_t *out)

@@ -1,5 +1,6 @@
-// midaspom_amd/csrc/spom_future_plan.cpp -- host planning of k_future_wide
-// (spom_future_plan.h): option parsing, kernel selection, the two-sided
+// midaspom_amd/csrc/spom_future_plan.cpp -- host planning of the future
+// engine (spom_future_plan.h): option parsing, kernel selection, the
+// cumulative posterior, the lane kernels' mask and table, the two-sided
 // distance image, the lane-owned layout and its inverse.  Host only.
 #include "spom_future_plan.h"
 
@@ -60,6 +61,69 @@ int fut_select_kernel(uint32_t n, FutWideMode mode, uint32_t *np)
         return MDP_OK;
     }
     *np = n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8;
+    return MDP_OK;
+}
+
+int fut_lane_plan(const int32_t *last_row, uint32_t n, double m, double d, double KD, double KS, double dS,
+                  FutLanePlan *plan)
+{
+    if (!last_row || !plan || n == 0 || n > kFutLaneMaxN)
+        return mdp_set_error(MDP_EINVAL, "internal: lane plan of %u patches", n);
+    FutLanePlan &p = *plan;
+    p = FutLanePlan();
+    p.n = n;
+    p.nm = fut_lane_nm(n);
+    // last survey row -> occupied bits and missing columns (:292-323)
+    for (uint32_t j = 0; j < n; ++j) {
+        if (last_row[j] == 1) p.occ0 |= 1ull << j;
+        else if (last_row[j] == -1) p.miss.push_back(1ull << j);
+        else if (last_row[j] != 0)
+            return mdp_set_error(MDP_EINVAL, "survey value %d in column %u (expected -1, 0 or 1)", last_row[j], j);
+    }
+    if (p.miss.size() > kFutMaxMissing)
+        return mdp_set_error(MDP_EUNSUPPORTED, "%zu missing patches (npstates = 2^%zu overflows int)", p.miss.size(),
+                             p.miss.size());
+    p.nmiss = (uint32_t)p.miss.size();
+    // dispersal (:266-277), a = 1/m; M*K_D and the source term M[n][k]*K_S
+    const double a = 1.0 / m;
+    p.MK.assign((size_t)p.nm * p.nm, 0.0);
+    p.src.assign(p.nm, 0.0);
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j = i + 1; j < n; ++j) {
+            const double v = exp(-a * (j - i) * d);
+            p.MK[(size_t)i * p.nm + j] = v * KD;
+            p.MK[(size_t)j * p.nm + i] = v * KD;
+        }
+    for (uint32_t j = 0; j < n; ++j) p.src[j] = exp(-a * (j + 1) * dS) * KS;
+    return MDP_OK;
+}
+
+int fut_post_plan(const double *post, uint32_t necstep, FutPostPlan *plan)
+{
+    if (!plan || (necstep > 0 && !post)) return mdp_set_error(MDP_EINVAL, "null posterior");
+    FutPostPlan &p = *plan;
+    p = FutPostPlan();
+    // the scan stops matching at the first NaN
+    p.pcum.resize((size_t)necstep * necstep);
+    double acc = 0;
+    size_t lv = p.pcum.size();
+    for (uint32_t ie = 0; ie < necstep; ++ie)
+        for (uint32_t ic = 0; ic < necstep; ++ic) {
+            double w = 1.0;
+            if (ie == 0 || ie == necstep - 1) w *= 0.5;
+            if (ic == 0 || ic == necstep - 1) w *= 0.5;
+            acc += w * post[(size_t)ie * necstep + ic];
+            const size_t i = (size_t)ie * necstep + ic;
+            p.pcum[i] = acc;
+            if (std::isnan(acc) && lv == p.pcum.size()) lv = i;
+        }
+    for (size_t i = 0; i < lv; ++i)
+        if (p.pcum[i] < (i ? p.pcum[i - 1] : 0.0))
+            return mdp_set_error(MDP_EUNSUPPORTED, "posterior with negative entries (cell %zu): the sampler "
+                                 "needs a non-decreasing cumulative sum", i);
+    if (lv > 0 && !(p.pcum[lv - 1] > 0)) lv = 0;  // no draw is ever below the mass: (0, 0) for all
+    p.lvalid = (uint32_t)lv;
+    p.pscale = (double)((int)(necstep - 1) * (int)(necstep - 1));
     return MDP_OK;
 }
 

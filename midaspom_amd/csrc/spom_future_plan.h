@@ -1,9 +1,12 @@
-// midaspom_amd/csrc/spom_future_plan.h -- host planning of the future
-// engine's patch-parallel kernel k_future_wide<NP> (spom_future.hip): the
-// options of mdp_future_create_opts, the two-sided distance image, the
-// lane-owned bit layout of the occupancy and the un-interleaving of the
-// states the kernel writes.  No HIP runtime call (spom_future_plan.cpp links
-// into future_plan_check.cpp as it links into libmidaspom.so).
+// midaspom_amd/csrc/spom_future_plan.h -- host planning of the future engine
+// (spom_future.hip), both kernel families: the options of
+// mdp_future_create_opts and the kernel they select, the cumulative posterior
+// the sampler searches, the lane kernels' k_future<NM> occupancy mask and
+// dispersal table, and for the patch-parallel k_future_wide<NP> the two-sided
+// distance image, the lane-owned bit layout of the occupancy and the
+// un-interleaving of the states the kernel writes.  No HIP runtime call
+// (spom_future_plan.cpp links into future_plan_check.cpp as it links into
+// libmidaspom.so).
 #ifndef SPOM_FUTURE_PLAN_H
 #define SPOM_FUTURE_PLAN_H
 #include <cstdint>
@@ -31,6 +34,36 @@ int fut_parse_opts(const char *s, FutWideMode *mode, uint32_t *sum_years = nullp
 // mode's limit.
 int fut_select_kernel(uint32_t n, FutWideMode mode, uint32_t *np);
 
+// padded patch count NM of the lane kernel k_future<NM> of n <= 64 patches
+constexpr uint32_t fut_lane_nm(uint32_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+
+// What k_future<NM> is given of the last survey row and the dispersal
+// parameters (future.c:266-277, :292-323).
+struct FutLanePlan {
+    uint32_t n = 0, nm = 0, nmiss = 0;
+    uint64_t occ0 = 0;            // bit k = patch k occupied in the last survey
+    std::vector<uint64_t> miss;   // [nmiss] the bit of each missing patch, in patch order
+    std::vector<double> MK;       // [nm][nm] M[l][k]*K_D, 0.0 on the diagonal and in the padding
+    std::vector<double> src;      // [nm] M[n][k]*K_S, 0.0 for k >= n
+};
+
+// the last survey row (values -1 / 0 / 1, <= 30 missing) of n <= 64 patches
+// and the dispersal parameters into the plan
+int fut_lane_plan(const int32_t *last_row, uint32_t n, double m, double d, double KD, double KS, double dS,
+                  FutLanePlan *plan);
+
+// The trapezoid-weighted cumulative posterior in the reference's scan order
+// (:362-369), for both families.
+struct FutPostPlan {
+    std::vector<double> pcum;  // [necstep^2]
+    uint32_t lvalid = 0;       // cells the sampler searches: up to the first NaN; 0 when the mass is not positive
+    double pscale = 0.0;       // (double)((necstep-1)*(necstep-1)) (:361)
+};
+
+// MDP_EUNSUPPORTED for a cumulative sum that decreases before the first NaN
+// (a negative cell); post may be null when necstep is 0
+int fut_post_plan(const double *post, uint32_t necstep, FutPostPlan *plan);
+
 // Lane lambda of a wave owns the patch pairs m = lambda + 64*j, j < NP, that
 // is patches 2m and 2m+1; its occupancy word holds patch 2m + p in bit 2j + p.
 struct FutWidePlan {
@@ -49,8 +82,8 @@ struct FutWidePlan {
 };
 
 // first 16-byte slot of survivor l's row: slots m + slot0 hold
-// (M[l][2m]*K_D, M[l][2m+1]*K_D) for every pair m
-inline uint32_t fut_wide_slot0(uint32_t n, uint32_t len, uint32_t l)
+// (M[l][2m]*K_D, M[l][2m+1]*K_D) for every pair m (constexpr: host and device)
+constexpr uint32_t fut_wide_slot0(uint32_t n, uint32_t len, uint32_t l)
 {
     const uint32_t base = n - 1 - l;  // index in G of patch 0's entry
     return (base & 1u) ? (len + base - 1) >> 1 : base >> 1;

@@ -288,3 +288,43 @@ def test_plan_check_program(n):
     assert r.stdout.splitlines()[0].startswith("kernel " + want)
     r = _plan_check(PLAN_CHECK, row, "")
     assert (r.returncode == 0) == (n <= 64), r.stderr
+
+
+def lane_plan(row, m, d, KD, KS, dS):
+    """What future_plan_check prints for a lane kernel, from the definitions:
+    bit k of a mask is patch k, the missing bits in patch order, M*K_D padded
+    with zeros to NM x NM and the source row M[n]*K_S to NM."""
+    n = len(row)
+    NM = 8 if n <= 8 else 16 if n <= 16 else 32 if n <= 32 else 64
+    M = matrix(n, m, d, dS)
+    MK = np.zeros((NM, NM))
+    MK[:n, :n] = M[:n] * KD
+    src = np.zeros(NM)
+    src[:n] = M[n] * KS
+    occ0 = sum(1 << k for k, v in enumerate(row) if v == 1)
+    miss = np.array([1 << k for k, v in enumerate(row) if v == -1], dtype="<u8")
+    return (f"kernel k_future<{NM}>\n"
+            f"lane nmiss {miss.size} occ0 {occ0:x} miss {_fnv(miss.tobytes()):016x} "
+            f"MK {_fnv(MK.astype('<f8').tobytes()):016x} src {_fnv(src.astype('<f8').tobytes()):016x}\n")
+
+
+@pytest.mark.parametrize("n", [1, 7, 9, 17, 33, 64])
+def test_plan_check_program_lane(n):
+    """The lane kernels' plan (occupied mask, missing bits, M*K_D, source row)
+    with two missing patches (one at n = 1), on every padded size."""
+    assert PLAN_CHECK.exists(), "future_plan_check is built by `make -C midaspom_amd/csrc`"
+    row = make_row(n, min(2, n), 0.4, seed=2000 + n)
+    assert int((row == -1).sum()) == min(2, n)
+    for options in ("", "MDP_FUT_WIDE=auto"):
+        r = _plan_check(PLAN_CHECK, row, options)
+        assert r.returncode == 0, r.stderr
+        assert r.stdout == lane_plan(list(row), 400.0, 100.0, 0.7, 0.3, 150.0)
+
+
+def test_plan_check_program_lane_refusals():
+    """A lane row is refused as mdp_future_create refuses it."""
+    r = _plan_check(PLAN_CHECK, [1, 0, 2, 1], "")
+    assert r.returncode == 1 and "survey value 2 in column 2" in r.stderr
+    r = _plan_check(PLAN_CHECK, [-1] * 31 + [1], "")
+    assert r.returncode == 1 and "31 missing patches" in r.stderr
+    assert _plan_check(PLAN_CHECK, [-1] * 30 + [1], "").returncode == 0
