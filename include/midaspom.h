@@ -427,6 +427,70 @@ int mdp_scenario_set_grid(mdp_scenario *scenario, int ts, int tdis, const double
 int mdp_scenario_run(mdp_scenario *scenario, double *d_out, void *stream);
 int mdp_scenario_time_kernels(mdp_scenario *scenario, double *d_out, void *stream, int reps, double *ms);
 
+/* ------------------------------------------------------------------ */
+/* Simulated scenario likelihoods for rows of up to 64 patches          */
+/* (Rscript/simuls_traj.R, simtrajH1 / simtrajH2)                       */
+/* ------------------------------------------------------------------ */
+
+/* Also added after ABI 9 without a version bump.  The two hypotheses of
+ * mdp_scenario_lik by Monte Carlo, for first survey rows beyond the 16 patches
+ * of the exact engine (and any smaller one).  A replicate draws a uniform
+ * initial state over the 2^n, runs ts years under the scenario (kind 0
+ * die-off: E = e/K, pC = (c s1) K; kind 1 loss: E = e, pC = c (s1 + src K))
+ * and tdis baseline years (E = e, pC = c s1), and its final state is tallied:
+ *   L = 2^n E[prior(final) 1{final compatible with the row}]
+ * exactly in expectation.  Draws are Philox4x32-10 keyed by `seed`, addressed
+ * by (replicate, year, patch pair) as in the future engine, the initial state
+ * at counter {rep_lo, rep_hi, 0xffffffff, 1}; the grid point is not in the
+ * counter, so every point sees the same replicates (common random numbers)
+ * and no result depends on how replicates or points are split.
+ *
+ * create: row, n, m, p, d, kind as mdp_scenario_create; 1 <= n <= 64.  No
+ * device call is made before the first computing call, and every refusal of
+ * every call comes before its first device call.  Options (test hooks):
+ *   MDP_SIM_NM=8|16|32|64   the instantiation k_scnsim<NM>, at least the one
+ *                           n needs (the smallest NM >= n); smaller: MDP_EINVAL
+ *   MDP_SIM_LAUNCH_PTS=N    at most N grid points per launch (0: no cap)
+ * Refusals: MDP_EINVAL for n = 0, a row value outside {-1, 0, 1}, both
+ * tables NULL, ts < 0 or tdis < 0, a negative or non-finite e, c or dsrc, a K
+ * that is not finite and > 0, an unknown option name or value;
+ * MDP_EUNSUPPORTED for n > 64, `match` with more than 10 missing patches,
+ * ts + tdis > 12288, more than 2^20 grid points or 2^24 cells in a table,
+ * nrep > 2^31 per call. */
+typedef struct mdp_scenario_sim mdp_scenario_sim;
+int mdp_scenario_sim_create(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
+                            const char *options, mdp_scenario_sim **out);
+void mdp_scenario_sim_destroy(mdp_scenario_sim *sim);
+/* "k_scnsim<32>" (owned by the engine) */
+const char *mdp_scenario_sim_kernel(const mdp_scenario_sim *sim);
+/* Over replicates [rep0, rep0 + nrep) and the grid points g = ((ie*nc + ic)*nK
+ * + iK)*nd + id (the layout of mdp_scenario_lik; nd = 1 and dsrc ignored for
+ * kind 0), G = ne*nc*nK*nd:
+ *   hist[g*(n+1) + m]       += replicates with m occupied patches at the end
+ *   match[(g << nmiss) + j] += replicates whose final state is completion j
+ *                              of the row (the first missing patch is the
+ *                              MSB of j, dieoff.c:205-232)
+ * Host memory, 64-bit counts; either table may be NULL, not both. */
+int mdp_scenario_sim_tables(mdp_scenario_sim *sim, int ts, int tdis, const double *e, uint32_t ne, const double *c,
+                            uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd, uint64_t seed,
+                            uint64_t rep0, uint64_t nrep, uint64_t *hist, uint64_t *match);
+/* Same into caller-owned device memory (overwritten, not accumulated); the
+ * launches are asynchronous on `stream` (NULL = HIP's null stream), after the
+ * stream's earlier work has been waited for and the grid uploaded. */
+int mdp_scenario_sim_tables_device(mdp_scenario_sim *sim, int ts, int tdis, const double *e, uint32_t ne,
+                                   const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
+                                   uint32_t nd, uint64_t seed, uint64_t rep0, uint64_t nrep, uint64_t *d_hist,
+                                   uint64_t *d_match, void *stream);
+/* out[g] = (sum_j (double)prior_j * (double)match[g][j], j ascending) * 2^n
+ * / nrep, prior_j the float prior of completion j (dieoff.c:230).  Host. */
+int mdp_scenario_sim_lik(const mdp_scenario_sim *sim, const uint64_t *match, size_t npoints, uint64_t nrep,
+                         double *out);
+/* Mean duration (ms) of `reps` runs of the call's launches over replicates
+ * [0, nrep) (hist, and match when the row has <= 10 missing patches). */
+int mdp_scenario_sim_time_kernel(mdp_scenario_sim *sim, int ts, int tdis, const double *e, uint32_t ne,
+                                 const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
+                                 uint32_t nd, uint64_t seed, uint64_t nrep, int reps, double *ms);
+
 /* Thread-local description of the last error. */
 const char *mdp_last_error(void);
 

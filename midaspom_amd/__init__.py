@@ -28,6 +28,7 @@ __all__ = [
     "Model", "Engine", "grid", "log_total", "write_posterior", "posterior",
     "run_file", "MidaspomError", "Scenario", "kgrid", "dgrid", "first_row",
     "Future", "read_survey", "read_posterior", "device_count", "quasi_extinction", "mean_occupied",
+    "ScenarioSim", "count_likelihood",
 ]
 
 
@@ -412,6 +413,134 @@ class Scenario:
         ms = (ctypes.c_double * 2)()
         check(lib().mdp_scenario_time_kernels(self._h, ctypes.c_void_p(d_out), ctypes.c_void_p(stream), reps, ms))
         return {"k_scn_v": ms[0], "k_scn_lik": ms[1]}
+
+
+class ScenarioSim:
+    """The two scenario hypotheses by simulation (``mdp_scenario_sim``,
+    Rscript/simuls_traj.R simtrajH1 / simtrajH2), for first survey rows of up
+    to 64 patches: every replicate draws a uniform initial state, runs ``ts``
+    scenario years and ``tdis`` baseline years, and its final state is tallied
+    per grid point.  All grid points see the same replicates.
+
+    ``options`` (a dict or "NAME=VALUE;..." string; test hooks): ``MDP_SIM_NM``
+    = 8 | 16 | 32 | 64 picks the kernel instantiation, ``MDP_SIM_LAUNCH_PTS``
+    = N caps the grid points per launch.  Creating the object makes no device
+    call; the first computing call does."""
+
+    def __init__(self, row, kind: str = "dieoff", m: float = 400.0, p: float = 0.5, d: float = 200.0,
+                 device: int = 0, options=None):
+        if kind not in ("dieoff", "loss"):
+            raise ValueError("kind must be 'dieoff' or 'loss'")
+        self.kind = kind
+        row = np.ascontiguousarray(row, dtype=np.int32)
+        self.n = int(row.size)
+        self.nmiss = int((row == -1).sum())
+        h = ctypes.c_void_p()
+        opts = _lib.options_string(options, _lib.SCENARIO_SIM_OPTION_NAMES)
+        check(lib().mdp_scenario_sim_create(row.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), row.size, m, p, d,
+                                            1 if kind == "loss" else 0, device, opts, ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def kernel(self) -> str:
+        """Name of the simulation kernel, e.g. ``k_scnsim<32>``."""
+        return lib().mdp_scenario_sim_kernel(self._h).decode()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mdp_scenario_sim_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _grid(self, e, c, K, dsrc):
+        e = np.ascontiguousarray(np.atleast_1d(e), dtype=np.float64)
+        c = np.ascontiguousarray(np.atleast_1d(c), dtype=np.float64)
+        K = np.ascontiguousarray(np.atleast_1d(K), dtype=np.float64)
+        if self.kind == "loss":
+            dsrc = np.ascontiguousarray(np.atleast_1d(dsrc), dtype=np.float64)
+            shape = (e.size, c.size, K.size, dsrc.size)
+        else:
+            dsrc = np.zeros(1)
+            shape = (e.size, c.size, K.size)
+        return (_dptr(e), e.size, _dptr(c), c.size, _dptr(K), K.size, _dptr(dsrc), dsrc.size), shape, (e, c, K, dsrc)
+
+    def tables(self, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10, nrep: int = 10000, seed: int = 0,
+               rep0: int = 0, hist=True, match=True):
+        """(hist, match) over replicates [rep0, rep0 + nrep): uint64 arrays of
+        shape grid + (n + 1,) and grid + (2**nmiss,), grid = (ne, nc, nK) for
+        die-off and (ne, nc, nK, nd) for loss.  hist[..., m] counts the
+        replicates with m occupied patches after the last year, match[..., j]
+        those whose final state is completion j of the row (the first missing
+        patch is the most significant bit of j).  A table passed as an array
+        is added to; ``False`` leaves it out (None in its place)."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+
+        def table(x, width):
+            if x is False or x is None:
+                return None
+            if x is True:
+                return np.zeros(shape + (width,), dtype=np.uint64)
+            if x.dtype != np.uint64 or x.shape != shape + (width,) or not x.flags.c_contiguous:
+                raise ValueError(f"table must be a C-contiguous uint64 array of shape {shape + (width,)}")
+            return x
+        h = table(hist, self.n + 1)
+        # more than 10 missing patches: the library refuses match before it touches the table
+        mt = table(match, 1 << self.nmiss if self.nmiss <= 10 or not isinstance(match, bool) else 1)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        check(lib().mdp_scenario_sim_tables(self._h, ts, tdis, *args, seed, rep0, nrep,
+                                            h.ctypes.data_as(u64p) if h is not None else None,
+                                            mt.ctypes.data_as(u64p) if mt is not None else None))
+        return h, mt
+
+    def tables_device(self, d_hist: int, d_match: int, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10,
+                      nrep: int = 10000, seed: int = 0, rep0: int = 0, stream: int = 0) -> tuple:
+        """Into device memory at ``d_hist`` and ``d_match`` (uint64, the shapes
+        of tables(); either may be 0), overwritten, the launches asynchronous
+        on hipStream ``stream``.  Returns the grid shape."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        check(lib().mdp_scenario_sim_tables_device(self._h, ts, tdis, *args, seed, rep0, nrep,
+                                                   ctypes.c_void_p(d_hist or None), ctypes.c_void_p(d_match or None),
+                                                   ctypes.c_void_p(stream)))
+        return shape
+
+    def lik(self, match, nrep: int) -> np.ndarray:
+        """L = 2**n * sum_j prior_j match[..., j] / nrep per grid point: the
+        estimate of mdp_scenario_lik's value from tables() of ``nrep``
+        replicates in all."""
+        match = np.ascontiguousarray(match, dtype=np.uint64)
+        out = np.empty(match.shape[:-1])
+        check(lib().mdp_scenario_sim_lik(self._h, match.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), out.size,
+                                         nrep, _dptr(out)))
+        return out
+
+    def time_kernel(self, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10, nrep: int = 10000, seed: int = 0,
+                    reps: int = 10) -> float:
+        """Mean ms of the call's launches over ``reps`` runs."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        ms = ctypes.c_double()
+        check(lib().mdp_scenario_sim_time_kernel(self._h, ts, tdis, *args, seed, nrep, reps, ctypes.byref(ms)))
+        return ms.value
+
+
+def count_likelihood(hist, m_obs: int) -> np.ndarray:
+    """hist[..., m_obs] / hist.sum(-1): the share of replicates that end with
+    ``m_obs`` occupied patches, the statistic of Rscript/simuls_traj.R
+    (``rowMeans(simp == ppend)``).  NaN where a point has no replicates."""
+    hist = np.asarray(hist)
+    tot = hist.sum(axis=-1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return hist[..., m_obs].astype(np.float64) / tot
 
 
 # ---------------------------------------------------------------------------

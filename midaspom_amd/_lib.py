@@ -86,6 +86,9 @@ class EngineInfo(ctypes.Structure):
     ]
 
 
+# the (e, c, K, dsrc) axes of the scenario simulator's calls
+_SIM_GRID = [c_dbl_p, ctypes.c_uint32, c_dbl_p, ctypes.c_uint32, c_dbl_p, ctypes.c_uint32, c_dbl_p, ctypes.c_uint32]
+
 # (name, restype, argtypes) for every function declared in include/midaspom.h
 SIGNATURES = [
     ("mdp_model_load", ctypes.c_int,
@@ -183,6 +186,21 @@ SIGNATURES = [
       ctypes.c_void_p, ctypes.c_void_p]),
     ("mdp_future_time_summary", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, c_dbl_p]),
+    # the scenario simulator (also after ABI 9 without a version bump)
+    ("mdp_scenario_sim_create", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, ctypes.c_double, ctypes.c_float, ctypes.c_double,
+      ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("mdp_scenario_sim_destroy", None, [ctypes.c_void_p]),
+    ("mdp_scenario_sim_kernel", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("mdp_scenario_sim_tables", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+      ctypes.POINTER(ctypes.c_uint64)]),
+    ("mdp_scenario_sim_tables_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("mdp_scenario_sim_lik", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_uint64, c_dbl_p]),
+    ("mdp_scenario_sim_time_kernel", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, c_dbl_p]),
 ]
 
 _lib = None
@@ -227,6 +245,7 @@ ENGINE_OPTION_NAMES = (
     "MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")
 SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW", "MDP_SCN_LAUNCH_PTS")
 FUTURE_OPTION_NAMES = ("MDP_FUT_WIDE",)
+SCENARIO_SIM_OPTION_NAMES = ("MDP_SIM_NM", "MDP_SIM_LAUNCH_PTS")
 
 
 DIAG_OPTION_NAMES = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")

@@ -16,6 +16,14 @@
  * slabs (remainder to the first, the MIDASPOM_{dieoff,loss}_MPI.out
  * partition, dieoff_MPI.c:323-330), one host thread and engine per slab, the
  * slabs dealt round-robin over the visible GPUs; the output is the same file.
+ *
+ * Extension: -R <nrep> evaluates the same likelihood by simulation
+ * (mdp_scenario_sim, Rscript/simuls_traj.R) with nrep replicates per grid
+ * point -- the path for first rows of 17 to 64 patches, which the exact
+ * engine refuses; -r <seed> (default 0) keys the draws, -H <file> writes the
+ * final occupied-patch counts, one line per grid point in output order, n+1
+ * "%llu\t" values.  All grid points share their replicates, so the files do
+ * not depend on -g.  Without -R nothing changes.
  */
 #include <ctype.h>
 #include <math.h>
@@ -40,6 +48,8 @@ struct slab {
     int ts, tdis, dev;
     const double *K, *dv;
     double *L;
+    unsigned long long nrep, seed; /* -R, -r: nrep > 0 selects the simulator */
+    uint64_t *H;                   /* -H: [nK*nd][n+1] or NULL */
     int rc;
     char err[256];
 };
@@ -47,6 +57,30 @@ struct slab {
 static void *run_slab(void *arg)
 {
     struct slab *sl = arg;
+    if (sl->nrep) {
+        mdp_scenario_sim *sim = NULL;
+        const size_t G = (size_t)sl->nK * sl->nd;
+        unsigned nm = 0;
+        for (unsigned j = 0; j < sl->n; ++j) nm += sl->row[j] == -1;
+        uint64_t *match = NULL;
+        sl->rc = mdp_scenario_sim_create(sl->row, sl->n, sl->mdisp, sl->prioroc, sl->d, SCN_KIND, sl->dev, NULL, &sim);
+        if (sl->rc == MDP_OK && sl->nK) {
+            match = calloc(G << nm, sizeof(uint64_t)); /* nm <= 10, checked in main */
+            if (!match) {
+                snprintf(sl->err, sizeof sl->err, "out of host memory");
+                sl->rc = MDP_ENOMEM;
+                mdp_scenario_sim_destroy(sim);
+                return NULL;
+            }
+            sl->rc = mdp_scenario_sim_tables(sim, sl->ts, sl->tdis, &sl->eB, 1, &sl->cB, 1, sl->K, sl->nK, sl->dv, sl->nd,
+                                             sl->seed, 0, sl->nrep, sl->H, match);
+            if (sl->rc == MDP_OK) sl->rc = mdp_scenario_sim_lik(sim, match, G, sl->nrep, sl->L);
+        }
+        if (sl->rc != MDP_OK) snprintf(sl->err, sizeof sl->err, "%s", mdp_last_error());
+        free(match);
+        mdp_scenario_sim_destroy(sim);
+        return NULL;
+    }
     mdp_scenario *sc = NULL;
     sl->rc = mdp_scenario_create(sl->row, sl->n, sl->mdisp, sl->prioroc, sl->d, SCN_KIND, sl->dev, &sc);
     if (sl->rc == MDP_OK && sl->nK)
@@ -61,12 +95,12 @@ int main(int argc, char **argv)
 #if SCN_KIND == 0
     printf("------ MIDASPOM, in situ die-off hypothesis, beta version -------\n-> N. Alcala, E. M. Cole, N. A. "
            "Rosenberg <-\n");
-    const char *opts = "b:a:e:c:m:p:d:i:o:s:l:u:g:";
+    const char *opts = "b:a:e:c:m:p:d:i:o:s:l:u:g:R:r:H:";
     const char *fout = "lh_dieoff.txt";
 #else
     printf("------ MIDASPOM, habitat loss hypothesis, beta version -------\n-> N. Alcala, E. M. Cole, N. A. "
            "Rosenberg  <-\n");
-    const char *opts = "b:a:e:c:m:p:d:i:o:s:v:l:u:L:U:g:";
+    const char *opts = "b:a:e:c:m:p:d:i:o:s:v:l:u:L:U:g:R:r:H:";
     const char *fout = "lh_loss.txt";
 #endif
     int ts = 20, tdis = 0, have_a = 0, have_e = 0, have_c = 0, ngpu = 1;
@@ -74,7 +108,8 @@ int main(int argc, char **argv)
     unsigned nstep = 151, nstepd = 20;
     double eB = 0, cB = 0, Kmin = 0.1, Kmax = 100.0, mdisp = 400.0, d = 200, dmin = 200, dmax = 4000;
     float prioroc = 0.5f;
-    const char *fname = "input.txt";
+    const char *fname = "input.txt", *fhist = NULL;
+    unsigned long long nrep = 0, seed = 0;
     int c;
     opterr = 0;
     while ((c = getopt(argc, argv, opts)) != -1) {
@@ -95,6 +130,9 @@ int main(int argc, char **argv)
         case 'L': dmin = atof(optarg); break;
         case 'U': dmax = atof(optarg); break;
         case 'g': ngpu = atoi(optarg); break;
+        case 'R': nrep = strtoull(optarg, NULL, 10); break;
+        case 'r': seed = strtoull(optarg, NULL, 10); break;
+        case 'H': fhist = optarg; break;
         case '?':
             if (optopt == 'c')
                 fprintf(stderr, "Option -%c requires an argument.\n", optopt);
@@ -141,8 +179,12 @@ int main(int argc, char **argv)
     /* observed states and priors for the log lines (dieoff.c:205-232) */
     unsigned nm = 0;
     for (unsigned j = 0; j < n; ++j) nm += row[j] == -1;
+    if (nrep && nm > 10) { /* the simulator's match table holds 2^10 completions */
+        fprintf(stderr, "midaspom: %u missing patches in the first row: -R takes at most 10\n", nm);
+        return 1;
+    }
     const unsigned np = 1u << nm;
-    unsigned *ps = calloc(np, sizeof(unsigned));
+    unsigned long long *ps = calloc(np, sizeof(unsigned long long));
     float *pr = malloc(np * sizeof(float));
     for (unsigned k = 0; k < np; ++k) pr[k] = 1;
     unsigned s1 = 0;
@@ -150,10 +192,10 @@ int main(int argc, char **argv)
         if (row[j] == -1) s1++;
         for (unsigned k = 0; k < np; ++k) {
             if (row[j] > -1) {
-                ps[k] += (unsigned)row[j] << (n - j - 1);
+                ps[k] += (unsigned long long)row[j] << (n - j - 1);
             } else {
                 const unsigned st1 = np >> s1, b = k / st1 % 2;
-                ps[k] += b << (n - j - 1);
+                ps[k] += (unsigned long long)b << (n - j - 1);
                 pr[k] *= b * prioroc + (1 - b) * (1 - prioroc);
             }
         }
@@ -174,7 +216,7 @@ int main(int argc, char **argv)
 #if SCN_KIND == 1
         printf("\t");
 #endif
-        for (unsigned j = 0; j < n; ++j) printf("%u ", (ps[k] >> (n - 1 - j)) & 1u);
+        for (unsigned j = 0; j < n; ++j) printf("%u ", (unsigned)((ps[k] >> (n - 1 - j)) & 1u));
         printf("; pr=%lf\n", pr[k]);
     }
     double *K = malloc(nstep * sizeof(double)), *dv = malloc(nstepd * sizeof(double));
@@ -183,8 +225,10 @@ int main(int argc, char **argv)
     time_t start, end;
     time(&start);
     printf("Starting likelihood computation\n");
+    if (nrep) printf("Simulated likelihood: %llu replicates per grid point, seed %llu\n", nrep, seed);
     const unsigned nd = SCN_KIND == 1 ? nstepd : 1u;
     double *L = malloc((size_t)nstep * nd * sizeof(double));
+    uint64_t *H = nrep && fhist ? calloc((size_t)nstep * nd * (n + 1), sizeof(uint64_t)) : NULL;
     if (ngpu < 1) ngpu = 1;
     if ((unsigned)ngpu > nstep) ngpu = (int)(nstep ? nstep : 1);
     struct slab *sl = calloc((size_t)ngpu, sizeof *sl);
@@ -193,7 +237,7 @@ int main(int argc, char **argv)
     for (int r = 0; r < ngpu; ++r) {
         const unsigned k0 = r == 0 ? 0 : (unsigned)r * avg + rem, k1 = (unsigned)(r + 1) * avg + rem;
         sl[r] = (struct slab){row, n, k1 - k0, nd, mdisp, d, eB, cB, prioroc, ts, tdis, r, K + k0, dv,
-                              L + (size_t)k0 * nd, 0, ""};
+                              L + (size_t)k0 * nd, nrep, seed, H ? H + (size_t)k0 * nd * (n + 1) : NULL, 0, ""};
     }
     {   /* slabs dealt round-robin over the visible devices */
         const int ndev = mdp_device_count() > 0 ? mdp_device_count() : 1;
@@ -228,10 +272,22 @@ int main(int argc, char **argv)
 #endif
     }
     fclose(fe);
+    if (H) {
+        FILE *fh = fopen(fhist, "wb");
+        if (!fh) {
+            fprintf(stderr, "cannot write %s\n", fhist);
+            return 1;
+        }
+        for (size_t g = 0; g < (size_t)nstep * nd; ++g) {
+            for (unsigned m = 0; m <= n; ++m) fprintf(fh, "%llu\t", (unsigned long long)H[g * (n + 1) + m]);
+            fprintf(fh, "\n");
+        }
+        fclose(fh);
+    }
     printf("done\n");
     time(&end);
     printf("Finished. It took  %.2lf min\n", difftime(end, start) / 60.0);
-    free(row), free(ps), free(pr), free(K), free(dv), free(L);
+    free(row), free(ps), free(pr), free(K), free(dv), free(L), free(H);
     /* without the HIP runtime's exit-time teardown unless a tool needs the
      * exit handlers (cli_exit.h) */
     mdp_cli_leave(0);

@@ -58,13 +58,14 @@
 
 #pragma clang fp contract(off)
 
+#include "spom_rng.h"  // u32x4, philox, kRandMax, u_gt, u_lt (shared with spom_scnsim.hip)
+
 namespace {
 
 constexpr int kFutBlock = 256;
 constexpr int kFutMaxWG = 4096;         // grid-stride cap (>= 16 workgroups per CU)
 constexpr uint32_t kFutMaxT = 12288;    // LDS year counters (48 KB; + 16 KB table for n <= 8)
 constexpr uint32_t kLookBack = 1u << 16;
-constexpr double kRandMax = 2147483647.0;  // glibc RAND_MAX
 
 #define FUT_TRY(expr)                                                                        \
     do {                                                                                     \
@@ -73,26 +74,6 @@ constexpr double kRandMax = 2147483647.0;  // glibc RAND_MAX
             return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                                  __FILE__, __LINE__);                                        \
     } while (0)
-
-// Philox4x32-10 (Salmon et al., SC'11), the Random123 constants.
-struct u32x4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ u32x4 philox(uint32_t k0, uint32_t k1, u32x4 c)
-{
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        // one v_mad_u64_u32 per product (instead of mul_lo + mul_hi)
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c = u32x4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 struct FutArgs {
     uint32_t n, nmiss, tfut, lvalid;
@@ -103,30 +84,6 @@ struct FutArgs {
     double pscale;          // (double)((necstep-1)*(necstep-1)) (:361)
     double K;               // K_D (:67, :93)
 };
-
-// The reference compares u = (double)r / (double)RAND_MAX with a threshold
-// (u > E, u < pC).  r * fl(1/RAND_MAX) is within 3.4e-16 of fl(r/RAND_MAX)
-// (both within ~1.2 ulp of r/RAND_MAX <= 1), so outside a 1e-15 band around
-// the threshold the product decides the comparison; inside it the exact
-// correctly rounded quotient does.  Bit-identical outcomes, ~never divides.
-constexpr double kInvRandMax = 1.0 / 2147483647.0;
-constexpr double kBand = 1e-15;
-
-__device__ __forceinline__ bool u_gt(uint32_t r, double x)  // fl(r/R) > x
-{
-    const double q = (double)r * kInvRandMax;
-    if (q > x + kBand) return true;
-    if (q < x - kBand) return false;
-    return (double)r / kRandMax > x;
-}
-
-__device__ __forceinline__ bool u_lt(uint32_t r, double x)  // fl(r/R) < x
-{
-    const double q = (double)r * kInvRandMax;
-    if (q < x - kBand) return true;
-    if (q > x + kBand) return false;
-    return (double)r / kRandMax < x;
-}
 
 // first i < len with x < pcum[i] (pcum non-decreasing), or len
 __device__ __forceinline__ uint32_t upper_bound(const double *__restrict__ pcum, uint32_t len, double x)

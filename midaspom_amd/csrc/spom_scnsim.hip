@@ -1,0 +1,484 @@
+// midaspom_amd/csrc/spom_scnsim.hip -- the die-off and habitat-loss
+// hypotheses by simulation, for first survey rows the exact scenario engine
+// (spom_scenario.hip, 2^n states, n <= 16) cannot hold: 17..64 patches, and
+// any smaller row.  The reference's authors do the same in R
+// (Rscript/simuls_traj.R, simtrajH1 / simtrajH2): draw an initial state, run
+// ts years under the scenario and tdis baseline years, tally the final state.
+//
+// With a uniform initial state the estimator is exact in expectation:
+//   L = sum_i sum_s [PK^ts P^tdis]_{i,s} prior_s
+//     = 2^n E[ prior(final) 1{final compatible with the row} ]
+// (main_MIDASPOM_dieoff.c:304-351, main_MIDASPOM_loss.c:341-386).
+//
+// One replicate rg = rep0 + r, the same for every grid point but for its
+// rates (common random numbers: the counter holds no grid point):
+//   initial state  w = philox(seed; rg_lo, rg_hi, 0xffffffff, 1): patch k
+//                  occupied iff bit k & 31 of word k >> 5 (fair bits);
+//   year t         the future engine's addressing (spom_future.hip): pair
+//                  m = k >> 1, w = philox(seed; rg_lo, rg_hi, t, m), word
+//                  2(k&1) the extinction draw, 2(k&1)+1 the colonisation draw;
+//   rates          s1_k = sum over surviving l != k, ascending, of M[l][k];
+//                  scenario years t < ts:
+//                    die-off (dieoff.c:51-83)  E = min(1, e/K), pC = min(1, (c s1) K)
+//                    loss (loss.c:52-105)      E = min(1, e),   pC = min(1, c (s1 + src_k K))
+//                  baseline years: E = min(1, e), pC = min(1, c s1).
+// Contraction is off: every product is rounded before the next operation.
+//
+// GPU design: one lane per (grid point, replicate), the 64 lanes of a wave on
+// one grid point, so K, e, c, E and the source row are wave-uniform (scalar
+// operands).  A work tile is (point, 256 replicates); workgroups of 256
+// threads walk the tiles grid-stride.  Occupancy is one 64-bit mask; the
+// year is k_future's (fut_year<NM>) on the unscaled M, K applied after the
+// sum.  The tallies happen once per trajectory: ballots per wave, then 64-bit
+// integer atomics into the global tables -- exact, the same for every split.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <type_traits>
+#include <vector>
+
+#include "mdp_internal.h"
+#include "spom_scnsim_plan.h"
+
+#pragma clang fp contract(off)
+
+#include "spom_rng.h"
+
+namespace {
+
+#define SIM_TRY(expr)                                                                        \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                \
+            return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                                 __FILE__, __LINE__);                                        \
+    } while (0)
+
+constexpr int kTabN = 8;  // k_scnsim<8>: survivor-sum table of the unscaled M in LDS
+
+struct SimArgs {
+    uint32_t n, nmiss, ts, tdis;
+    uint32_t nc, nK, nd, kind;
+    uint64_t p0;       // first grid point of the launch
+    uint64_t tiles;    // work tiles of the launch: points x tpp
+    uint64_t tpp;      // tiles per point: ceil(nrep / 256)
+    uint64_t rep0, nrep;
+    uint32_t key0, key1;
+    uint64_t live, fixed, missmask;
+};
+
+// one year of replicate rg: fut_year<NM> of spom_future.hip on the unscaled
+// table, with the scenario's pressure
+//   pC = (c (s1 + src_k ks)) km
+// where (ks, km) = (0, 1) in a baseline year, (0, K) under die-off and (K, 1)
+// under loss: adding 0.0 to s1 >= 0 and multiplying by 1.0 are exact, so each
+// case is the reference's own expression and rounding.
+template <int NM>
+__device__ __forceinline__ uint64_t sim_year(const SimArgs &a, const double *__restrict__ M,
+                                             const double *__restrict__ src, const double *Ts, uint64_t rg,
+                                             uint32_t t, uint32_t npairs, uint64_t occ, double E, double c, double ks,
+                                             double km)
+{
+    uint64_t surv = 0;
+    uint32_t colw[NM];
+#pragma unroll
+    for (int m = 0; m < NM / 2; ++m) {
+        if ((uint32_t)m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, (uint32_t)m});
+            const uint32_t k0 = 2 * m, k1 = 2 * m + 1;
+            colw[k0] = w.y >> 1;
+            colw[k1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (dieoff.c:56-64)
+            if (((occ >> k0) & 1u) && u_gt(w.x >> 1, E)) surv |= 1ull << k0;
+            if (((occ >> k1) & 1u) && u_gt(w.z >> 1, E)) surv |= 1ull << k1;
+        } else {
+            colw[2 * m] = colw[2 * m + 1] = 0;
+        }
+    }
+    // colonisation sums, ascending l for every k (dieoff.c:72-77)
+    double s1[NM];
+    if constexpr (NM == kTabN) {
+        const double2 *row = reinterpret_cast<const double2 *>(Ts + (uint32_t)surv * kTabN);
+#pragma unroll
+        for (int k = 0; k < NM; k += 2) {
+            const double2 v = row[k / 2];
+            s1[k] = v.x, s1[k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NM; ++k) s1[k] = 0.0;
+        for (uint32_t l = 0; l < a.n; ++l) {
+            const bool on = (surv >> l) & 1u;
+#pragma unroll
+            for (int k = 0; k < NM; ++k) s1[k] += on ? M[l * NM + k] : 0.0;
+        }
+    }
+    uint64_t nw = surv;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+        if ((uint32_t)k < a.n && !((surv >> k) & 1u)) {
+            const double sk = src[k] * ks;       // loss.c:95-98: the product is rounded before the add
+            double pc = (c * (s1[k] + sk)) * km;  // dieoff.c:78 (c s1) K
+            if (pc > 1) pc = 1;
+            if (u_lt(colw[k], pc)) nw |= 1ull << k;
+        }
+    }
+    return nw;
+}
+
+template <int NM>
+__global__ __launch_bounds__(kSimBlock) void k_scnsim(SimArgs a, const double *__restrict__ M,
+                                                      const double *__restrict__ srcv,
+                                                      const double *__restrict__ ev, const double *__restrict__ cv,
+                                                      const double *__restrict__ Kv,
+                                                      const uint32_t *__restrict__ miss,
+                                                      unsigned long long *__restrict__ hist,
+                                                      unsigned long long *__restrict__ match)
+{
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    double *Ts = dyn;
+    if constexpr (NM == kTabN) {
+        // T[surv][k] = sum over l in surv, l != k, ascending, of M[l][k]
+        for (uint32_t i = threadIdx.x; i < (1u << kTabN) * kTabN; i += kSimBlock) {
+            const uint32_t sv = i / kTabN, k = i % kTabN;
+            double s = 0.0;
+            for (uint32_t l = 0; l < a.n; ++l)
+                if (l != k && ((sv >> l) & 1u)) s += M[l * kTabN + k];
+            Ts[i] = s;
+        }
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t npairs = (a.n + 1) >> 1;
+    const uint32_t years = a.ts + a.tdis;
+    for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        // workgroup-uniform: the tile's grid point; wave-uniform: its replicates
+        const uint64_t pl = tile / a.tpp;
+        const uint64_t g = a.p0 + pl;
+        const uint64_t rb = (tile - pl * a.tpp) * kSimBlock + (threadIdx.x & ~63u);
+        if (rb >= a.nrep) continue;  // a wave past the last replicate
+        const uint64_t r = rb + lane, rg = a.rep0 + r;
+        const bool act = r < a.nrep;
+        const uint32_t id = (uint32_t)(g % a.nd), iK = (uint32_t)((g / a.nd) % a.nK);
+        const uint32_t ic = (uint32_t)((g / ((uint64_t)a.nd * a.nK)) % a.nc);
+        const uint32_t ie = (uint32_t)(g / ((uint64_t)a.nd * a.nK * a.nc));
+        const double e = ev[ie], c = cv[ic], K = Kv[iK];
+        double Eb = e;  // baseline and loss: E = e (loss.c:57)
+        if (Eb > 1) Eb = 1;
+        double Es = a.kind ? e : e / K;  // dieoff.c:56-57
+        if (Es > 1) Es = 1;
+        const double Ks = a.kind ? K : 0.0, Km = a.kind ? 1.0 : K;
+        const double *src = srcv + (size_t)id * NM;
+        // ---- initial state: 64 fair bits
+        uint64_t occ = 0;
+        if (act) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), 0xffffffffu, 1u});
+            occ = (((uint64_t)w.y << 32) | w.x) & a.live;
+        }
+        // ---- ts scenario years, then tdis baseline years
+        for (uint32_t t = 0; t < years; ++t) {
+            const bool scen = t < a.ts;
+            // nobody left in the wave and no source in this or any later
+            // year: every sum is 0, pC = c*0, and no draw is below 0
+            if (!(a.kind && scen) && __ballot(act && occ != 0) == 0) break;
+            if (act) occ = sim_year<NM>(a, M, src, Ts, rg, t, npairs, occ, scen ? Es : Eb, c, scen ? Ks : 0.0,
+                                        scen ? Km : 1.0);
+        }
+        // ---- tallies of the final state
+        if (hist) {  // one atomic per distinct occupied count in the wave
+            const uint32_t m = (uint32_t)__popcll(occ);
+            unsigned long long *row = hist + g * (a.n + 1);
+            uint64_t rem = __ballot(act);
+            while (rem) {
+                const uint32_t lead = (uint32_t)__builtin_ctzll(rem);
+                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)m, (int)lead);
+                const uint64_t same = __ballot(act && m == v);
+                if (lane == lead) atomicAdd(&row[v], (unsigned long long)__popcll(same));
+                rem &= ~same;
+            }
+        }
+        if (match) {  // compatible with the row: its completion, the first missing patch the MSB
+            const bool ok = act && ((occ ^ a.fixed) & ~a.missmask) == 0;
+            uint32_t j = 0;
+            for (uint32_t q = 0; q < a.nmiss; ++q) j = (j << 1) | (uint32_t)((occ >> miss[q]) & 1u);
+            unsigned long long *row = match + (g << a.nmiss);
+            uint64_t rem = __ballot(ok);
+            while (rem) {
+                const uint32_t lead = (uint32_t)__builtin_ctzll(rem);
+                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)j, (int)lead);
+                const uint64_t same = __ballot(ok && j == v);
+                if (lane == lead) atomicAdd(&row[v], (unsigned long long)__popcll(same));
+                rem &= ~same;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+struct mdp_scenario_sim {
+    SimPlan plan;
+    int device = 0;
+    bool ready = false;  // the device side exists (set up by the first call that needs it)
+    bool touched = false;  // a device call was made for this engine
+    char kname[32] = "";
+    double *dM = nullptr, *dgrid = nullptr;
+    uint32_t *dmiss = nullptr;
+    unsigned long long *dhist = nullptr, *dmatch = nullptr;
+    size_t grid_cap = 0, hist_cap = 0, match_cap = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace {
+
+template <typename T>
+int sim_grow(T *&p, size_t &cap, size_t need)
+{
+    if (need <= cap) return MDP_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    SIM_TRY(hipMalloc((void **)&p, need * sizeof(T)));
+    cap = need;
+    return MDP_OK;
+}
+
+// the one switch over the padded patch count: fn(integral_constant<int, NM>)
+template <typename F>
+int sim_for_nm(uint32_t nm, F &&fn)
+{
+    switch (nm) {
+    case 8: return fn(std::integral_constant<int, 8>());
+    case 16: return fn(std::integral_constant<int, 16>());
+    case 32: return fn(std::integral_constant<int, 32>());
+    case 64: return fn(std::integral_constant<int, 64>());
+    default: return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", nm);
+    }
+}
+
+// the first device calls of an engine: the device, the tables, stream and events
+int sim_device(mdp_scenario_sim *s)
+{
+    if (s->ready) {
+        SIM_TRY(hipSetDevice(s->device));
+        return MDP_OK;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
+    if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
+    SIM_TRY(hipSetDevice(s->device));
+    s->touched = true;
+    if (!s->dM) {
+        SIM_TRY(hipMalloc((void **)&s->dM, s->plan.M.size() * sizeof(double)));
+        SIM_TRY(hipMemcpy(s->dM, s->plan.M.data(), s->plan.M.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!s->dmiss) {
+        SIM_TRY(hipMalloc((void **)&s->dmiss, std::max<size_t>(1, s->plan.miss.size()) * sizeof(uint32_t)));
+        if (!s->plan.miss.empty())
+            SIM_TRY(hipMemcpy(s->dmiss, s->plan.miss.data(), s->plan.miss.size() * sizeof(uint32_t),
+                              hipMemcpyHostToDevice));
+    }
+    if (!s->stream) SIM_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (!s->ev0) SIM_TRY(hipEventCreate(&s->ev0));
+    if (!s->ev1) SIM_TRY(hipEventCreate(&s->ev1));
+    s->ready = true;
+    return MDP_OK;
+}
+
+struct SimGrid {
+    int ts, tdis;
+    const double *e, *c, *K, *dsrc;
+    uint32_t ne, nc, nK, nd;
+};
+
+// the axes and the source rows into s->dgrid: [e | c | K | src[nd][nm]].
+// `st` is drained first, so that no launch still reads the buffer.
+int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
+{
+    std::vector<double> src;
+    sim_src(s->plan, gr.dsrc, gr.nd, &src);
+    std::vector<double> h;
+    h.reserve((size_t)gr.ne + gr.nc + gr.nK + src.size());
+    h.insert(h.end(), gr.e, gr.e + gr.ne);
+    h.insert(h.end(), gr.c, gr.c + gr.nc);
+    h.insert(h.end(), gr.K, gr.K + gr.nK);
+    h.insert(h.end(), src.begin(), src.end());
+    SIM_TRY(hipStreamSynchronize(st));
+    if (int rc = sim_grow(s->dgrid, s->grid_cap, h.size())) return rc;
+    SIM_TRY(hipMemcpy(s->dgrid, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    return MDP_OK;
+}
+
+// every launch of a call on st; the tables accumulate
+int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint64_t seed, uint64_t rep0,
+               uint64_t nrep, unsigned long long *d_hist, unsigned long long *d_match, hipStream_t st)
+{
+    const SimPlan &p = s->plan;
+    const double *de = s->dgrid, *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = dK + gr.nK;
+    const size_t lds = p.nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0;
+    for (const SimLaunch &l : call.launches) {
+        SimArgs a{};
+        a.n = p.n;
+        a.nmiss = p.nmiss;
+        a.ts = (uint32_t)gr.ts;
+        a.tdis = (uint32_t)gr.tdis;
+        a.nc = gr.nc;
+        a.nK = gr.nK;
+        a.nd = gr.nd;
+        a.kind = (uint32_t)p.kind;
+        a.p0 = l.p0;
+        a.tiles = l.tiles;
+        a.tpp = call.tiles_per_point;
+        a.rep0 = rep0;
+        a.nrep = nrep;
+        a.key0 = (uint32_t)seed;
+        a.key1 = (uint32_t)(seed >> 32);
+        a.live = p.live;
+        a.fixed = p.fixed;
+        a.missmask = p.missmask;
+        if (int rc = sim_for_nm(p.nm, [&](auto NM) {
+                hipLaunchKernelGGL(k_scnsim<decltype(NM)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a, s->dM, dsrc,
+                                   de, dc, dK, s->dmiss, d_hist, d_match);
+                return MDP_OK;
+            }))
+            return rc;
+        SIM_TRY(hipGetLastError());
+    }
+    return MDP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Every refusal comes before the engine exists; the engine's device side is
+// set up by the first call that computes, after that call's own refusals.
+int mdp_scenario_sim_create(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
+                            const char *options, mdp_scenario_sim **out)
+{
+    if (!out) return mdp_set_error(MDP_EINVAL, "null argument");
+    *out = nullptr;
+    SimOpts opts;
+    if (int rc = sim_parse_opts(options, &opts)) return rc;
+    std::unique_ptr<mdp_scenario_sim> s(new (std::nothrow) mdp_scenario_sim());
+    if (!s) return mdp_set_error(MDP_ENOMEM, "out of host memory");
+    if (int rc = sim_plan(row, n, m, p, d, kind, opts, &s->plan)) return rc;
+    s->device = device;
+    snprintf(s->kname, sizeof s->kname, "k_scnsim<%u>", s->plan.nm);
+    *out = s.release();
+    return MDP_OK;
+}
+
+void mdp_scenario_sim_destroy(mdp_scenario_sim *s)
+{
+    if (!s) return;
+    if (s->touched) {
+        (void)hipSetDevice(s->device);
+        if (s->stream) (void)hipStreamSynchronize(s->stream);
+        (void)hipFree(s->dM);
+        (void)hipFree(s->dgrid);
+        (void)hipFree(s->dmiss);
+        (void)hipFree(s->dhist);
+        (void)hipFree(s->dmatch);
+        if (s->ev0) (void)hipEventDestroy(s->ev0);
+        if (s->ev1) (void)hipEventDestroy(s->ev1);
+        if (s->stream) (void)hipStreamDestroy(s->stream);
+    }
+    delete s;
+}
+
+const char *mdp_scenario_sim_kernel(const mdp_scenario_sim *s) { return s ? s->kname : ""; }
+
+int mdp_scenario_sim_tables_device(mdp_scenario_sim *s, int ts, int tdis, const double *e, uint32_t ne,
+                                   const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
+                                   uint32_t nd, uint64_t seed, uint64_t rep0, uint64_t nrep, uint64_t *d_hist,
+                                   uint64_t *d_match, void *stream)
+{
+    if (!s) return mdp_set_error(MDP_EINVAL, "null scenario simulator");
+    SimCall call;
+    if (int rc = sim_call(s->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, nrep, d_hist != nullptr,
+                          d_match != nullptr, &call))
+        return rc;
+    if (int rc = sim_device(s)) return rc;
+    hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
+    const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
+    if (int rc = sim_upload(s, gr, st)) return rc;
+    if (d_hist) SIM_TRY(hipMemsetAsync(d_hist, 0, call.hist_cells * sizeof(uint64_t), st));
+    if (d_match) SIM_TRY(hipMemsetAsync(d_match, 0, call.match_cells * sizeof(uint64_t), st));
+    return sim_launch(s, call, gr, seed, rep0, nrep, (unsigned long long *)d_hist, (unsigned long long *)d_match, st);
+}
+
+int mdp_scenario_sim_tables(mdp_scenario_sim *s, int ts, int tdis, const double *e, uint32_t ne, const double *c,
+                            uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd, uint64_t seed,
+                            uint64_t rep0, uint64_t nrep, uint64_t *hist, uint64_t *match)
+{
+    if (!s) return mdp_set_error(MDP_EINVAL, "null scenario simulator");
+    SimCall call;
+    if (int rc = sim_call(s->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, nrep, hist != nullptr, match != nullptr,
+                          &call))
+        return rc;
+    if (nrep == 0) return MDP_OK;
+    if (int rc = sim_device(s)) return rc;
+    if (hist)
+        if (int rc = sim_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+    if (match)
+        if (int rc = sim_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+    int rc = mdp_scenario_sim_tables_device(s, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, seed, rep0, nrep,
+                                            hist ? (uint64_t *)s->dhist : nullptr,
+                                            match ? (uint64_t *)s->dmatch : nullptr, s->stream);
+    if (rc) return rc;
+    std::vector<uint64_t> hh(hist ? (size_t)call.hist_cells : 0), hm(match ? (size_t)call.match_cells : 0);
+    if (hist)
+        SIM_TRY(hipMemcpyAsync(hh.data(), s->dhist, hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    if (match)
+        SIM_TRY(hipMemcpyAsync(hm.data(), s->dmatch, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    SIM_TRY(hipStreamSynchronize(s->stream));
+    for (size_t i = 0; i < hh.size(); ++i) hist[i] += hh[i];
+    for (size_t i = 0; i < hm.size(); ++i) match[i] += hm[i];
+    return MDP_OK;
+}
+
+int mdp_scenario_sim_lik(const mdp_scenario_sim *s, const uint64_t *match, size_t npoints, uint64_t nrep, double *out)
+{
+    if (!s) return mdp_set_error(MDP_EINVAL, "null scenario simulator");
+    return sim_lik(s->plan, match, npoints, nrep, out);
+}
+
+int mdp_scenario_sim_time_kernel(mdp_scenario_sim *s, int ts, int tdis, const double *e, uint32_t ne, const double *c,
+                                 uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd,
+                                 uint64_t seed, uint64_t nrep, int reps, double *ms)
+{
+    if (!s) return mdp_set_error(MDP_EINVAL, "null scenario simulator");
+    const bool want_match = s->plan.nmiss <= kSimMaxMatchMissing;
+    SimCall call;
+    if (int rc = sim_call(s->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, nrep, true, want_match, &call)) return rc;
+    if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
+    if (int rc = sim_device(s)) return rc;
+    if (int rc = sim_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+    if (want_match)
+        if (int rc = sim_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+    const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
+    if (int rc = sim_upload(s, gr, s->stream)) return rc;
+    SIM_TRY(hipMemsetAsync(s->dhist, 0, call.hist_cells * sizeof(uint64_t), s->stream));
+    if (want_match) SIM_TRY(hipMemsetAsync(s->dmatch, 0, call.match_cells * sizeof(uint64_t), s->stream));
+    auto launch = [&]() {
+        return sim_launch(s, call, gr, seed, 0, nrep, s->dhist, want_match ? s->dmatch : nullptr, s->stream);
+    };
+    if (int rc = launch()) return rc;  // warm-up
+    SIM_TRY(hipEventRecord(s->ev0, s->stream));
+    for (int i = 0; i < reps; ++i)
+        if (int rc = launch()) return rc;
+    SIM_TRY(hipEventRecord(s->ev1, s->stream));
+    SIM_TRY(hipEventSynchronize(s->ev1));
+    float t = 0;
+    SIM_TRY(hipEventElapsedTime(&t, s->ev0, s->ev1));
+    *ms = (double)t / reps;
+    return MDP_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,13 @@ split into contiguous row slabs (remainder to rank 0,
 main_MIDASPOM_dieoff_MPI.c:323-330, main_MIDASPOM_loss_MPI.c:366-371), one
 gather to rank 0, and that program's per-rank stdout lines (banner :108,
 start / end :320, :397, send / gather :401-418).  Rank 0 writes the file.
+
+`-R nrep` evaluates the likelihood by simulation (midaspom_amd.ScenarioSim,
+Rscript/simuls_traj.R) with nrep replicates per grid point: the path for first
+rows of 17 to 64 patches.  `-r seed` (default 0) keys the draws; `-H file`
+writes the final occupied-patch counts, one line per grid point (single
+process only).  Same bytes as the compiled drop-ins, for every -g and rank
+count: all grid points share their replicates.
 """
 from __future__ import annotations
 
@@ -55,6 +62,9 @@ def parse_args(kind, argv):
         ap.add_argument("-U", type=float, default=4000.0, help="source distance upper bound")
     ap.add_argument("-g", type=int, default=None,
                     help="GPUs (single process): K slabs, one thread per slab (default MIDASPOM_GPUS or 1)")
+    ap.add_argument("-R", type=int, default=0, help="simulate: replicates per grid point (0: the exact engine)")
+    ap.add_argument("-r", type=int, default=0, help="seed of the simulated likelihood")
+    ap.add_argument("-H", default=None, help="with -R: file of final occupied-patch counts per grid point")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl)")
     return ap.parse_args(argv)
 
@@ -64,7 +74,7 @@ def _states(row, p):
     n = row.size
     miss = [j for j in range(n) if row[j] == -1]
     np_ = 1 << len(miss)
-    ps = np.zeros(np_, dtype=np.int64)
+    ps = np.zeros(np_, dtype=object if n > 62 else np.int64)  # the state numbers of 63 and 64 patches pass int64
     pr = np.ones(np_, dtype=np.float32)
     s1 = 0
     for j in range(n):
@@ -81,6 +91,19 @@ def _states(row, p):
     return ps, pr
 
 
+def _slab(mdp, row, kind, a, K, dv, nd, device):
+    """(lik[nK, nd], hist[nK, nd, n+1] or None) of one K slab on one device:
+    the exact engine, or with -R the simulator."""
+    d = dv if kind == "loss" else None
+    if a.R:
+        with mdp.ScenarioSim(row, kind, m=a.m, p=a.p, d=a.d, device=device) as sim:
+            hist, match = sim.tables(a.e, a.c, K, d, ts=a.b, tdis=a.a, nrep=a.R, seed=a.r, hist=bool(a.H))
+            lik = sim.lik(match, a.R)[0, 0].reshape(K.size, nd)
+        return lik, None if hist is None else hist[0, 0].reshape(K.size, nd, row.size + 1)
+    with mdp.Scenario(row, kind, m=a.m, p=a.p, d=a.d, device=device) as sc:
+        return sc.lik(a.e, a.c, K, d, ts=a.b, tdis=a.a)[0, 0].reshape(K.size, nd), None
+
+
 def _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd):
     """Single-process -g N: the K grid in N contiguous slabs (the MPI
     partition), one thread and scenario engine per slab, the slabs dealt
@@ -93,15 +116,16 @@ def _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd):
     ngpu = max(1, min(ngpu, a.s)) if a.s else 1
     ndev = max(1, mdp.device_count())
     lik = np.zeros((a.s, nd))
+    hist = np.zeros((a.s, nd, row.size + 1), dtype=np.uint64) if a.R and a.H else None
     errs = []
 
     def run(r):
         r0, r1 = mdist.row_slab(r, ngpu, a.s)
         try:
             if r1 > r0:
-                with mdp.Scenario(row, kind, m=a.m, p=a.p, d=a.d, device=r % ndev) as sc:
-                    lik[r0:r1] = sc.lik(a.e, a.c, K[r0:r1], dv if kind == "loss" else None,
-                                        ts=a.b, tdis=a.a)[0, 0].reshape(r1 - r0, nd)
+                lik[r0:r1], h = _slab(mdp, row, kind, a, K[r0:r1], dv, nd, r % ndev)
+                if h is not None:
+                    hist[r0:r1] = h
         except Exception as exc:  # re-raised on the main thread
             errs.append(exc)
 
@@ -113,7 +137,7 @@ def _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd):
         t.join()
     if errs:
         raise errs[0]
-    return lik
+    return lik, hist
 
 
 def main(argv=None) -> int:
@@ -151,6 +175,12 @@ def main(argv=None) -> int:
         sys.stderr.write(f"cannot open {a.i}\n")
         return 1
     n = row.size
+    if a.R and a.H and mpi:
+        sys.stderr.write("midaspom: -H is not available under torchrun (the counts are not gathered)\n")
+        return 1
+    if a.R and int((row == -1).sum()) > 10:
+        sys.stderr.write(f"midaspom: {int((row == -1).sum())} missing patches in the first row: -R takes at most 10\n")
+        return 1
     if kind == "loss":
         out(f"{n} patches\nReading observations from file {a.i}... ")
     out("done\n")
@@ -169,9 +199,11 @@ def main(argv=None) -> int:
     dv = mdp.dgrid(a.v, a.L, a.U) if kind == "loss" else np.zeros(1)
     nd = dv.size
     start = int(time.time())
+    hist = None
+    sim_line = f"Simulated likelihood: {a.R} replicates per grid point, seed {a.r}\n" if a.R else ""
     if not mpi:
-        out("Starting likelihood computation\n")
-        lik = _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd)
+        out("Starting likelihood computation\n" + sim_line)
+        lik, hist = _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd)
         out("end likelihood computation\n")
     else:
         import torch
@@ -185,12 +217,11 @@ def main(argv=None) -> int:
         else:
             dist.init_process_group(backend)
         out(f"Starting parallel likelihood computation process {rank + 1}/{world}\n", all_ranks=True)
+        out(sim_line)
         r0, r1 = mdist.row_slab(rank, world, a.s)
         local_lik = np.zeros((r1 - r0, nd))
         if r1 > r0:
-            with mdp.Scenario(row, kind, m=a.m, p=a.p, d=a.d, device=dev) as sc:
-                local_lik = sc.lik(a.e, a.c, K[r0:r1], dv if kind == "loss" else None,
-                                   ts=a.b, tdis=a.a)[0, 0].reshape(r1 - r0, nd)
+            local_lik, _ = _slab(mdp, row, kind, a, K[r0:r1], dv, nd, dev)
         out(f"end likelihood computation process {rank + 1}/{world}\n", all_ranks=True)
         if not root:
             out(f"Sending data (proc {rank})... ", all_ranks=True)
@@ -210,6 +241,10 @@ def main(argv=None) -> int:
             fe.write("".join(f"{v:.20f}\t" for v in lik[i]))
             if kind == "loss":
                 fe.write("\n")
+    if hist is not None:
+        with open(a.H, "w") as fh:
+            for g in hist.reshape(a.s * nd, n + 1):
+                fh.write("".join(f"{int(v)}\t" for v in g) + "\n")
     out("done\n")
     out(f"Finished. It took  {(int(time.time()) - start) / 60.0:.2f} min\n")
     return 0
