@@ -39,6 +39,7 @@
 #include <string>
 #include <vector>
 
+#include "spom_dev.h"
 #include "spom_engine.h"
 
 namespace {
@@ -72,14 +73,6 @@ __constant__ double c_binom[kMaxDeg + 1][kMaxDeg + 1];
         if ((stamps) && threadIdx.x == 0)                                                 \
             (stamps)[(size_t)(blockIdx.x + gridDim.x * blockIdx.y) * kStampSlots + (slot)] = \
                 __builtin_amdgcn_s_memrealtime();                                         \
-    } while (0)
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr,               \
-                                 hipGetErrorString(e_), __FILE__, __LINE__);              \
     } while (0)
 
 // Kernel timing: while an engine is profiled, every launch of a run carries
@@ -2183,40 +2176,6 @@ __global__ __launch_bounds__(kBlock) void k_fwd_wide(
 // host side
 // ---------------------------------------------------------------------------
 
-template <typename T>
-int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-    if (e != hipSuccess)
-        return mdp_set_error(MDP_ENOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T),
-                             hipGetErrorString(e));
-    return MDP_OK;
-}
-
-template <typename T>
-int dev_upload(T **p, const std::vector<T> &h)
-{
-    int rc = dev_alloc(p, h.size());
-    if (rc) return rc;
-    if (!h.empty()) HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MDP_OK;
-}
-
-template <typename T>
-int dev_reserve(T **p, size_t *cap, size_t count)
-{
-    if (count <= *cap && *p) return MDP_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    int rc = dev_alloc(p, count);
-    if (rc) return rc;
-    *cap = count ? count : 1;
-    return MDP_OK;
-}
-
 constexpr int kNumEv = 6;  // start/stop per kernel: k_zpv, k_coefs, k_forward
 const char *const kKernelNames[3][3] = {{"k_zpv", "k_coefs", "k_forward"},
                                         {"k_zrows", "k_qrows", "k_forward"},
@@ -2307,15 +2266,15 @@ int upload_qrows_tables(const mdp_engine *eng, DevCtx &d, double cmax)
     for (uint32_t js = 0; js < nj; ++js)
         for (size_t k = 0; k < rows[js].size(); ++k) zsT[js * kmax + k] = rows[js][k];
     int rc;
-    if ((rc = dev_reserve(&d.zs, &d.cap_zs, zsT.size()))) return rc;
+    if ((rc = dev_grow(d.zs, d.cap_zs, zsT.size()))) return rc;
     HIP_TRY(hipMemcpy(d.zs, zsT.data(), zsT.size() * sizeof(double), hipMemcpyHostToDevice));
     // k_qrows' copy: row js's product chain q (columns k = q mod 4) contiguous
     std::vector<double> zsq(kmax * nj + 2, 0.0);  // + a double2 k_qrows may read at kmax 0
     for (uint32_t js = 0; js < nj; ++js)
         for (size_t k = 0; k < kmax; ++k) zsq[js * kmax + (k % 4) * (kmax / 4) + k / 4] = zsT[js * kmax + k];
-    if ((rc = dev_reserve(&d.zsq, &d.cap_zsq, zsq.size()))) return rc;
+    if ((rc = dev_grow(d.zsq, d.cap_zsq, zsq.size()))) return rc;
     HIP_TRY(hipMemcpy(d.zsq, zsq.data(), zsq.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = dev_reserve(&d.zc, &d.cap_zc, zc.size()))) return rc;
+    if ((rc = dev_grow(d.zc, d.cap_zc, zc.size()))) return rc;
     HIP_TRY(hipMemcpy(d.zc, zc.data(), zc.size() * sizeof(double), hipMemcpyHostToDevice));
     d.zs_cmax = cmax;
     d.zs_len = (uint32_t)(kmax * nj);
@@ -2348,7 +2307,7 @@ int upload_qrows_tables(const mdp_engine *eng, DevCtx &d, double cmax)
     }
     for (size_t k = 0; k < kmax; ++k)  // zs pairs (k, k+1) of a row adjacent: one ds_read_b128
         for (uint32_t js = 0; js < nj; ++js) img[pl.off_zs + ((k / 2) * nj + js) * 2 + (k & 1)] = zs[k * nj + js];
-    if ((rc = dev_reserve(&d.coltab, &d.cap_coltab, ct))) return rc;
+    if ((rc = dev_grow(d.coltab, d.cap_coltab, ct))) return rc;
     HIP_TRY(hipMemcpy(d.coltab, img.data(), ct * sizeof(double), hipMemcpyHostToDevice));
     d.ct_len = (uint32_t)ct;
     return MDP_OK;
@@ -2399,7 +2358,7 @@ int jit_load(mdp_engine *eng, DevCtx &d, int variant)
             }
             fns.push_back(f);
             uint32_t *qi = nullptr;
-            if (!eng->chunks[i].qidx.empty() && (rc = dev_upload(&qi, eng->chunks[i].qidx))) {
+            if (!eng->chunks[i].qidx.empty() && (rc = dev_upload(qi, eng->chunks[i].qidx))) {
                 unload();
                 return rc;
             }
@@ -2456,14 +2415,15 @@ int init_generic(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
     for (uint32_t b = 0; b < p->nvar; ++b) row_col.push_back(p->var_cols[b]);
     std::vector<double> M(p->M, p->M + (size_t)p->n * p->n);
     double *dM = nullptr;
-    if ((rc = dev_upload(&dM, M))) return rc;
-    if ((rc = dev_upload(&d.var_cols, var)) || (rc = dev_upload(&d.row_col, row_col)) ||
-        (rc = dev_upload(&d.pairA, eng->pairA)) || (rc = dev_upload(&d.pairB, eng->pairB)) ||
-        (rc = dev_upload(&d.pairOff, eng->pairOff)) || (rc = dev_upload(&d.udesc, eng->udesc)) ||
-        (rc = dev_upload(&d.pairPart0, eng->pairPart0)) || (rc = dev_upload(&d.partP, eng->partP)) ||
-        (rc = dev_upload(&d.partK0, eng->partK0)) ||
-        (rc = dev_upload(&d.prog, eng->prog)) ||
-        (rc = dev_alloc(&d.S, (size_t)p->n * eng->nstates))) {
+    size_t cap_S = 0;  // d.S is allocated once
+    if ((rc = dev_upload(dM, M))) return rc;
+    if ((rc = dev_upload(d.var_cols, var)) || (rc = dev_upload(d.row_col, row_col)) ||
+        (rc = dev_upload(d.pairA, eng->pairA)) || (rc = dev_upload(d.pairB, eng->pairB)) ||
+        (rc = dev_upload(d.pairOff, eng->pairOff)) || (rc = dev_upload(d.udesc, eng->udesc)) ||
+        (rc = dev_upload(d.pairPart0, eng->pairPart0)) || (rc = dev_upload(d.partP, eng->partP)) ||
+        (rc = dev_upload(d.partK0, eng->partK0)) ||
+        (rc = dev_upload(d.prog, eng->prog)) ||
+        (rc = dev_grow(d.S, cap_S, (size_t)p->n * eng->nstates))) {
         (void)hipFree(dM);
         return rc;
     }
@@ -2511,33 +2471,33 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
         }
         std::vector<uint32_t> qitem = eng->qitem;
         qitem.push_back(0u);
-        if ((rc = dev_upload(&d.sv, sv)) || (rc = dev_upload(&d.items, items)) ||
-            (rc = dev_upload(&d.qstart, eng->qstart)) || (rc = dev_upload(&d.qitem, qitem)) ||
-            (rc = dev_upload(&d.qslot, eng->qslot)) || (rc = dev_upload(&d.qlane, eng->qlane)) ||
-            (rc = dev_upload(&d.islot, eng->islot)))
+        if ((rc = dev_upload(d.sv, sv)) || (rc = dev_upload(d.items, items)) ||
+            (rc = dev_upload(d.qstart, eng->qstart)) || (rc = dev_upload(d.qitem, qitem)) ||
+            (rc = dev_upload(d.qslot, eng->qslot)) || (rc = dev_upload(d.qlane, eng->qlane)) ||
+            (rc = dev_upload(d.islot, eng->islot)))
             return rc;
         if (eng->wide) {
-            if ((rc = dev_upload(&d.np_d, eng->np)) || (rc = dev_upload(&d.udesc_w, eng->udesc_d))) return rc;
+            if ((rc = dev_upload(d.np_d, eng->np)) || (rc = dev_upload(d.udesc_w, eng->udesc_d))) return rc;
             if (eng->mma &&
-                ((rc = dev_upload(&d.mma_kt, eng->mma_kt)) || (rc = dev_upload(&d.mma_kbase, eng->mma_kbase)) ||
-                 (rc = dev_upload(&d.mma_wplan, eng->mma_wplan)) ||
-                 (rc = dev_upload(&d.mma_desc, eng->mma_desc)) || (rc = dev_upload(&d.mma_dbase, eng->mma_dbase))))
+                ((rc = dev_upload(d.mma_kt, eng->mma_kt)) || (rc = dev_upload(d.mma_kbase, eng->mma_kbase)) ||
+                 (rc = dev_upload(d.mma_wplan, eng->mma_wplan)) ||
+                 (rc = dev_upload(d.mma_desc, eng->mma_desc)) || (rc = dev_upload(d.mma_dbase, eng->mma_dbase))))
                 return rc;
             if (eng->mma)
                 HIP_TRY(hipFuncSetAttribute(mma_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mma_lds(eng)));
             if (eng->mmt &&
-                ((rc = dev_upload(&d.mmt_kt, eng->mmt_kt)) || (rc = dev_upload(&d.mmt_ktile, eng->mmt_ktile)) ||
-                 (rc = dev_upload(&d.mmt_wplan, eng->mmt_wplan)) || (rc = dev_upload(&d.mmt_cidx, eng->mmt_cidx))))
+                ((rc = dev_upload(d.mmt_kt, eng->mmt_kt)) || (rc = dev_upload(d.mmt_ktile, eng->mmt_ktile)) ||
+                 (rc = dev_upload(d.mmt_wplan, eng->mmt_wplan)) || (rc = dev_upload(d.mmt_cidx, eng->mmt_cidx))))
                 return rc;
             if (eng->mmt)
                 HIP_TRY(hipFuncSetAttribute(mmt_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mmt_lds(eng)));
             if (eng->hs &&
-                ((rc = dev_upload(&d.hs_kt, eng->hs_kt)) || (rc = dev_upload(&d.hs_cidx, eng->hs_cidx)) ||
-                 (rc = dev_upload(&d.hs_pbase, eng->hs_pbase)) || (rc = dev_upload(&d.hs_ppos, eng->hs_ppos)) ||
-                 (rc = dev_upload(&d.hs_dpos, eng->hs_dpos)) || (rc = dev_upload(&d.hs_dbase, eng->hs_dbase)) ||
-                 (rc = dev_upload(&d.hs_pk, eng->hs_pk)) ||
-                 (rc = dev_upload(&d.hs_wplan, eng->hs_wplan)) || (rc = dev_upload(&d.hs_pass, eng->hs_pass)) ||
-                 (rc = dev_upload(&d.hs_dpk, eng->hs_dpk))))
+                ((rc = dev_upload(d.hs_kt, eng->hs_kt)) || (rc = dev_upload(d.hs_cidx, eng->hs_cidx)) ||
+                 (rc = dev_upload(d.hs_pbase, eng->hs_pbase)) || (rc = dev_upload(d.hs_ppos, eng->hs_ppos)) ||
+                 (rc = dev_upload(d.hs_dpos, eng->hs_dpos)) || (rc = dev_upload(d.hs_dbase, eng->hs_dbase)) ||
+                 (rc = dev_upload(d.hs_pk, eng->hs_pk)) ||
+                 (rc = dev_upload(d.hs_wplan, eng->hs_wplan)) || (rc = dev_upload(d.hs_pass, eng->hs_pass)) ||
+                 (rc = dev_upload(d.hs_dpk, eng->hs_dpk))))
                 return rc;
             if (eng->hs)
                 HIP_TRY(hipFuncSetAttribute(hs_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_lds(eng)));
@@ -2630,7 +2590,7 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
             return mdp_set_error(MDP_EINVAL, "colonisation rate c[%u] = %g (the engine takes finite c >= 0)", i, c[i]);
     HIP_TRY(hipSetDevice(d.device));
     int rc;
-    if ((rc = dev_reserve(&d.e, &d.cap_e, ne)) || (rc = dev_reserve(&d.c, &d.cap_c, nc))) return rc;
+    if ((rc = dev_grow(d.e, d.cap_e, ne)) || (rc = dev_grow(d.c, d.cap_c, nc))) return rc;
     d.ne_sform = 0;
     for (uint32_t i = 0; i < ne; ++i) {  // the kernels' form test: x = min(e, 1), s-form where x < 1 - x
         const double x = e[i] > 1.0 ? 1.0 : e[i];
@@ -2640,11 +2600,11 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
     if (eng->wide || eng->jit) {
         double cmax = eng->cbound;
         for (uint32_t i = 0; i < nc; ++i) cmax = std::isnan(c[i]) ? c[i] : std::max(cmax, std::fabs(c[i]));
-        if ((rc = dev_reserve(&d.Qrow, &d.cap_qrow, (size_t)nc * eng->ldQ))) return rc;
+        if ((rc = dev_grow(d.Qrow, d.cap_qrow, (size_t)nc * eng->ldQ))) return rc;
         if (!(d.zs_cmax == cmax) && (rc = upload_qrows_tables(eng, d, cmax))) return rc;
     }
     if (qglobal) {
-        if ((rc = dev_reserve(&d.Zg, &d.cap_zg, (size_t)nc * eng->nj + 1))) return rc;
+        if ((rc = dev_grow(d.Zg, d.cap_zg, (size_t)nc * eng->nj + 1))) return rc;
         // k_zrows stages kZRows rows of explicit columns in dynamic LDS
         const size_t zl = (size_t)kZRows * d.zs_kmax * sizeof(double);
         if (zl > kQrowsLdsMax)
@@ -2662,9 +2622,9 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
             d.wide_cb_items = (uint32_t)std::min<size_t>(nc, std::max<size_t>(1, kHsPgBytes / 8 / ldp));
             if (const char *cv = eng->opts.get("MDP_WIDE_CB"))
                 d.wide_cb_items = std::min(d.wide_cb_items, (uint32_t)std::max(1, atoi(cv)));
-            if ((rc = dev_reserve(&d.Pg, &d.cap_pg, (size_t)d.wide_cb_items * ldp))) return rc;
+            if ((rc = dev_grow(d.Pg, d.cap_pg, (size_t)d.wide_cb_items * ldp))) return rc;
             HIP_TRY(hipMemset(d.Pg, 0, (size_t)d.wide_cb_items * ldp * sizeof(double)));
-        } else if ((rc = dev_reserve(&d.Pg, &d.cap_pg, (size_t)d.wide_cb_items * eng->nitems + 1))) {
+        } else if ((rc = dev_grow(d.Pg, d.cap_pg, (size_t)d.wide_cb_items * eng->nitems + 1))) {
             return rc;
         }
     }
@@ -2676,7 +2636,7 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
         d.wide_cb_fwd = (uint32_t)std::min(cap_c, std::max<size_t>(1, kWideVBytes / 8 / (2 * (size_t)eng->npmax * ne_pad)));
         if (const char *cv = eng->opts.get("MDP_WIDE_CB"))
             d.wide_cb_fwd = std::min(d.wide_cb_fwd, (uint32_t)std::max(1, atoi(cv)));
-        if (!eng->mma && !eng->mmt && (rc = dev_reserve(&d.V, &d.cap_v, 2 * (size_t)eng->npmax * d.wide_cb_fwd * ne_pad))) return rc;
+        if (!eng->mma && !eng->mmt && (rc = dev_grow(d.V, d.cap_v, 2 * (size_t)eng->npmax * d.wide_cb_fwd * ne_pad))) return rc;
     } else if (eng->jit) {
         // forward kernels with several points per lane read them from a list
         // that puts only e rows of one ratio form in a lane (spom_jit.cpp)
@@ -2687,12 +2647,12 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
             const std::vector<uint32_t> pl = point_list(e, ne, epl_max);
             for (uint32_t i = 0; i < pl.size() && d.plist_identity; ++i) d.plist_identity = pl[i] == i;
             if (!d.plist_identity) {  // an identity list is not uploaded: the kernels use the position
-                if ((rc = dev_reserve(&d.plist, &d.cap_plist, pl.size()))) return rc;
+                if ((rc = dev_grow(d.plist, d.cap_plist, pl.size()))) return rc;
                 HIP_TRY(hipMemcpy(d.plist, pl.data(), pl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
                 std::vector<double> el(pl.size() + 1);
                 for (size_t i = 0; i < pl.size(); ++i) el[i] = ne ? e[pl[i] & 0x7fffffffu] : 0.0;  // (no rows: never run)
                 el[pl.size()] = ne ? e[0] : 0.0;
-                if ((rc = dev_reserve(&d.elist, &d.cap_elist, el.size()))) return rc;
+                if ((rc = dev_grow(d.elist, d.cap_elist, el.size()))) return rc;
                 HIP_TRY(hipMemcpy(d.elist, el.data(), el.size() * sizeof(double), hipMemcpyHostToDevice));
             }
             d.nlist = (uint32_t)pl.size();
@@ -2725,19 +2685,19 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
             d.ldv = gy * eng->jit_kblock * (uint32_t)eng->jit_epl;
             uint32_t nb = 1;  // most states at a chunk boundary
             for (size_t i = 1; i < eng->chunks.size(); ++i) nb = std::max(nb, eng->chunks[i].np[0]);
-            if ((rc = dev_reserve(&d.vscr, &d.cap_vscr, (size_t)nb * nc * d.ldv))) return rc;
+            if ((rc = dev_grow(d.vscr, d.cap_vscr, (size_t)nb * nc * d.ldv))) return rc;
         }
         // c values per k_qrows workgroup: enough workgroups for every CU, within the LDS
         uint32_t cb = nc >= 1024 ? 4u : nc >= 512 ? 2u : 1u;  // power of two
         cb = std::min(cb, eng->nvar <= 8 ? 4u : eng->nvar <= 16 ? 2u : 1u);  // registers (k_qrows)
         while (cb > 1 && qrows_lds(eng, cb) > kQrowsLdsMax) cb >>= 1;
         d.qrows_cb = cb;
-    } else if ((rc = dev_reserve(&d.ZPV, &d.cap_zpv, (size_t)nc * (eng->nvar + 1) * eng->nstates)) ||
-               (rc = dev_reserve(&d.R, &d.cap_r, (size_t)nc * ldR_of(eng)))) {
+    } else if ((rc = dev_grow(d.ZPV, d.cap_zpv, (size_t)nc * (eng->nvar + 1) * eng->nstates)) ||
+               (rc = dev_grow(d.R, d.cap_r, (size_t)nc * ldR_of(eng)))) {
         return rc;
     }
     if (!eng->jit && !eng->wide && !eng->lds_part &&
-        (rc = dev_reserve(&d.gpart, &d.cap_gpart, (size_t)nc * eng->partP.size() * (eng->nvar + 1))))
+        (rc = dev_grow(d.gpart, d.cap_gpart, (size_t)nc * eng->partP.size() * (eng->nvar + 1))))
         return rc;
     if (eng->diag) {
         d.nst[0] = eng->jit ? (size_t)nc
@@ -2745,7 +2705,7 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
         d.nst[1] = nc;
         d.nst[2] = (size_t)nc * ((ne + kBlock - 1) / kBlock);  // >= the JIT grid (EPL >= 1)
         for (int k = 0; k < 3; ++k) {
-            if ((rc = dev_reserve(&d.stamps[k], &d.cap_st[k], d.nst[k] * kStampSlots))) return rc;
+            if ((rc = dev_grow(d.stamps[k], d.cap_st[k], d.nst[k] * kStampSlots))) return rc;
             HIP_TRY(hipMemset(d.stamps[k], 0, d.cap_st[k] * sizeof(unsigned long long)));
         }
     }
@@ -3297,7 +3257,7 @@ int mdp_loglik_grid_layout(mdp_engine *eng, const double *e, uint32_t ne, const 
         DevCtx &d = eng->devs[r];
         const uint32_t rows = r1[r] - r0[r];
         if ((rc = set_grid_dev(eng, d, e + r0[r], rows, c, nc))) return rc;
-        if ((rc = dev_reserve(&d.out, &d.cap_out, (size_t)rows * nc))) return rc;
+        if ((rc = dev_grow(d.out, d.cap_out, (size_t)rows * nc))) return rc;
         // the layout asked of this call (not the engine's mdp_engine_run
         // layout): the slab [e][c] (ld nc) or [c][e] (ld = the slab's rows)
         if ((rc = run_dev(eng, d, d.out, ce ? OutStrides{1u, rows} : OutStrides{nc, 1u}, d.stream))) return rc;

@@ -53,7 +53,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "mdp_internal.h"
+#include "spom_dev.h"
 #include "spom_future_plan.h"
 
 #pragma clang fp contract(off)
@@ -66,14 +66,6 @@ constexpr int kFutBlock = 256;
 constexpr int kFutMaxWG = 4096;         // grid-stride cap (>= 16 workgroups per CU)
 constexpr uint32_t kFutMaxT = 12288;    // LDS year counters (48 KB; + 16 KB table for n <= 8)
 constexpr uint32_t kLookBack = 1u << 16;
-
-#define FUT_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                        \
-    } while (0)
 
 struct FutArgs {
     uint32_t n, nmiss, tfut, lvalid;
@@ -708,14 +700,6 @@ __global__ __launch_bounds__(256) void k_future_split(const unsigned long long *
     }
 }
 
-template <typename T>
-int dev_up(T **p, const std::vector<T> &h)
-{
-    FUT_TRY(hipMalloc((void **)p, std::max<size_t>(1, h.size()) * sizeof(T)));
-    if (!h.empty()) FUT_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MDP_OK;
-}
-
 }  // namespace
 struct mdp_future {
     int device = 0;
@@ -747,20 +731,6 @@ struct mdp_future {
 };
 
 namespace {
-
-// grow-only device buffer of `need` elements of `elem` bytes; after a failed
-// hipMalloc the pointer is null and the capacity 0
-template <typename T>
-int fut_grow(T *&p, size_t &cap, size_t need, size_t elem)
-{
-    if (need <= cap) return MDP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    FUT_TRY(hipMalloc((void **)&p, need * elem));
-    cap = need;
-    return MDP_OK;
-}
 
 // the one switch over the lane kernels' padded patch count: fn(integral_constant<int, NM>)
 template <typename F>
@@ -810,8 +780,8 @@ int fut_grid(const mdp_future *f, uint64_t nrep)
 
 int fut_reserve(mdp_future *f, int nwg, uint32_t tfut)
 {
-    if (int rc = fut_grow(f->dpartial, f->partial_cap, (size_t)nwg * tfut, sizeof(uint32_t))) return rc;
-    return fut_grow(f->dcounts, f->counts_cap, tfut, sizeof(unsigned long long));
+    if (int rc = dev_grow(f->dpartial, f->partial_cap, (size_t)nwg * tfut, sizeof(uint32_t))) return rc;
+    return dev_grow(f->dcounts, f->counts_cap, tfut, sizeof(unsigned long long));
 }
 
 FutArgs fut_args(const mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut)
@@ -870,7 +840,7 @@ int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, 
             return MDP_OK;
         }))
         return rc;
-    FUT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return MDP_OK;
 }
 
@@ -890,11 +860,11 @@ int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint3
                 return MDP_OK;
             }))
             return rc;
-        FUT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (sum) {
         hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial, (uint32_t)nwg, tfut, d_counts);
-        FUT_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return MDP_OK;
 }
@@ -915,7 +885,7 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
                     hipStream_t st, uint32_t *derr)
 {
     const size_t ncell = (size_t)tfut * (2 * f->n + 1);
-    FUT_TRY(hipMemsetAsync(f->dtab, 0, ncell * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(f->dtab, 0, ncell * sizeof(unsigned long long), st));
     const uint64_t per = fut_per_wg(f);
     const size_t lds = (size_t)p.lds;
     for (uint64_t done = 0; done < nrep; done += p.reps) {
@@ -946,7 +916,7 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
                 });
             }
             if (rc) return rc;
-            FUT_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     return MDP_OK;
@@ -959,12 +929,12 @@ int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan 
     if (!f) return mdp_set_error(MDP_EINVAL, "null future engine");
     if (nrep > (1ull << 62)) return mdp_set_error(MDP_EINVAL, "replicate count too large");
     if (int rc = fut_sum_plan(f->n, f->np, f->wlen, tfut, f->sum_years, p)) return rc;
-    FUT_TRY(hipSetDevice(f->device));
-    if (int rc = fut_grow(f->dtab, f->tab_cap, (size_t)tfut * (2 * f->n + 1), sizeof(unsigned long long))) return rc;
+    HIP_TRY(hipSetDevice(f->device));
+    if (int rc = dev_grow(f->dtab, f->tab_cap, (size_t)tfut * (2 * f->n + 1), sizeof(unsigned long long))) return rc;
     const size_t recs = p->windows > 1 ? (size_t)std::min<uint64_t>(nrep, p->reps) : 0;
-    if (int rc = fut_grow(f->drec_occ, f->rec_occ_cap, recs, f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t)))
+    if (int rc = dev_grow(f->drec_occ, f->rec_occ_cap, recs, f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t)))
         return rc;
-    return fut_grow(f->drec_idx, f->rec_idx_cap, recs, sizeof(uint32_t));
+    return dev_grow(f->drec_idx, f->rec_idx_cap, recs, sizeof(uint32_t));
 }
 
 // the mean time in ms of `reps` runs of launch() on f->stream, after one
@@ -974,13 +944,13 @@ int fut_time(mdp_future *f, int reps, double *ms, F launch)
 {
     int rc;
     if ((rc = launch())) return rc;
-    FUT_TRY(hipEventRecord(f->ev0, f->stream));
+    HIP_TRY(hipEventRecord(f->ev0, f->stream));
     for (int i = 0; i < reps; ++i)
         if ((rc = launch())) return rc;
-    FUT_TRY(hipEventRecord(f->ev1, f->stream));
-    FUT_TRY(hipEventSynchronize(f->ev1));
+    HIP_TRY(hipEventRecord(f->ev1, f->stream));
+    HIP_TRY(hipEventSynchronize(f->ev1));
     float t = 0;
-    FUT_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
+    HIP_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
     *ms = (double)t / reps;
     return MDP_OK;
 }
@@ -992,10 +962,10 @@ int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp
     const int device = f->device;
     if (hipSetDevice(device) != hipSuccess) return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
     int rc;
-    if ((rc = dev_up(&f->dpcum, pp.pcum))) return rc;
+    if ((rc = dev_upload(f->dpcum, pp.pcum))) return rc;
     if (f->np) {
-        if ((rc = dev_up(&f->dimage, wp.image)) || (rc = dev_up(&f->dsrc, wp.src)) ||
-            (rc = dev_up(&f->docc0, wp.occ0)) || (rc = dev_up(&f->dwmiss, wp.miss)))
+        if ((rc = dev_upload(f->dimage, wp.image)) || (rc = dev_upload(f->dsrc, wp.src)) ||
+            (rc = dev_upload(f->docc0, wp.occ0)) || (rc = dev_upload(f->dwmiss, wp.miss)))
             return rc;
         // the image and kFutMaxT year counters pass 64 KB of dynamic LDS; the
         // summary kernel: the image and one window's table
@@ -1012,7 +982,7 @@ int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp
                 return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d%s", f->kname, lds[i], device,
                                      i ? " (summary)" : "");
     } else {
-        if ((rc = dev_up(&f->dMK, lp.MK)) || (rc = dev_up(&f->dsrc, lp.src)) || (rc = dev_up(&f->dmiss, lp.miss)))
+        if ((rc = dev_upload(f->dMK, lp.MK)) || (rc = dev_upload(f->dsrc, lp.src)) || (rc = dev_upload(f->dmiss, lp.miss)))
             return rc;
         if (f->nm == kTabN) {
             if (hipMalloc((void **)&f->dT, sizeof(double) * (kTabN << kTabN)) != hipSuccess)
@@ -1116,18 +1086,18 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
                              "words per call", (unsigned long long)nrep, W, (unsigned long long)kFutStatesMaxWords);
     if (nrep == 0) return MDP_OK;
     if (!words) return mdp_set_error(MDP_EINVAL, "null states");
-    FUT_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipSetDevice(f->device));
     int rc;
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
-    if ((rc = fut_grow(f->dstates, f->states_cap, (size_t)nrep, 64 * sizeof(uint32_t)))) return rc;
-    FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = dev_grow(f->dstates, f->states_cap, (size_t)nrep, 64 * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_launch_wide(f, seed, rep0, nrep, tfut, f->stream, f->dstates, f->derr + 1))) return rc;
     std::vector<uint32_t> lanes((size_t)nrep * 64);
     uint32_t err = 0;
-    FUT_TRY(hipMemcpyAsync(lanes.data(), f->dstates, lanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(lanes.data(), f->dstates, lanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            f->stream));
-    FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
-    FUT_TRY(hipStreamSynchronize(f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     fut_wide_unpack(lanes.data(), nrep, f->n, f->np, words);
     return MDP_OK;
@@ -1165,7 +1135,7 @@ int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint
     int rc = fut_check_args(f, nrep, tfut);
     if (rc) return rc;
     if (!d_counts) return mdp_set_error(MDP_EINVAL, "null device counts");
-    FUT_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     // the look-back overflow flag is sticky: mdp_future_check reads and
@@ -1176,12 +1146,12 @@ int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint
 int mdp_future_check(mdp_future *f, void *stream)
 {
     if (!f) return mdp_set_error(MDP_EINVAL, "null future engine");
-    FUT_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
     uint32_t err = 0;
-    FUT_TRY(hipMemcpyAsync(&err, f->derr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    FUT_TRY(hipMemsetAsync(f->derr, 0, sizeof(uint32_t), st));
-    FUT_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(f->derr, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipStreamSynchronize(st));
     return fut_lookback(err, true);
 }
 
@@ -1191,16 +1161,16 @@ int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nr
     int rc = fut_check_args(f, nrep, tfut);
     if (rc) return rc;
     if (!counts) return mdp_set_error(MDP_EINVAL, "null counts");
-    FUT_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipSetDevice(f->device));
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if (nrep == 0) return MDP_OK;
-    FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
+    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_launch(f, seed, rep0, nrep, tfut, f->dcounts, f->stream, true, f->derr + 1))) return rc;
     std::vector<unsigned long long> h(tfut);
     uint32_t err = 0;
-    FUT_TRY(hipMemcpyAsync(h.data(), f->dcounts, tfut * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
-    FUT_TRY(hipStreamSynchronize(f->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), f->dcounts, tfut * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) counts[t] += h[t];
     return MDP_OK;
@@ -1211,7 +1181,7 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     int rc = fut_check_args(f, nrep, tfut);
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
-    FUT_TRY(hipSetDevice(f->device));
+    HIP_TRY(hipSetDevice(f->device));
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     return fut_time(f, reps, ms, [&]() {
         return fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1);
@@ -1231,7 +1201,7 @@ int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint6
     const uint32_t ncell = tfut * (2 * f->n + 1);
     hipLaunchKernelGGL(k_future_split, dim3((ncell + 255) / 256), dim3(256), 0, st, f->dtab, ncell, f->n,
                        (unsigned long long *)d_hist, (unsigned long long *)d_occ);
-    FUT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return MDP_OK;
 }
 
@@ -1243,14 +1213,14 @@ int mdp_future_summary(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nre
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (nrep == 0) return MDP_OK;
-    FUT_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
+    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, f->stream, f->derr + 1))) return rc;
     const uint32_t n = f->n, cells = 2 * n + 1;
     std::vector<unsigned long long> h((size_t)tfut * cells);
     uint32_t err = 0;
-    FUT_TRY(hipMemcpyAsync(h.data(), f->dtab, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    FUT_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
-    FUT_TRY(hipStreamSynchronize(f->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), f->dtab, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) {
         const unsigned long long *row = h.data() + (size_t)t * cells;

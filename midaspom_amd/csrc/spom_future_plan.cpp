@@ -7,17 +7,15 @@
 #include <cmath>
 #include <string>
 
+#include "spom_opts.h"
+
 int fut_parse_opts(const char *s, FutWideMode *mode, uint32_t *sum_years)
 {
     *mode = kFutWideOff;
     if (sum_years) *sum_years = 0;
     if (!s) return MDP_OK;
-    std::string cur;
-    auto flush = [&]() -> int {
-        if (cur.empty()) return MDP_OK;
-        const size_t eq = cur.find('=');
-        const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string("1") : cur.substr(eq + 1);
-        cur.clear();
+    return mdp_for_each_opt(s, [&](const std::string &k, const std::string &val, bool has) -> int {
+        const std::string v = has ? val : std::string("1");
         if (k == "MDP_FUT_SUM_YEARS") {
             // 1 to 5 decimal digits, at most kFutSumMaxT
             uint32_t y = 0;
@@ -37,17 +35,7 @@ int fut_parse_opts(const char *s, FutWideMode *mode, uint32_t *sum_years)
         else if (v == "1") *mode = kFutWideOn;
         else return mdp_set_error(MDP_EINVAL, "MDP_FUT_WIDE=%s (expected 0, auto or 1)", v.c_str());
         return MDP_OK;
-    };
-    for (const char *c = s;; ++c) {
-        if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
-            const int rc = flush();
-            if (rc) return rc;
-            if (*c == 0) break;
-        } else {
-            cur += *c;
-        }
-    }
-    return MDP_OK;
+    });
 }
 
 int fut_select_kernel(uint32_t n, FutWideMode mode, uint32_t *np)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "spom_engine.h"
+#include "spom_opts.h"
 
 // Engine options (ABI 7, mdp_engine_create_opts): "NAME=VALUE" pairs
 // separated by ';', ',' or white space.  They select among the engine's
@@ -45,12 +46,7 @@ int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build)
 {
     o.kv.clear();
     if (!s) return MDP_OK;
-    std::string cur;
-    auto flush = [&]() -> int {
-        if (cur.empty()) return MDP_OK;
-        const size_t eq = cur.find('=');
-        const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string("1") : cur.substr(eq + 1);
-        cur.clear();
+    return mdp_for_each_opt(s, [&](const std::string &k, const std::string &val, bool has) -> int {
         bool known = false, diag = false;
         for (const char *n : kEngineOptNames) known |= k == n;
         for (const char *n : kDiagOptNames) diag |= k == n;
@@ -58,19 +54,9 @@ int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build)
             return mdp_set_error(MDP_EINVAL, "option %s is measurement-only (libmidaspom_diag.so, -DMDP_DIAG_BUILD)",
                                  k.c_str());
         if (!known && !diag) return mdp_set_error(MDP_EINVAL, "unknown engine option '%s'", k.c_str());
-        o.kv[k] = v;
+        o.kv[k] = has ? val : std::string("1");
         return MDP_OK;
-    };
-    for (const char *c = s;; ++c) {
-        if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
-            const int rc = flush();
-            if (rc) return rc;
-            if (*c == 0) break;
-        } else {
-            cur += *c;
-        }
-    }
-    return MDP_OK;
+    });
 }
 
 namespace {

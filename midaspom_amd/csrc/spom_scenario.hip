@@ -1,7 +1,9 @@
 // midaspom_amd/csrc/spom_scenario.hip -- MI355X engine for the reference's two
 // scenario likelihoods:
-//   in-situ die-off  /root/reference/sources/main_MIDASPOM_dieoff.c:304-351
-//   habitat loss     /root/reference/sources/main_MIDASPOM_loss.c:341-386
+//   in-situ die-off  sources/main_MIDASPOM_dieoff.c:304-351
+//   habitat loss     sources/main_MIDASPOM_loss.c:341-386
+// Kernels, device buffers and launches; the options, refusals, kernel choice,
+// tables and launch lists are the host planner's (spom_scenario_plan.cpp).
 //
 // Both evaluate, for every grid point, L = sum_i sum_s [PK^ts P^tdis]_{i,s}
 // prior_s over the full 2^n state space of the FIRST survey row (s its
@@ -22,41 +24,18 @@
 // read at consecutive addresses.  j rows are processed in popcount groups so
 // every lane of a wave does the same amount of work.  k_scn_v computes v per
 // (c, e) once (shared by every K); k_scn_lik the rest.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
+#include <memory>
 #include <new>
-#include <string>
 #include <vector>
 
-#include "mdp_internal.h"
+#include "spom_dev.h"
+#include "spom_scenario_plan.h"  // the constants shared with the planner, pow3, scn_nl
 
 namespace {
 
-constexpr int kScnBlock = 1024;       // 16 waves: four per SIMD
 constexpr bool kPingPong = kScnBlock <= 768;  // register double-buffering (needs > 128 VGPRs)
 constexpr bool kDppFactors = true;  // hi factors by DPP row broadcast (fma_rowbcast) instead of LDS broadcasts
-constexpr int kE = 32;                 // e values per workgroup (lanes mod 32)
-constexpr int kWaves = kScnBlock / 64;
-constexpr uint32_t kMaxN = 8;          // k_scn: 2 x 2^8 x 32 state values + factor tables in LDS
-constexpr uint32_t kBigMaxN = 16;      // k_scn_big: state vectors in HBM
-constexpr int kBigBlock = 256;
-constexpr size_t kBigScratch = 1ull << 30;  // k_scn_big state-vector scratch per launch (bytes)
-constexpr int kRowBlock = 256;              // k_scn_row: one grid point per workgroup
-constexpr size_t kRowPer = (size_t)1 << 22;  // k_scn_row: points per launch
-constexpr uint32_t kRowMaxN = 12;           // k_scn_row: 2 x 2^n states + 3 n x 256 per-lane values in LDS
-
-#define SCN_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                        \
-    } while (0)
 
 struct ScnArgs {
     uint32_t n, ns, ne, nc, nK, nd;
@@ -67,12 +46,6 @@ struct ScnArgs {
     uint32_t btot;      // doubles of the hi factor table
 };
 
-__host__ __device__ constexpr int pow3(int x)
-{
-    int r = 1;
-    for (; x > 0; --x) r *= 3;
-    return r;
-}
 __host__ __device__ constexpr int popc_c(int x)
 {
     int c = 0;
@@ -698,9 +671,7 @@ __global__ __launch_bounds__(kRowBlock) void k_scn_row(ScnArgs a, const double *
     }
 }
 
-size_t row_lds(uint32_t n) { return (2 * ((size_t)1 << n) + 3 * (size_t)n * kRowBlock) * sizeof(double); }
-
-// instantiation for n patches: NL = min(3, n) lo patches, NH = n - NL
+// instantiation for n patches: NL = scn_nl(n) lo patches, NH = n - NL
 typedef void (*ScnKernel)(ScnArgs, const double *, const double *, const double *, const double *, const double *,
                           const double *, const uint32_t *, const uint32_t *, double *);
 ScnKernel scn_kernel(uint32_t n)
@@ -717,114 +688,49 @@ ScnKernel scn_kernel(uint32_t n)
     default: return nullptr;
     }
 }
-uint32_t scn_nl(uint32_t n) { return n < 3 ? n : 3u; }
-
-template <typename T>
-int dev_up(T **p, const std::vector<T> &h)
-{
-    *p = nullptr;
-    SCN_TRY(hipMalloc((void **)p, std::max<size_t>(1, h.size()) * sizeof(T)));
-    if (!h.empty()) SCN_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MDP_OK;
-}
 
 }  // namespace
 
+// The host side: every decision is the planner's (spom_scenario_plan.cpp);
+// this unit owns the device copies of its tables and launches what it lists.
 struct mdp_scenario {
-    uint32_t n = 0, ns = 0;
-    int kind = 0;  // 0 die-off, 1 habitat loss
-    double m = 400.0, d = 200.0;
+    ScnPlan plan;
+    ScnGrid grid;  // set by mdp_scenario_set_grid
     int device = 0;
-    std::vector<double> S, w;
-    std::vector<uint32_t> boff, jsched;  // hi factor table offsets; per-wave hi-row schedule
-    uint32_t nsched = 0, btot = 0;
     double *dS = nullptr, *dw = nullptr;
-    uint32_t *dboff = nullptr, *djsched = nullptr;
+    uint32_t *dboff = nullptr, *djsched = nullptr, *djord = nullptr;
     hipStream_t stream = nullptr;
-    // grid set by mdp_scenario_set_grid (device resident)
-    int ts = 0, tdis = 0;
-    uint32_t ne = 0, nc = 0, nK = 0, nd = 0;
-    double *de = nullptr, *dc = nullptr, *dK = nullptr, *dsr = nullptr, *dV = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // k_scn_big (n > 8, or MDP_SCN_BIG=1): state-vector scratch, points per launch
-    bool big = false;
-    double *dY = nullptr;
-    uint32_t big_pts = 0;
-    // k_scn_row (8 < n <= 12, or MDP_SCN_ROW=1): rows by decreasing free-patch count
-    bool row = false;
-    uint32_t *djord = nullptr;
-    // MDP_SCN_LAUNCH_PTS: cap on the points per k_scn_big / k_scn_row launch (0: none)
-    size_t launch_pts = 0;
+    // grow-only buffers of the grid: the axes, the source rows, v, k_scn_big's state scratch
+    double *de = nullptr, *dc = nullptr, *dK = nullptr, *dsr = nullptr, *dV = nullptr, *dY = nullptr;
+    size_t e_cap = 0, c_cap = 0, K_cap = 0, sr_cap = 0, V_cap = 0, Y_cap = 0;
 };
 
 namespace {
 
-void scn_free_grid(mdp_scenario *sc)
-{
-    for (double **p : {&sc->de, &sc->dc, &sc->dK, &sc->dsr, &sc->dV, &sc->dY}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    sc->ne = sc->nc = sc->nK = sc->nd = 0;
-}
-
-size_t scn_lds(const mdp_scenario *sc)
-{
-    const uint32_t nl = scn_nl(sc->n), nh = sc->n - nl;
-    const size_t na = (size_t)((pow3((int)nl) + 1) & ~1) << nh;
-    return (2 * ((size_t)sc->ns * kE + (2u << nl)) + na + sc->btot + (1u << nl)) * sizeof(double);
-}
-
 // v = P^tdis w (which = 1), L = 1^T PK^ts v (which = 2) or both (3) on stream st
 int scn_launch(mdp_scenario *sc, double *dout, hipStream_t st, int which)
 {
-    if (sc->row) {
-        for (int mode = 0; mode < 2; ++mode) {
-            if (!(which & (1 << mode))) continue;
-            ScnArgs a{sc->n, sc->ns, sc->ne, sc->nc, sc->nK, sc->nd, mode ? sc->ts : sc->tdis, sc->kind, mode, 0, 0};
-            const double *y0 = mode ? sc->dV : sc->dw;
-            double *o = mode ? dout : sc->dV;
-            const size_t tot = mode ? (size_t)sc->ne * sc->nc * sc->nK * sc->nd : (size_t)sc->nc * sc->ne;
-            // points per launch (grid of < 2^32 threads), or the MDP_SCN_LAUNCH_PTS cap
-            const size_t per = sc->launch_pts ? std::min(sc->launch_pts, kRowPer) : kRowPer;
-            for (size_t p0 = 0; p0 < tot; p0 += per) {  // one workgroup per point
-                const uint32_t nb = (uint32_t)std::min(per, tot - p0);
-                hipLaunchKernelGGL(k_scn_row, dim3(nb), dim3(kRowBlock), row_lds(sc->n), st, a, sc->dS, y0, sc->de,
-                                   sc->dc, sc->dK, sc->dsr, sc->djord, p0, o);
-            }
-            SCN_TRY(hipGetLastError());
-        }
-        return MDP_OK;
-    }
-    if (sc->big) {
-        for (int mode = 0; mode < 2; ++mode) {
-            if (!(which & (1 << mode))) continue;
-            ScnArgs a{sc->n, sc->ns, sc->ne, sc->nc, sc->nK, sc->nd, mode ? sc->ts : sc->tdis, sc->kind, mode, 0, 0};
-            const double *y0 = mode ? sc->dV : sc->dw;
-            double *o = mode ? dout : sc->dV;
-            const size_t tot = mode ? (size_t)sc->ne * sc->nc * sc->nK * sc->nd : (size_t)sc->nc * sc->ne;
-            for (size_t p0 = 0; p0 < tot; p0 += sc->big_pts) {
-                const uint32_t npl = (uint32_t)std::min<size_t>(sc->big_pts, tot - p0);
-                hipLaunchKernelGGL(k_scn_big, dim3(sc->big_pts / kBigBlock), dim3(kBigBlock), 0, st, a, sc->dS, y0,
-                                   sc->de, sc->dc, sc->dK, sc->dsr, p0, npl, sc->dY, o);
-            }
-            SCN_TRY(hipGetLastError());
-        }
-        return MDP_OK;
-    }
-    const uint32_t nchunk = (sc->ne + kE - 1) / kE;
-    ScnKernel fn = scn_kernel(sc->n);
-    const size_t lds = scn_lds(sc);
-    const size_t npt = (size_t)sc->nc * sc->nK * sc->nd;
+    const ScnPlan &p = sc->plan;
+    const ScnGrid &g = sc->grid;
     for (int mode = 0; mode < 2; ++mode) {
         if (!(which & (1 << mode))) continue;
-        ScnArgs a{sc->n, sc->ns, sc->ne, sc->nc, sc->nK, sc->nd, mode ? sc->ts : sc->tdis, sc->kind, mode,
-                  sc->nsched, sc->btot};
+        ScnArgs a{p.n, p.ns, g.ne, g.nc, g.nK, g.nd, mode ? g.ts : g.tdis, p.kind, mode, p.nsched, p.btot};
         const double *y0 = mode ? sc->dV : sc->dw;
         double *o = mode ? dout : sc->dV;
-        void *args[] = {&a, &sc->dS, &y0, &sc->de, &sc->dc, &sc->dK, &sc->dsr, &sc->dboff, &sc->djsched, &o};
-        const uint32_t nb = (uint32_t)(nchunk * (mode ? npt : sc->nc));
-        SCN_TRY(hipLaunchKernel((const void *)fn, dim3(nb), dim3(kScnBlock), args, lds, st));
+        for (const ScnLaunch &l : g.launches[mode]) {
+            if (p.path == kScnRow) {  // one workgroup per point
+                hipLaunchKernelGGL(k_scn_row, dim3(l.nwg), dim3(kRowBlock), p.lds, st, a, sc->dS, y0, sc->de, sc->dc,
+                                   sc->dK, sc->dsr, sc->djord, (size_t)l.p0, o);
+            } else if (p.path == kScnBig) {
+                hipLaunchKernelGGL(k_scn_big, dim3(l.nwg), dim3(kBigBlock), 0, st, a, sc->dS, y0, sc->de, sc->dc,
+                                   sc->dK, sc->dsr, (size_t)l.p0, (uint32_t)l.pts, sc->dY, o);
+            } else {
+                void *args[] = {&a, &sc->dS, &y0, &sc->de, &sc->dc, &sc->dK, &sc->dsr, &sc->dboff, &sc->djsched, &o};
+                HIP_TRY(hipLaunchKernel((const void *)scn_kernel(p.n), dim3(l.nwg), dim3(kScnBlock), args, p.lds, st));
+            }
+        }
+        HIP_TRY(hipGetLastError());
     }
     return MDP_OK;
 }
@@ -832,21 +738,6 @@ int scn_launch(mdp_scenario *sc, double *dout, hipStream_t st, int which)
 }  // namespace
 
 extern "C" {
-
-double mdp_kgrid(uint32_t s, double lo, double hi, double *K)
-{
-    // dieoff.c:284-286 / loss.c:315-317
-    for (uint32_t i = 0; i < s; ++i)
-        K[i] = pow(10.0, ((double)i) / (s - 1) * (log10(hi) - log10(lo)) + log10(lo));
-    return s ? K[0] : 0.0;
-}
-
-double mdp_dgrid(uint32_t s, double lo, double hi, double *dv)
-{
-    // loss.c:319-322
-    for (uint32_t i = 0; i < s; ++i) dv[i] = i * (hi - lo) / (s - 1) + lo;
-    return s ? dv[0] : 0.0;
-}
 
 int mdp_device_count(void)
 {
@@ -860,6 +751,20 @@ int mdp_scenario_create(const int32_t *row, uint32_t n, double m, float p, doubl
     return mdp_scenario_create_opts(row, n, m, p, d, kind, device, nullptr, out);
 }
 
+void mdp_scenario_destroy(mdp_scenario *sc)
+{
+    if (!sc) return;
+    (void)hipSetDevice(sc->device);
+    if (sc->stream) (void)hipStreamSynchronize(sc->stream);
+    for (void *p : {(void *)sc->dS, (void *)sc->dw, (void *)sc->dboff, (void *)sc->djsched, (void *)sc->djord,
+                    (void *)sc->de, (void *)sc->dc, (void *)sc->dK, (void *)sc->dsr, (void *)sc->dV, (void *)sc->dY})
+        if (p) (void)hipFree(p);
+    if (sc->ev0) (void)hipEventDestroy(sc->ev0);
+    if (sc->ev1) (void)hipEventDestroy(sc->ev1);
+    if (sc->stream) (void)hipStreamDestroy(sc->stream);
+    delete sc;
+}
+
 // options (ABI 7): "MDP_SCN_BIG=1" / "MDP_SCN_ROW=1" force the HBM-state or
 // the row-parallel kernel (tests pin the kernels against each other);
 // "MDP_SCN_LAUNCH_PTS=N" caps the grid points per launch of those two kernels
@@ -870,252 +775,86 @@ int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, 
 {
     if (!row || !out || n == 0) return mdp_set_error(MDP_EINVAL, "null argument");
     *out = nullptr;
-    bool force_big = false, force_row = false;
-    long launch_pts = 0;
-    if (options) {
-        std::string cur;
-        for (const char *c = options;; ++c) {
-            if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
-                if (!cur.empty()) {
-                    const size_t eq = cur.find('=');
-                    const std::string k = cur.substr(0, eq);
-                    const bool on = eq == std::string::npos || atoi(cur.c_str() + eq + 1) != 0;
-                    if (k == "MDP_SCN_BIG") force_big = on;
-                    else if (k == "MDP_SCN_ROW") force_row = on;
-                    else if (k == "MDP_SCN_LAUNCH_PTS")
-                        launch_pts = eq == std::string::npos ? 0 : atol(cur.c_str() + eq + 1);
-                    else return mdp_set_error(MDP_EINVAL, "unknown scenario option '%s'", k.c_str());
-                    cur.clear();
-                }
-                if (*c == 0) break;
-            } else {
-                cur += *c;
-            }
-        }
-    }
-    if (n > kBigMaxN)
-        return mdp_set_error(MDP_EUNSUPPORTED, "%u patches: the scenario engine takes n <= %u (2^n states)", n,
-                             kBigMaxN);
-    for (uint32_t j = 0; j < n; ++j)
-        if (row[j] < -1 || row[j] > 1) return mdp_set_error(MDP_EINVAL, "observation %d not in {-1,0,1}", row[j]);
+    ScnOpts opts;
+    if (int rc = scn_parse_opts(options, &opts)) return rc;
+    ScnPlan plan;
+    if (int rc = scn_plan(row, n, m, p, d, kind, opts, &plan)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
     if (device < 0 || device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", device);
-    mdp_scenario *sc = new (std::nothrow) mdp_scenario();
+    HIP_TRY(hipSetDevice(device));
+    struct Del {
+        void operator()(mdp_scenario *s) const { mdp_scenario_destroy(s); }
+    };
+    std::unique_ptr<mdp_scenario, Del> sc(new (std::nothrow) mdp_scenario());
     if (!sc) return mdp_set_error(MDP_ENOMEM, "out of host memory");
-    sc->n = n;
-    sc->ns = 1u << n;
-    sc->kind = kind;
-    sc->m = m;
-    sc->d = d;
     sc->device = device;
-    sc->launch_pts = launch_pts > 0 ? std::min((size_t)launch_pts, (size_t)1 << 32) : 0;
-    // n > 8: the LDS-resident k_scn does not fit; 8 < n <= 12: k_scn_row
-    // (option MDP_SCN_ROW=1 forces it for any n <= 12); n > 12: k_scn_big
-    // (MDP_SCN_BIG=1 forces it for any n)
-    sc->row = !force_big && n <= kRowMaxN && (n > kMaxN || force_row);
-    sc->big = !sc->row && (n > kMaxN || force_big);
-    const uint32_t ns = sc->ns;
-    // dispersal M (dieoff.c:238-248) and colonisation sums S[j][k] =
-    // sum over l != k, ascending, of M[l][k] * j_l (dieoff.c:72-77)
-    std::vector<double> M((size_t)n * n, 0.0);
-    const double a = 1.0 / m;
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t j = i + 1; j < n; ++j) M[i * n + j] = M[j * n + i] = exp(-a * (double)(j - i) * d);
-    sc->S.assign((size_t)ns * n, 0.0);
-    for (uint32_t j = 0; j < ns; ++j)
-        for (uint32_t k = 0; k < n; ++k) {
-            double s1 = 0;
-            for (uint32_t l = 0; l < n; ++l)
-                if (l != k) s1 += M[l * n + k] * (double)((j >> (n - 1 - l)) & 1u);
-            sc->S[(size_t)j * n + k] = s1;
-        }
-    // observed first-row states and float priors (dieoff.c:198-232):
-    // w[s] = prior of s
-    sc->w.assign(ns, 0.0);
-    {
-        uint32_t nm = 0;
-        for (uint32_t j = 0; j < n; ++j) nm += row[j] == -1;
-        const uint32_t np = 1u << nm;
-        std::vector<uint32_t> ps(np, 0);
-        std::vector<float> pr(np, 1.0f);
-        uint32_t s1 = 0;
-        for (uint32_t j = 0; j < n; ++j) {
-            if (row[j] == -1) s1++;
-            for (uint32_t k = 0; k < np; ++k) {
-                if (row[j] > -1) {
-                    ps[k] += (uint32_t)row[j] << (n - j - 1);
-                } else {
-                    const uint32_t st1 = np >> s1, bitv = k / st1 % 2;
-                    ps[k] += bitv << (n - j - 1);
-                    pr[k] *= (float)bitv * p + (float)(1 - bitv) * (1 - p);
-                }
-            }
-        }
-        for (uint32_t k = 0; k < np; ++k) sc->w[ps[k]] += (double)pr[k];
-    }
-    // hi factor table offsets (rows jh ascending, 2^(NH-|jh|) supersets x
-    // 2^NL lo rows each) and the hi-row schedule: rows dealt to the waves by
-    // longest-processing-time-first (row jh costs its 2^(f-1) superset
-    // pairs, f = NH - |jh|, plus one for its loads and epilogue)
-    std::vector<uint32_t> jord;
-    if (sc->row) {  // rows by decreasing free-patch count (stable: ascending j within a count)
-        jord.resize(ns);
-        for (uint32_t j = 0; j < ns; ++j) jord[j] = j;
-        std::stable_sort(jord.begin(), jord.end(),
-                         [](uint32_t x, uint32_t y) { return __builtin_popcount(x) < __builtin_popcount(y); });
-    }
-    if (!sc->big && !sc->row) {
-        const uint32_t nl = scn_nl(n), nh = n - nl, nhi = 1u << nh;
-        sc->boff.assign(nhi, 0);
-        uint32_t off = 0;
-        for (uint32_t jh = 0; jh < nhi; ++jh) {
-            sc->boff[jh] = off;
-            off += (1u << (nh - __builtin_popcount(jh))) << nl;
-        }
-        sc->btot = off;
-        std::vector<uint32_t> rows(nhi);
-        for (uint32_t jh = 0; jh < nhi; ++jh) rows[jh] = jh;
-        auto cost = [&](uint32_t jh) {
-            const uint32_t f = nh - __builtin_popcount(jh);
-            return (f ? 1u << (f - 1) : 1u) + 1u;
-        };
-        std::stable_sort(rows.begin(), rows.end(), [&](uint32_t x, uint32_t y) { return cost(x) > cost(y); });
-        std::vector<std::vector<uint32_t>> grp(kWaves);
-        std::vector<uint64_t> load(kWaves, 0);
-        for (uint32_t jh : rows) {
-            const size_t g = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-            grp[g].push_back(jh);
-            load[g] += cost(jh);
-        }
-        size_t mx = 0;
-        for (auto &v : grp) mx = std::max(mx, v.size());
-        sc->nsched = (uint32_t)mx;
-        sc->jsched.assign(mx * kWaves, 0xffffffffu);
-        for (uint32_t g = 0; g < (uint32_t)kWaves; ++g)
-            for (size_t i = 0; i < grp[g].size(); ++i) sc->jsched[g * mx + i] = grp[g][i];
-    }
+    sc->plan = std::move(plan);
+    const ScnPlan &pl = sc->plan;
     int rc;
-    if (hipSetDevice(device) != hipSuccess) {
-        delete sc;
-        return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
-    }
-    if ((rc = dev_up(&sc->dS, sc->S)) || (rc = dev_up(&sc->dw, sc->w)) || (rc = dev_up(&sc->dboff, sc->boff)) ||
-        (rc = dev_up(&sc->djsched, sc->jsched)) || (rc = dev_up(&sc->djord, jord)) ||
-        hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking) != hipSuccess) {
-        mdp_scenario_destroy(sc);
-        return rc ? rc : mdp_set_error(MDP_EHIP, "stream creation failed");
-    }
-    if (sc->row) {
-        if (row_lds(n) > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)k_scn_row, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)row_lds(n));
-    } else if (!sc->big) {
-        const size_t lds = scn_lds(sc);
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)scn_kernel(n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    *out = sc;
+    if ((rc = dev_upload(sc->dS, pl.S)) || (rc = dev_upload(sc->dw, pl.w)) || (rc = dev_upload(sc->dboff, pl.boff)) ||
+        (rc = dev_upload(sc->djsched, pl.jsched)) || (rc = dev_upload(sc->djord, pl.jord)))
+        return rc;
+    HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+    if (pl.lds > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(pl.path == kScnRow ? (const void *)k_scn_row : (const void *)scn_kernel(n),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+    *out = sc.release();
     return MDP_OK;
-}
-
-void mdp_scenario_destroy(mdp_scenario *sc)
-{
-    if (!sc) return;
-    (void)hipSetDevice(sc->device);
-    if (sc->stream) (void)hipStreamSynchronize(sc->stream);
-    scn_free_grid(sc);
-    for (void *p : {(void *)sc->dS, (void *)sc->dw, (void *)sc->dboff, (void *)sc->djsched, (void *)sc->djord})
-        if (p) (void)hipFree(p);
-    if (sc->ev0) (void)hipEventDestroy(sc->ev0);
-    if (sc->ev1) (void)hipEventDestroy(sc->ev1);
-    if (sc->stream) (void)hipStreamDestroy(sc->stream);
-    delete sc;
 }
 
 int mdp_scenario_set_grid(mdp_scenario *sc, int ts, int tdis, const double *e, uint32_t ne, const double *c,
                           uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd)
 {
-    if (!sc || (ne && !e) || (nc && !c) || (nK && !K)) return mdp_set_error(MDP_EINVAL, "null argument");
-    if (ts < 0 || tdis < 0) return mdp_set_error(MDP_EINVAL, "negative number of years");
-    if (sc->kind == 1) {
-        if (nd && !dsrc) return mdp_set_error(MDP_EINVAL, "null source distances");
-    } else {
-        nd = 1;
-    }
-    SCN_TRY(hipSetDevice(sc->device));
-    SCN_TRY(hipStreamSynchronize(sc->stream));
-    scn_free_grid(sc);
-    sc->ts = ts, sc->tdis = tdis;
-    if (!ne || !nc || !nK || !nd) return MDP_OK;
-    const uint32_t n = sc->n, ns = sc->ns;
-    const uint32_t nchunk = (ne + kE - 1) / kE;
-    if ((size_t)nchunk * nc * nK * nd > 0x7fffffffull)
-        return mdp_set_error(MDP_EUNSUPPORTED, "grid of %zu points too large", (size_t)ne * nc * nK * nd);
-    // source terms M[n][k] = exp(-a (k+1) dsrc), loss.c:365
-    std::vector<double> src((size_t)nd * n, 0.0);
-    if (sc->kind == 1)
-        for (uint32_t id = 0; id < nd; ++id)
-            for (uint32_t k = 0; k < n; ++k) src[(size_t)id * n + k] = exp(-(1.0 / sc->m) * (k + 1) * dsrc[id]);
-    if (hipMalloc((void **)&sc->de, ne * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&sc->dc, nc * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&sc->dK, nK * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&sc->dsr, std::max<size_t>(1, src.size()) * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&sc->dV, (size_t)nc * ns * ne * sizeof(double)) != hipSuccess) {
-        scn_free_grid(sc);
-        return mdp_set_error(MDP_ENOMEM, "device allocation failed");
-    }
-    if (sc->big) {  // points per k_scn_big launch: two state vectors each within kBigScratch
-        const size_t tot = std::max((size_t)ne * nc * nK * nd, (size_t)nc * ne);
-        size_t pts = kBigScratch / (2 * (size_t)ns * sizeof(double));
-        pts = std::max<size_t>(kBigBlock, std::min(pts, tot + kBigBlock - 1) / kBigBlock * kBigBlock);
-        if (sc->launch_pts)  // the cap, rounded up to whole blocks
-            pts = std::min(pts, (sc->launch_pts + kBigBlock - 1) / kBigBlock * kBigBlock);
-        sc->big_pts = (uint32_t)std::min<size_t>(pts, (size_t)65535 * kBigBlock);
-        if (hipMalloc((void **)&sc->dY, 2 * (size_t)ns * sc->big_pts * sizeof(double)) != hipSuccess) {
-            scn_free_grid(sc);
-            return mdp_set_error(MDP_ENOMEM, "device allocation failed (state scratch)");
-        }
-    }
-    if (hipMemcpy(sc->de, e, ne * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(sc->dc, c, nc * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(sc->dK, K, nK * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        (!src.empty() &&
-         hipMemcpy(sc->dsr, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) {
-        scn_free_grid(sc);
-        return mdp_set_error(MDP_EHIP, "upload failed");
-    }
-    sc->ne = ne, sc->nc = nc, sc->nK = nK, sc->nd = nd;
+    if (!sc) return mdp_set_error(MDP_EINVAL, "null argument");
+    ScnGrid g;
+    if (int rc = scn_grid_plan(sc->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, &g)) return rc;
+    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipStreamSynchronize(sc->stream));  // no launch still reads the buffers
+    sc->grid = ScnGrid();  // no grid until this one is whole
+    sc->grid.ts = ts, sc->grid.tdis = tdis;
+    if (!g.ne) return MDP_OK;
+    auto put = [](double *&p, size_t &cap, const double *h, size_t count) -> int {
+        if (int rc = dev_grow(p, cap, count)) return rc;
+        if (count) HIP_TRY(hipMemcpy(p, h, count * sizeof(double), hipMemcpyHostToDevice));
+        return MDP_OK;
+    };
+    int rc;
+    if ((rc = put(sc->de, sc->e_cap, e, g.ne)) || (rc = put(sc->dc, sc->c_cap, c, g.nc)) ||
+        (rc = put(sc->dK, sc->K_cap, K, g.nK)) || (rc = put(sc->dsr, sc->sr_cap, g.src.data(), g.src.size())) ||
+        (rc = dev_grow(sc->dV, sc->V_cap, g.nV)) || (g.nY && (rc = dev_grow(sc->dY, sc->Y_cap, g.nY))))
+        return rc;
+    sc->grid = std::move(g);
     return MDP_OK;
 }
 
 int mdp_scenario_run(mdp_scenario *sc, double *d_out, void *stream)
 {
     if (!sc) return mdp_set_error(MDP_EINVAL, "null scenario");
-    if (!sc->ne) return MDP_OK;
+    if (!sc->grid.ne) return MDP_OK;
     if (!d_out) return mdp_set_error(MDP_EINVAL, "null device output");
-    SCN_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->device));
     return scn_launch(sc, d_out, (hipStream_t)stream, 3);
 }
 
 int mdp_scenario_time_kernels(mdp_scenario *sc, double *d_out, void *stream, int reps, double *ms)
 {
     if (!sc || !ms || reps <= 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
-    if (!sc->ne) return mdp_set_error(MDP_EINVAL, "no grid set");
-    SCN_TRY(hipSetDevice(sc->device));
+    if (!sc->grid.ne) return mdp_set_error(MDP_EINVAL, "no grid set");
+    HIP_TRY(hipSetDevice(sc->device));
     hipStream_t st = (hipStream_t)stream;
-    if (!sc->ev0) SCN_TRY(hipEventCreate(&sc->ev0));
-    if (!sc->ev1) SCN_TRY(hipEventCreate(&sc->ev1));
+    if (!sc->ev0) HIP_TRY(hipEventCreate(&sc->ev0));
+    if (!sc->ev1) HIP_TRY(hipEventCreate(&sc->ev1));
     int rc = scn_launch(sc, d_out, st, 3);
     if (rc) return rc;
     for (int which = 1; which <= 2; ++which) {
-        SCN_TRY(hipEventRecord(sc->ev0, st));
+        HIP_TRY(hipEventRecord(sc->ev0, st));
         for (int i = 0; i < reps; ++i)
             if ((rc = scn_launch(sc, d_out, st, which))) return rc;
-        SCN_TRY(hipEventRecord(sc->ev1, st));
-        SCN_TRY(hipEventSynchronize(sc->ev1));
+        HIP_TRY(hipEventRecord(sc->ev1, st));
+        HIP_TRY(hipEventSynchronize(sc->ev1));
         float t = 0;
-        SCN_TRY(hipEventElapsedTime(&t, sc->ev0, sc->ev1));
+        HIP_TRY(hipEventElapsedTime(&t, sc->ev0, sc->ev1));
         ms[which - 1] = (double)t / reps;
     }
     return MDP_OK;
@@ -1126,8 +865,9 @@ int mdp_scenario_lik(mdp_scenario *sc, int ts, int tdis, const double *e, uint32
 {
     if (!sc || !out) return mdp_set_error(MDP_EINVAL, "null argument");
     int rc = mdp_scenario_set_grid(sc, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd);
-    if (rc || !sc->ne) return rc;
-    const size_t npts = (size_t)sc->ne * sc->nc * sc->nK * sc->nd;
+    if (rc || !sc->grid.ne) return rc;
+    const ScnGrid &g = sc->grid;
+    const size_t npts = (size_t)g.ne * g.nc * g.nK * g.nd;
     double *dout = nullptr;
     if (hipMalloc((void **)&dout, npts * sizeof(double)) != hipSuccess)
         return mdp_set_error(MDP_ENOMEM, "device allocation failed");

@@ -41,7 +41,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "mdp_internal.h"
+#include "spom_dev.h"
 #include "spom_scnsim_plan.h"
 
 #pragma clang fp contract(off)
@@ -49,14 +49,6 @@
 #include "spom_rng.h"
 
 namespace {
-
-#define SIM_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                \
-            return mdp_set_error(MDP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                        \
-    } while (0)
 
 constexpr int kTabN = 8;  // k_scnsim<8>: survivor-sum table of the unscaled M in LDS
 
@@ -236,18 +228,6 @@ struct mdp_scenario_sim {
 
 namespace {
 
-template <typename T>
-int sim_grow(T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return MDP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    SIM_TRY(hipMalloc((void **)&p, need * sizeof(T)));
-    cap = need;
-    return MDP_OK;
-}
-
 // the one switch over the padded patch count: fn(integral_constant<int, NM>)
 template <typename F>
 int sim_for_nm(uint32_t nm, F &&fn)
@@ -265,27 +245,21 @@ int sim_for_nm(uint32_t nm, F &&fn)
 int sim_device(mdp_scenario_sim *s)
 {
     if (s->ready) {
-        SIM_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipSetDevice(s->device));
         return MDP_OK;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
     if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
-    SIM_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     s->touched = true;
-    if (!s->dM) {
-        SIM_TRY(hipMalloc((void **)&s->dM, s->plan.M.size() * sizeof(double)));
-        SIM_TRY(hipMemcpy(s->dM, s->plan.M.data(), s->plan.M.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    if (!s->dmiss) {
-        SIM_TRY(hipMalloc((void **)&s->dmiss, std::max<size_t>(1, s->plan.miss.size()) * sizeof(uint32_t)));
-        if (!s->plan.miss.empty())
-            SIM_TRY(hipMemcpy(s->dmiss, s->plan.miss.data(), s->plan.miss.size() * sizeof(uint32_t),
-                              hipMemcpyHostToDevice));
-    }
-    if (!s->stream) SIM_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->ev0) SIM_TRY(hipEventCreate(&s->ev0));
-    if (!s->ev1) SIM_TRY(hipEventCreate(&s->ev1));
+    if (!s->dM)
+        if (int rc = dev_upload(s->dM, s->plan.M)) return rc;
+    if (!s->dmiss)
+        if (int rc = dev_upload(s->dmiss, s->plan.miss)) return rc;
+    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
+    if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
     s->ready = true;
     return MDP_OK;
 }
@@ -308,9 +282,9 @@ int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
     h.insert(h.end(), gr.c, gr.c + gr.nc);
     h.insert(h.end(), gr.K, gr.K + gr.nK);
     h.insert(h.end(), src.begin(), src.end());
-    SIM_TRY(hipStreamSynchronize(st));
-    if (int rc = sim_grow(s->dgrid, s->grid_cap, h.size())) return rc;
-    SIM_TRY(hipMemcpy(s->dgrid, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = dev_grow(s->dgrid, s->grid_cap, h.size())) return rc;
+    HIP_TRY(hipMemcpy(s->dgrid, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     return MDP_OK;
 }
 
@@ -347,7 +321,7 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
                 return MDP_OK;
             }))
             return rc;
-        SIM_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return MDP_OK;
 }
@@ -408,8 +382,8 @@ int mdp_scenario_sim_tables_device(mdp_scenario_sim *s, int ts, int tdis, const 
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
     const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
     if (int rc = sim_upload(s, gr, st)) return rc;
-    if (d_hist) SIM_TRY(hipMemsetAsync(d_hist, 0, call.hist_cells * sizeof(uint64_t), st));
-    if (d_match) SIM_TRY(hipMemsetAsync(d_match, 0, call.match_cells * sizeof(uint64_t), st));
+    if (d_hist) HIP_TRY(hipMemsetAsync(d_hist, 0, call.hist_cells * sizeof(uint64_t), st));
+    if (d_match) HIP_TRY(hipMemsetAsync(d_match, 0, call.match_cells * sizeof(uint64_t), st));
     return sim_launch(s, call, gr, seed, rep0, nrep, (unsigned long long *)d_hist, (unsigned long long *)d_match, st);
 }
 
@@ -425,19 +399,19 @@ int mdp_scenario_sim_tables(mdp_scenario_sim *s, int ts, int tdis, const double 
     if (nrep == 0) return MDP_OK;
     if (int rc = sim_device(s)) return rc;
     if (hist)
-        if (int rc = sim_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+        if (int rc = dev_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
     if (match)
-        if (int rc = sim_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+        if (int rc = dev_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
     int rc = mdp_scenario_sim_tables_device(s, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, seed, rep0, nrep,
                                             hist ? (uint64_t *)s->dhist : nullptr,
                                             match ? (uint64_t *)s->dmatch : nullptr, s->stream);
     if (rc) return rc;
     std::vector<uint64_t> hh(hist ? (size_t)call.hist_cells : 0), hm(match ? (size_t)call.match_cells : 0);
     if (hist)
-        SIM_TRY(hipMemcpyAsync(hh.data(), s->dhist, hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(hh.data(), s->dhist, hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     if (match)
-        SIM_TRY(hipMemcpyAsync(hm.data(), s->dmatch, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-    SIM_TRY(hipStreamSynchronize(s->stream));
+        HIP_TRY(hipMemcpyAsync(hm.data(), s->dmatch, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     for (size_t i = 0; i < hh.size(); ++i) hist[i] += hh[i];
     for (size_t i = 0; i < hm.size(); ++i) match[i] += hm[i];
     return MDP_OK;
@@ -459,24 +433,24 @@ int mdp_scenario_sim_time_kernel(mdp_scenario_sim *s, int ts, int tdis, const do
     if (int rc = sim_call(s->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, nrep, true, want_match, &call)) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     if (int rc = sim_device(s)) return rc;
-    if (int rc = sim_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+    if (int rc = dev_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
     if (want_match)
-        if (int rc = sim_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+        if (int rc = dev_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
     const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
     if (int rc = sim_upload(s, gr, s->stream)) return rc;
-    SIM_TRY(hipMemsetAsync(s->dhist, 0, call.hist_cells * sizeof(uint64_t), s->stream));
-    if (want_match) SIM_TRY(hipMemsetAsync(s->dmatch, 0, call.match_cells * sizeof(uint64_t), s->stream));
+    HIP_TRY(hipMemsetAsync(s->dhist, 0, call.hist_cells * sizeof(uint64_t), s->stream));
+    if (want_match) HIP_TRY(hipMemsetAsync(s->dmatch, 0, call.match_cells * sizeof(uint64_t), s->stream));
     auto launch = [&]() {
         return sim_launch(s, call, gr, seed, 0, nrep, s->dhist, want_match ? s->dmatch : nullptr, s->stream);
     };
     if (int rc = launch()) return rc;  // warm-up
-    SIM_TRY(hipEventRecord(s->ev0, s->stream));
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
     for (int i = 0; i < reps; ++i)
         if (int rc = launch()) return rc;
-    SIM_TRY(hipEventRecord(s->ev1, s->stream));
-    SIM_TRY(hipEventSynchronize(s->ev1));
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipEventSynchronize(s->ev1));
     float t = 0;
-    SIM_TRY(hipEventElapsedTime(&t, s->ev0, s->ev1));
+    HIP_TRY(hipEventElapsedTime(&t, s->ev0, s->ev1));
     *ms = (double)t / reps;
     return MDP_OK;
 }

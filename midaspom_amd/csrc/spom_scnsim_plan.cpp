@@ -8,6 +8,9 @@
 #include <cmath>
 #include <string>
 
+#include "spom_opts.h"
+#include "spom_scn_row.h"
+
 namespace {
 
 // 1 to 19 decimal digits
@@ -28,13 +31,7 @@ bool sim_decimal(const std::string &v, uint64_t *out)
 int sim_parse_opts(const char *s, SimOpts *o)
 {
     *o = SimOpts();
-    if (!s) return MDP_OK;
-    std::string cur;
-    auto flush = [&]() -> int {
-        if (cur.empty()) return MDP_OK;
-        const size_t eq = cur.find('=');
-        const std::string k = cur.substr(0, eq), v = eq == std::string::npos ? std::string() : cur.substr(eq + 1);
-        cur.clear();
+    return mdp_for_each_opt(s, [&](const std::string &k, const std::string &v, bool) -> int {
         uint64_t x = 0;
         if (k == "MDP_SIM_NM") {
             if (!sim_decimal(v, &x) || (x != 8 && x != 16 && x != 32 && x != 64))
@@ -49,17 +46,7 @@ int sim_parse_opts(const char *s, SimOpts *o)
             return MDP_OK;
         }
         return mdp_set_error(MDP_EINVAL, "unknown scenario simulation option '%s'", k.c_str());
-    };
-    for (const char *c = s;; ++c) {
-        if (*c == 0 || *c == ';' || *c == ',' || *c == ' ' || *c == '\t' || *c == '\n') {
-            const int rc = flush();
-            if (rc) return rc;
-            if (*c == 0) break;
-        } else {
-            cur += *c;
-        }
-    }
-    return MDP_OK;
+    });
 }
 
 int sim_plan(const int32_t *row, uint32_t n, double m, float p, double d, int kind, const SimOpts &opts,
@@ -69,8 +56,7 @@ int sim_plan(const int32_t *row, uint32_t n, double m, float p, double d, int ki
     if (kind != 0 && kind != 1) return mdp_set_error(MDP_EINVAL, "scenario kind %d (expected 0 or 1)", kind);
     if (n > kSimMaxN)
         return mdp_set_error(MDP_EUNSUPPORTED, "%u patches: the scenario simulator holds <= %u", n, kSimMaxN);
-    for (uint32_t j = 0; j < n; ++j)
-        if (row[j] < -1 || row[j] > 1) return mdp_set_error(MDP_EINVAL, "observation %d not in {-1,0,1}", row[j]);
+    if (int rc = scn_check_row(row, n)) return rc;
     if (!(m > 0) && !(m < 0)) return mdp_set_error(MDP_EINVAL, "mean dispersal -m must be non-zero");
     if (opts.nm && opts.nm < sim_nm(n))
         return mdp_set_error(MDP_EINVAL, "MDP_SIM_NM=%u is smaller than the k_scnsim<%u> that %u patches need", opts.nm,
@@ -88,35 +74,18 @@ int sim_plan(const int32_t *row, uint32_t n, double m, float p, double d, int ki
         else if (row[j] == -1) s.missmask |= 1ull << j, s.miss.push_back(j);
     }
     s.nmiss = (uint32_t)s.miss.size();
-    // dispersal (dieoff.c:238-248), as the scenario engine forms it, unscaled
-    const double a = 1.0 / m;
+    // dispersal, unscaled, and the float priors of the completions: the
+    // scenario engine's own (spom_scn_row.h)
     s.M.assign((size_t)s.nm * s.nm, 0.0);
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t j = i + 1; j < n; ++j)
-            s.M[(size_t)i * s.nm + j] = s.M[(size_t)j * s.nm + i] = exp(-a * (double)(j - i) * d);
-    // float priors of the completions (dieoff.c:205-232): completion k holds
-    // the q-th missing patch in bit nmiss-1-q
-    if (s.nmiss <= kSimMaxMatchMissing) {
-        const uint32_t np = 1u << s.nmiss;
-        s.prior.assign(np, 1.0f);
-        for (uint32_t q = 0; q < s.nmiss; ++q) {
-            const uint32_t st1 = np >> (q + 1);
-            for (uint32_t k = 0; k < np; ++k) {
-                const uint32_t bitv = k / st1 % 2;
-                s.prior[k] *= (float)bitv * p + (float)(1 - bitv) * (1 - p);
-            }
-        }
-    }
+    scn_dispersal(n, m, d, s.nm, s.M.data());
+    if (s.nmiss <= kSimMaxMatchMissing) scn_priors(s.nmiss, p, &s.prior);
     return MDP_OK;
 }
 
 void sim_src(const SimPlan &plan, const double *dsrc, uint32_t nd, std::vector<double> *src)
 {
     src->assign((size_t)nd * plan.nm, 0.0);
-    if (plan.kind != 1) return;
-    for (uint32_t id = 0; id < nd; ++id)
-        for (uint32_t k = 0; k < plan.n; ++k)
-            (*src)[(size_t)id * plan.nm + k] = exp(-(1.0 / plan.m) * (k + 1) * dsrc[id]);  // loss.c:365
+    if (plan.kind == 1) scn_source_rows(plan.n, plan.m, dsrc, nd, plan.nm, src->data());
 }
 
 int sim_call(const SimPlan &plan, int ts, int tdis, const double *e, uint32_t ne, const double *c, uint32_t nc,

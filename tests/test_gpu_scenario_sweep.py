@@ -3,7 +3,8 @@ long-double evaluation of the model (tests/scn_ld.py): all eight k_scn<NL, NH>
 instantiations, k_scn_row and k_scn_big at every n <= 8 and k_scn_row at
 n = 9..12, each over a whole (e, c, K[, d]) grid -- every e lane of both
 32-value chunks -- and the multi-launch paths of k_scn_big and k_scn_row
-(p0 > 0, a short last launch, the scratch reused across launches).
+(p0 > 0, a short last launch, the scratch reused across launches).  One
+engine over three grids pins the grid buffers it keeps between set_grid calls.
 
 What is asserted: exactly 0 where the reference is 0, and a relative error of
 at most scn_ld.bound(n, ts, tdis) everywhere else, however small L is -- the
@@ -153,6 +154,29 @@ def test_one_point_launches(kind):
     capped = run(ROW[:n], kind, {**KERNELS["row"], "MDP_SCN_LAUNCH_PTS": 1}, e, c, K, d)
     assert np.array_equal(capped, whole)
     scn_ld.check(capped, ref, scn_ld.bound(n, TS, TDIS), f"row n={n} {kind} one point per launch")
+
+
+REUSE = {"lds": (4, KERNELS["lds"]), "row": (3, KERNELS["row"]),
+         "big": (3, {**KERNELS["big"], "MDP_SCN_LAUNCH_PTS": 256})}
+
+
+@pytest.mark.parametrize("kernel", ["lds", "row", "big"])
+@pytest.mark.parametrize("kind", ["dieoff", "loss"])
+def test_grid_buffers_reused(kind, kernel):
+    """One engine over three grids: the device buffers of a grid are kept and
+    grown, so the smaller second grid leaves the first one's values in their
+    tails (the axes, the source rows, v and k_scn_big's state scratch).  Every
+    result is bit-identical to a fresh engine's."""
+    n, opts = REUSE[kernel]
+    A = (E33, C2, K3, D2, 3, 2)
+    B = (E33[::8], C2[1:], K3[:2], D2[:1], 1, 4)  # 5 x 1 x 2 (x 1)
+    assert B[0].size == 5
+    with mdp.Scenario(ROW[:n], kind, m=M, p=P, d=D, options=opts) as sc:
+        for e, c, K, d, ts, tdis in (A, B, A):
+            got = sc.lik(e, c, K, d if kind == "loss" else None, ts=ts, tdis=tdis)
+            fresh = run(ROW[:n], kind, opts, e, c, K, d, ts=ts, tdis=tdis)
+            assert 2 * int((fresh > 0).sum()) >= fresh.size
+            assert np.array_equal(got, fresh)
 
 
 def real_size_grid():
