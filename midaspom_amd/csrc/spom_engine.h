@@ -3,6 +3,8 @@
 //   spom_plan.cpp    host planning: options, plan tables, hipRTC sources
 //   spom_engine.hip  device set-up, launches, timing, and the kernels
 //   plan_check.cpp   the planner's stand-alone driver
+// (the forward kernel's generator and its hipRTC unit, spom_jit.cpp and
+// spom_jit_rtc.cpp, share spom_jit.h, included here)
 // Plain C++17: the HIP headers below give the vector and handle types only.
 #ifndef MDP_SPOM_ENGINE_H
 #define MDP_SPOM_ENGINE_H

@@ -10,7 +10,8 @@
 //   spom_engine.hip  (this file) the kernels, device set-up (uploads,
 //                    set_grid_dev), the launch paths, run_dev, timing and the
 //                    rest of the C ABI
-//   spom_jit.cpp     generator and hipRTC cache of the specialised forward
+//   spom_jit.cpp     generator of the specialised forward kernel's source
+//   spom_jit_rtc.cpp its hipRTC compilation and code-object caches
 //
 // Paths (mdp_plan_engine picks one per engine; DESIGN.md sections 3-4):
 //   generic  any problem (MDP_JIT=0, or hipRTC failed): k_zpv -> k_coefs ->
@@ -2759,17 +2760,6 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
 {
     int rc;
     if (eng->jit) {
-        const double *Qrow = d.Qrow;
-        double prior0 = eng->prior0;
-        const double *ev = d.e;
-        uint32_t ne = d.ne, nc = d.nc, one = 1;
-        unsigned long long *st = d.stamps[2];
-        const double *cv = d.c, *ctab = d.coltab;
-        uint32_t ctl = d.ct_len, kmax = d.zs_kmax;
-        double *vscr = d.vscr;
-        uint32_t ldv = d.ldv;
-        const uint32_t *qidx = nullptr;
-        uint32_t se = os.se, sc = os.sc;
         // threads per e block: kb (x 2 with the split state-vector kernel)
         const uint32_t kb = d.fused ? eng->jit_kblock_fused : d.tall ? (uint32_t)kJitKblockTall : eng->jit_kblock;
         const uint32_t pro = d.fused ? eng->jit_pro_fused : 1u;
@@ -2786,24 +2776,37 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
         const uint64_t nb = gy * ((d.nc + fc - 1) / fc);  // e blocks x column groups
         if (nb * kb * fc * spl > 0xffffffffull)
             return mdp_set_error(MDP_EUNSUPPORTED, "grid %u x %u too large", d.ne, d.nc);
-        // mdp_fwd_jit's signature (spom_jit.cpp): the table the variant
-        // stages first, then what its front reads, the workgroup count, the
-        // chunk's gather list and what only its end reads
-        const double *tab = d.fused ? ctab : Qrow;
-        if (plist) ev = d.elist;  // a listed kernel reads e by list position
-        uint32_t nblk = (uint32_t)nb;
-        void *args[] = {(void *)&tab,   (void *)&cv,   (void *)&ev,  (void *)&ctl,  (void *)&nlist,
-                        (void *)&ne,    (void *)&nc,   (void *)&plist, (void *)&nblk, (void *)&kmax,
-                        (void *)&one,   (void *)&qidx, (void *)&out, (void *)&se,   (void *)&sc,
-                        (void *)&prior0, (void *)&vscr, (void *)&ldv, (void *)&st};
+        // mdp_fwd_jit's parameters (spom_jit.h declares them once, for the
+        // generated signature and for this struct)
+        MdpFwdJitArgs a;
+        a.tab = d.fused ? d.coltab : d.Qrow;  // the table the variant stages first
+        a.cvals = d.c;
+        a.evals = plist ? d.elist : d.e;  // a listed kernel reads e by list position
+        a.ct_len = d.ct_len;
+        a.nlist = nlist;
+        a.ne = d.ne;
+        a.nc = d.nc;
+        a.plist = plist;
+        a.nblk = (uint32_t)nb;
+        a.kmax = d.zs_kmax;
+        a.one = 1;
+        a.out = out;
+        a.ld_out = os.se;
+        a.out_cs = os.sc;
+        a.prior0 = eng->prior0;
+        a.vscr = d.vscr;
+        a.ldv = d.ldv;
+        a.stamps = d.stamps[2];
+        auto args = a.params();
+        static_assert(std::tuple_size<decltype(args)>::value == 19, "one kernelParams entry per parameter of mdp_fwd_jit");
         if (!eng->chunks.empty()) {  // a long series: its chunks in order on the stream
             const size_t nch = d.cfn.size();
             if (nch != eng->chunks.size() || d.cqidx.size() != nch)
                 return mdp_set_error(MDP_EHIP, "forward chunks not loaded (%zu of %zu)", nch, eng->chunks.size());
             for (size_t i = 0; i < nch; ++i) {
-                qidx = d.cqidx[i];
-                HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], (uint32_t)(nb * kb * spl), 1, 1, kb * spl, 1, 1, 0, s, args,
-                                                 nullptr, i == 0 ? t_kev.start : nullptr,
+                a.qidx = d.cqidx[i];  // the chunk's gather list (args points at the member)
+                HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], (uint32_t)(nb * kb * spl), 1, 1, kb * spl, 1, 1, 0, s,
+                                                 args.data(), nullptr, i == 0 ? t_kev.start : nullptr,
                                                  i + 1 == nch ? t_kev.stop : nullptr, 0));
             }
             note_launch(eng, d, "mdp_fwd_jit<reading,maxA%u,chunks%zu%s>", eng->maxA, nch,
@@ -2812,7 +2815,7 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
         }
         const uint32_t dyn = d.fused ? (d.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
         HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[d.fused ? 1 : d.tall ? 2 : 0], (uint32_t)(nb * kb * fc * spl * pro), 1, 1,
-                                         kb * fc * spl * pro, 1, 1, dyn, s, args, nullptr, t_kev.start, t_kev.stop, 0));
+                                         kb * fc * spl * pro, 1, 1, dyn, s, args.data(), nullptr, t_kev.start, t_kev.stop, 0));
         note_launch(eng, d, "mdp_fwd_jit<%s,maxA%u>", d.fused ? "fused" : "reading", eng->maxA);
         if (d.tall) note_launch(eng, d, "mdp_fwd_jit<reading,kb%d>", kJitKblockTall);
         return MDP_OK;

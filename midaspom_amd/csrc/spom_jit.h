@@ -1,6 +1,9 @@
-// midaspom_amd/csrc/spom_jit.h -- problem-specialised forward kernel (hipRTC).
+// midaspom_amd/csrc/spom_jit.h -- problem-specialised forward kernel (hipRTC):
+//   spom_jit.cpp      the generator of mdp_fwd_jit's HIP source (host only)
+//   spom_jit_rtc.cpp  hipRTC loading, the code-object caches, mdp_jit_compile
 #ifndef SPOM_JIT_H
 #define SPOM_JIT_H
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -100,6 +103,47 @@ MdpRatioWork mdp_jit_ratio_work(const MdpJitPlan &plan);
 // coefficient off + nX - k; slots of no group map to themselves.
 std::vector<uint32_t> mdp_jit_reversed_index(const std::vector<uint32_t> &udesc, size_t ldq);
 
+// mdp_fwd_jit's parameters, declared once, in order: IN(type, name) a table
+// the kernel only reads (const type *__restrict__), VAL(type, name) a value,
+// OUT(type, name) a table it writes (type *__restrict__); NL ends a line of the
+// generated list.  The generator emits the kernel's signature from this list
+// (`tab` named coltab in the fused variant, else Qrow) and the launch fills an
+// MdpFwdJitArgs, so the two cannot disagree.  Everything the kernel's front
+// reads ahead of its first barrier comes first and contiguous (14 SGPRs, the
+// kernel-argument preload's reach): the table the variant stages, c, e, the
+// sizes, the point list, the workgroup count and kmax; then one, the chunk's
+// gather list and what only the end of the kernel reads.
+#define MDP_FWD_JIT_PARAMS(IN, VAL, OUT, NL)                                         \
+    IN(double, tab) IN(double, cvals) NL                                             \
+    IN(double, evals) VAL(u32, ct_len) VAL(u32, nlist) VAL(u32, ne) VAL(u32, nc) NL  \
+    IN(u32, plist) VAL(u32, nblk) VAL(u32, kmax) VAL(u32, one) IN(u32, qidx) NL      \
+    OUT(double, out) VAL(u32, ld_out) VAL(u32, out_cs) VAL(double, prior0) NL        \
+    OUT(double, vscr) VAL(u32, ldv) OUT(unsigned long long, stamps)
+
+#define MDP_JIT_COUNT_(t, n) +1
+constexpr size_t kMdpFwdJitParams = 0 MDP_FWD_JIT_PARAMS(MDP_JIT_COUNT_, MDP_JIT_COUNT_, MDP_JIT_COUNT_, );
+#undef MDP_JIT_COUNT_
+static_assert(kMdpFwdJitParams == 19, "mdp_fwd_jit takes 19 parameters");
+
+// One launch's arguments: a member per parameter.
+struct MdpFwdJitArgs {
+    using u32 = uint32_t;
+#define MDP_JIT_IN_(t, n) const t *n = nullptr;
+#define MDP_JIT_VAL_(t, n) t n = 0;
+#define MDP_JIT_OUT_(t, n) t *n = nullptr;
+    MDP_FWD_JIT_PARAMS(MDP_JIT_IN_, MDP_JIT_VAL_, MDP_JIT_OUT_, )
+#undef MDP_JIT_IN_
+#undef MDP_JIT_VAL_
+#undef MDP_JIT_OUT_
+    // the kernelParams array of a module launch: each member's address, in order
+    std::array<void *, kMdpFwdJitParams> params()
+    {
+#define MDP_JIT_ADDR_(t, n) (void *)&n,
+        return {MDP_FWD_JIT_PARAMS(MDP_JIT_ADDR_, MDP_JIT_ADDR_, MDP_JIT_ADDR_, )};
+#undef MDP_JIT_ADDR_
+    }
+};
+
 // HIP source of `mdp_fwd_jit` for this plan; sets plan.epl when it was 0.
 std::string mdp_jit_forward_source(MdpJitPlan &plan);
 
@@ -107,6 +151,7 @@ std::string mdp_jit_forward_source(MdpJitPlan &plan);
 // kernels' own log (the prelude), for the accuracy test.
 std::string mdp_jit_log_source();
 
+// (spom_jit_rtc.cpp)
 // Compile (or fetch from the memory / disk cache) a gfx950 code object.
 // `fresh`: skip both caches and recompile (the runtime refused a cached
 // object); the new object replaces the cached one.

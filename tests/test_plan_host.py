@@ -39,6 +39,14 @@ def _full_year(n, year):
     return obs
 
 
+def _long_occupied(n, T, year, k):
+    """T years x n patches, all occupied, k patches unvisited in `year` (2^k states): min |A| is n in nearly every
+    year, so the forward's deferred exponent passes its flush threshold (192) within the series."""
+    obs = np.ones((T, n), dtype=int)
+    obs[year, :k] = -1
+    return obs
+
+
 def _highvar(nvar):   # as tests/test_gpu_highvar.py
     n, T, nv, dense, sparse, nmiss, seed = {12: (16, 8, 12, 11, 4, 2, 1), 16: (20, 8, 16, 15, 4, 2, 2),
                                             20: (22, 7, 20, 19, 3, 2, 3)}[nvar]
@@ -54,6 +62,7 @@ INPUTS = {
     "long200": (synth.LONG200, 400, 100),   # tests/test_gpu_longseries.py: 3 086 uses
     "s64": (lambda: np.array([[1, -1, -1, -1, -1, -1, -1, 1]] + LATER), 400, 100),
     "s128": (lambda: np.array([[-1] * 7 + [1]] + LATER), 400, 100),
+    "s32flush": (lambda: _long_occupied(8, 30, 27, 5), 400, 100),
     **{f"s512@{y}": ((lambda y=y: _full_year(9, y)), 400, 100) for y in (0, 2, 3)},
     **{f"s1024@{y}": ((lambda y=y: _full_year(10, y)), 400, 100) for y in (0, 1, 3)},
     "nvar12w": (lambda: _wide_obs(np.random.default_rng(3), 12, 5, {1: 6}), 400, 100),
@@ -76,6 +85,7 @@ CASES = [
     ("e", "config2", "MDP_QGLOBAL=1", "direct qglobal"),
     ("e", "config2", "MDP_QGLOBAL=1;MDP_JIT_CHUNK=40", r"direct chunked<\d+> qglobal"),
     ("f", "s64", "", "vlds"),
+    ("f", "s32flush", "", "vlds"),   # a vlds year that applies the deferred exponent
     ("f'", "s64", "MDP_WIDE=1", "wide-mmt<4,128,2buf>"),
     ("g", "s128", "", "wide-hs<2,8,8>"),
     ("g", "s128", "MDP_WIDE_MMA=0", "wide-plain"),
@@ -89,7 +99,16 @@ CASES = [
     ("i", "nvar12w", "MDP_WIDE=1;MDP_WIDE_MMA=3", "wide-mmt<4,128,2buf>"),   # nvar > 10: not k_fwd_hs
     *[("j", f"highvar{v}", o, p) for v in (12, 16, 20)
       for o, p in (("", "direct( fused-capable)?"), ("MDP_JIT=0", "generic"), ("MDP_WIDE=1", "wide-mmt<4,128,2buf>"))],
+    # the knobs that shape the generated forward source (csrc/spom_jit.cpp), one form of its text each
+    *[("k", "config2", o, "direct fused-capable") for o in (
+        "MDP_EPL=1", "MDP_EPL=4", "MDP_JIT_KBLOCK=512", "MDP_FUSED_COLS=1", "MDP_FUSED_COLS=4",
+        "MDP_JIT_ROT=0;MDP_JIT_SPLIT=0;MDP_JIT_XCD=0;MDP_JIT_EFAST=0;MDP_FAST_LOG=0",
+        "MDP_JIT_SLOTS=0;MDP_JIT_WINDOW=4", "MDP_JIT_SLOTS=2;MDP_JIT_WINDOW=16",
+        "MDP_DIAG=1", "MDP_JIT_HACK=1", "MDP_JIT_HACK=2;MDP_JIT_WPE=2")],   # the last three: plan_check --diag
+    *[("k", "s64", o, "vlds") for o in ("MDP_VSPLIT=1", "MDP_VSPLIT=2", "MDP_VLDS_EPL=2")],
+    ("k", "s64", "MDP_JIT_CHUNK=40", r"vlds chunked<\d+>"),
 ]
+DIAG_OPTIONS = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE")   # measurement-only names: accepted with --diag alone
 
 LINE = re.compile(r"^path (?P<path>.+) \| nj (\d+) nitems (?P<nitems>\d+) ldQ (\d+) nqi (\d+) qmaxlen (\d+) kzmax (\d+) "
                   r"slots (?P<slots>\d+) conflicts (?P<gather>\d+) \+ (?P<store>\d+) \| digest [0-9a-f]{16}$")
@@ -113,8 +132,9 @@ def inputs(tmp_path_factory):
 
 def _run(exe, inputs, name, options):
     _, m, d = INPUTS[name]
-    return subprocess.run([str(exe), str(inputs[name]), str(m), str(d), options], capture_output=True, text=True,
-                          timeout=120)
+    flags = ["--diag"] if any(k in options for k in DIAG_OPTIONS) else []
+    return subprocess.run([str(exe), *flags, str(inputs[name]), str(m), str(d), options], capture_output=True,
+                          text=True, timeout=120)
 
 
 def _check(r, case, name, options, path):
