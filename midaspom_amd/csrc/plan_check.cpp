@@ -1,6 +1,7 @@
 // midaspom_amd/csrc/plan_check.cpp -- the engine's host planner over one
 // problem, without a device or the HIP runtime:
-//   plan_check [--diag] [--sources] OBSFILE M D "OPTIONS"
+//   plan_check [--diag] [--sources] [--grid NE NC NCU [--e LO HI] [--c LO HI]
+//              [--cbound B] [--list]] OBSFILE M D "OPTIONS"
 // loads the observations (prior 0.5), parses the engine options, plans with
 // the 160 KiB LDS of gfx950 and generates the forward sources the plan would
 // compile (hipRTC is never called).  One line: the path taken, the counts of
@@ -13,8 +14,19 @@
 // named reading, fused and tall (the reading kernel at kJitKblockTall
 // threads, of direct plans that are neither chunked nor vlds), or chunk<i>:
 // two generators print the same lines exactly when they emit the same text.
+// --grid plans one grid as mdp_engine_set_grid would on a device of NCU
+// compute units (mdp_plan_grid; no device is asked): NE e values from LO to HI
+// (mdp_grid; 0 to 1 unless given, descending where LO > HI) by NC c values
+// (the same), under the |c| bound B if given.  After the summary line,
+//   grid <fused|reading|tall|-> | gy nlist epl identity ne_sform | qrows_cb
+//        wide_cb_items wide_cb_fwd | kmax ct_len zrows_lds | launch ... | buf ...
+//        | kernels <the names a run notes for mdp_engine_launched, ';' between> | fnv ...
+// with FNV-1a digests of the point list, its e values and each c table; a
+// refused grid is mdp_last_error() on stderr and exit 1.  --list adds the
+// point list itself (plist v v ...; bit 31 marks a padding duplicate).
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 
@@ -117,23 +129,104 @@ std::string path_of(const mdp_engine *e)
         return std::string(e->jit_plan.vlds ? "vlds " : "direct ") + b + (e->qglobal ? " qglobal" : "");
     }
     if (e->jit_plan.vlds) return "vlds";
+#ifdef MDP_PLAN_GRID
+    const bool fused = mdp_plan_fused_capable(e);
+#else  // a planner from before mdp_plan_grid (scripts/jit_sources.py --rev)
     const bool fused = !e->qglobal && fused_lds(e, e->jit_plan.ct_max) <= kFusedLdsMax;
+#endif
     return std::string("direct") + (fused ? " fused-capable" : "") + (e->qglobal ? " qglobal" : "");
 }
+
+template <typename T>
+unsigned long long fnv(const std::vector<T> &v)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < v.size() * sizeof(T); ++i) h = (h ^ ((const unsigned char *)v.data())[i]) * 0x100000001b3ull;
+    return h;
+}
+
+struct GridArgs {
+    bool on = false, list = false;
+    uint32_t ne = 0, nc = 0, ncu = 0;
+    double e[2] = {0.0, 1.0}, c[2] = {0.0, 1.0}, cbound = 0.0;
+};
+
+#ifdef MDP_PLAN_GRID
+// the --grid mode: plan the grid and print its line (after digest(): the
+// generator has settled the forward shapes)
+int grid_line(mdp_engine *eng, const GridArgs &a)
+{
+    if (!eng->chunks.empty()) {  // the chunks' shape, as jit_build_chunks takes it from the generator
+        MdpJitPlan c0 = eng->chunks[0];
+        (void)mdp_jit_forward_source(c0);
+        eng->jit_epl = c0.epl;
+        eng->jit_kblock = (uint32_t)c0.kblock;
+    }
+    eng->cbound = a.cbound;
+    std::vector<double> e(a.ne), c(a.nc);
+    mdp_grid(a.ne, a.e[0], a.e[1], e.data());
+    mdp_grid(a.nc, a.c[0], a.c[1], c.data());
+    MdpCTables ct;
+    MdpGridPlan g;
+    if (mdp_plan_grid(eng, ct, e.data(), a.ne, c.data(), a.nc, a.ncu, g)) return 1;
+    const bool jit = eng->jit && !eng->wide;
+    if (jit) mdp_plan_fwd_launch(eng, ct, a.ne, a.nc, g);
+    std::string kernels;
+    for (const std::string &k : mdp_plan_grid_kernels(eng, g, a.ne, a.nc)) kernels += (kernels.empty() ? "" : ";") + k;
+    printf("grid %s | gy %u nlist %u epl %u identity %d ne_sform %u | qrows_cb %u wide_cb_items %u wide_cb_fwd %u | "
+           "kmax %u ct_len %u zrows_lds %zu | launch nblk %llu threads %llu pro %u block %u lds %u nlist %u listed %d | "
+           "buf qrow %zu zg %zu pg %zu pg_zero %d v %zu vscr %zu ldv %u zpv %zu r %zu gpart %zu stamps %zu,%zu,%zu | "
+           "kernels %s | fnv plist %016llx elist %016llx zs %016llx zsq %016llx zc %016llx coltab %016llx\n",
+           !jit ? "-" : g.fused ? "fused" : g.tall ? "tall" : "reading", g.gy, g.nlist, g.nlist_epl, (int)g.plist_identity,
+           g.ne_sform, g.qrows_cb, g.wide_cb_items, g.wide_cb_fwd, ct.kmax, ct.ct_len, g.zrows_lds,
+           (unsigned long long)g.fwd_nblk, (unsigned long long)g.fwd_threads, g.fwd_pro, g.fwd_block, g.fwd_lds, g.fwd_nlist,
+           (int)g.fwd_listed, g.n_qrow, g.n_zg, g.n_pg, (int)g.pg_zero, g.n_v, g.n_vscr, g.ldv, g.n_zpv, g.n_r, g.n_gpart,
+           g.nst[0], g.nst[1], g.nst[2], kernels.empty() ? "-" : kernels.c_str(), fnv(g.plist), fnv(g.elist), fnv(ct.zs),
+           fnv(ct.zsq), fnv(ct.zc), fnv(ct.coltab));
+    if (a.list) {
+        printf("plist");
+        for (uint32_t v : g.plist) printf(" %u", v);
+        printf("\n");
+    }
+    return 0;
+}
+
+#else
+int grid_line(mdp_engine *, const GridArgs &)
+{
+    fprintf(stderr, "plan_check: this planner plans no grid\n");
+    return 2;
+}
+#endif
 
 }  // namespace
 
 int main(int argc, char **argv)
 {
     bool diag = false;
+    GridArgs grid;
     for (; argc > 1 && argv[1][0] == '-' && argv[1][1] == '-'; --argc, ++argv) {
         const std::string flag = argv[1];
+        // a flag's values follow it (a value may be negative, so none is taken for a flag)
+        auto values = [&](int n, double *v) {
+            if (argc < 2 + n) return argc = 0, false;
+            for (int i = 0; i < n; ++i) v[i] = atof(argv[2 + i]);
+            argc -= n, argv += n;
+            return true;
+        };
+        double v[3];
         if (flag == "--diag") diag = true;
         else if (flag == "--sources") g_sources = true;
+        else if (flag == "--list") grid.list = true;
+        else if (flag == "--grid" && values(3, v)) grid.on = true, grid.ne = (uint32_t)v[0], grid.nc = (uint32_t)v[1], grid.ncu = (uint32_t)v[2];
+        else if (flag == "--e" && values(2, grid.e)) continue;
+        else if (flag == "--c" && values(2, grid.c)) continue;
+        else if (flag == "--cbound" && values(1, &grid.cbound)) continue;
         else argc = 0;
     }
     if (argc != 5) {
-        fprintf(stderr, "usage: plan_check [--diag] [--sources] OBSFILE M D \"OPTIONS\"\n");
+        fprintf(stderr, "usage: plan_check [--diag] [--sources] [--grid NE NC NCU [--e LO HI] [--c LO HI] [--cbound B] "
+                        "[--list]] OBSFILE M D \"OPTIONS\"\n");
         return 2;
     }
     auto fail = []() {
@@ -155,5 +248,6 @@ int main(int argc, char **argv)
            eng->slot_conflicts, eng->slot_store_conflicts, (unsigned long long)g_h);
     if (g_sources && eng->jit && !eng->wide && eng->chunks.empty() && !pl.vlds && tall_source(eng.get())) return 1;
     fputs(g_src_lines.c_str(), stdout);
+    if (grid.on && grid_line(eng.get(), grid)) return fail();
     return 0;
 }

@@ -1,7 +1,10 @@
 // midaspom_amd/csrc/spom_engine.h -- internal to the posterior engine (not
 // installed; the public ABI is include/midaspom.h).  Shared by
-//   spom_plan.cpp    host planning: options, plan tables, hipRTC sources
-//   spom_engine.hip  device set-up, launches, timing, and the kernels
+//   spom_plan.cpp    host planning: options, plan tables, hipRTC sources, and
+//                    per grid the c tables and the grid plan (kernel variant,
+//                    point list, chunk widths, buffer sizes, launch shape)
+//   spom_engine.hip  the kernels; device set-up, uploads and launches as the
+//                    plans say; timing
 //   plan_check.cpp   the planner's stand-alone driver
 // (the forward kernel's generator and its hipRTC unit, spom_jit.cpp and
 // spom_jit_rtc.cpp, share spom_jit.h, included here)
@@ -18,6 +21,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mdp_internal.h"
@@ -60,6 +64,14 @@ constexpr size_t kQrowsLdsMax = 160 * 1024;  // k_qrows: every table of its c va
 constexpr size_t kFusedLdsMax = 64 * 1024;  // fused forward kernel: every table of one column
 constexpr int kZTerms = kZTermsDev;  // z_split: terms of the small columns' series
 constexpr int kJitKblockTall = 512;  // threads of the reading kernel's tall variant (jit_build)
+constexpr uint32_t kZRows = kBlock / 64;  // k_zrows: rows per workgroup (staged in dynamic LDS)
+constexpr uint32_t kQrowsMaxC = 4;        // k_qrows: most c values per workgroup
+constexpr int kZpvJ = 64;                 // k_zpv: hidden states per workgroup
+constexpr int kZpvCT = 2;                 // k_zpv: c values per thread
+constexpr int kStampSlots = 8;            // diagnostic stamps per workgroup
+constexpr size_t kWidePgBytes = 256ull << 20;  // wide path: item-factor chunk
+constexpr size_t kHsPgBytes = 2048ull << 20;   // k_fwd_hs: item factors of the columns of one launch
+constexpr size_t kWideVBytes = 1ull << 30;     // wide path: state-vector scratch
 
 // ---------------------------------------------------------------------------
 // types
@@ -69,6 +81,56 @@ constexpr int kJitKblockTall = 512;  // threads of the reading kernel's tall var
 struct LaunchNote {
     const char *fmt;
     uint64_t a[4];
+};
+
+// The tables that depend on the grid's |c| bound (mdp_plan_grid builds them;
+// z_split prunes the Z rows for the bound).  Cached by cmax: a grid under the
+// same bound neither rebuilds nor re-uploads them.
+struct MdpCTables {
+    double cmax = -1.0;          // the bound they were pruned for (-1: none yet)
+    uint32_t kmax = 0;           // padded length of the longest pruned row
+    uint32_t ct_len = 0;         // doubles of coltab (0: the plan never runs fused)
+    std::vector<double> zs;      // k_zrows: row-major [row][k]
+    std::vector<double> zsq;     // k_qrows: chain-major [row][k mod 4][k / 4] (a lane's chain contiguous)
+    std::vector<double> zc;      // Z-row series coefficients [row][kZTerms]
+    std::vector<double> coltab;  // the fused kernel's column image (plan offsets, zs last), 1 KiB padded
+};
+
+// What one grid runs (mdp_plan_grid): every per-grid choice of the engine,
+// made on the host without a device.  set_grid_dev grows and uploads what it
+// says, the launchers read it.
+struct MdpGridPlan {
+    uint32_t ne_sform = 0;  // e rows on the s-form (x < y), for the work count
+    bool tables_new = false;  // the c tables were rebuilt for this grid (upload them)
+    // forward kernels with several points per lane: list positions -> e rows
+    // (bit 31: a duplicate that is computed, not stored), grouped by ratio
+    // form; elist: e by list position, then e[0] (what a position past the
+    // list reads).  An identity list (0, 1, ...) is not uploaded.
+    std::vector<uint32_t> plist;
+    std::vector<double> elist;
+    uint32_t nlist = 0, nlist_epl = 0;  // list length (a multiple of nlist_epl, its points per lane)
+    bool plist_identity = true;
+    // the forward variant: jit_load's index (0 reading, 1 fused, 2 reading at
+    // kJitKblockTall threads)
+    bool fused = false, tall = false;
+    int variant = 0;
+    uint32_t gy = 0;   // e blocks per column of the reading shape
+    uint32_t ldv = 0;  // a chunked series: e values per (state, c) of the state scratch
+    // c values per k_qrows workgroup, per k_witems launch, per k_fwd_wide launch
+    uint32_t qrows_cb = 1, wide_cb_items = 1, wide_cb_fwd = 1;
+    // elements of the grow-only buffers (0: not used by this path)
+    size_t n_qrow = 0, n_zg = 0, n_pg = 0, n_v = 0, n_vscr = 0, n_zpv = 0, n_r = 0, n_gpart = 0;
+    size_t nst[3] = {0, 0, 0};  // diag stamps: workgroups of k_zpv / k_qrows, k_coefs, forward
+    bool pg_zero = false;       // Pg is zero-filled (k_fwd_hs reads its rows' zero slot)
+    size_t zrows_lds = 0;       // k_zrows' dynamic LDS (bytes)
+    // the mdp_fwd_jit launch (mdp_plan_fwd_launch): 64-bit products, so run
+    // time can still refuse a grid too large for the launch
+    uint64_t fwd_nblk = 0;      // e blocks x column groups (MdpFwdJitArgs::nblk)
+    uint64_t fwd_threads = 0;   // the launch's forward threads (x fwd_pro with the fused prologue's)
+    uint32_t fwd_pro = 1;
+    uint32_t fwd_block = 0, fwd_lds = 0;  // threads per workgroup, dynamic LDS (bytes)
+    uint32_t fwd_nlist = 0;     // MdpFwdJitArgs::nlist
+    bool fwd_listed = false;    // the kernel reads plist / elist
 };
 
 struct DevCtx {
@@ -82,23 +144,19 @@ struct DevCtx {
     double *e = nullptr, *c = nullptr;
     size_t cap_e = 0, cap_c = 0;
     uint32_t ne = 0, nc = 0;
-    uint32_t ne_sform = 0;  // e rows of this grid on the s-form (x < y), for the work count
-    // forward kernels with several points per lane: list positions -> e rows
-    // (bit 31: a duplicate that is computed, not stored), grouped by ratio form
+    MdpCTables ct;     // the c tables on the device (host copy and the bound they hold for)
+    MdpGridPlan plan;  // the current grid's plan (set_grid_dev)
+    // the plan's point list and its e values by position: a listed kernel
+    // loads its e values by position, beside the list, instead of through it
+    // (position -> row -> e would be two round trips in series)
     uint32_t *plist = nullptr;
     size_t cap_plist = 0;
-    // e by list position, then e[0] (what a position past the list reads): a
-    // listed kernel loads its e values by position, beside the list, instead
-    // of through it (position -> row -> e would be two round trips in series)
     double *elist = nullptr;
     size_t cap_elist = 0;
-    uint32_t nlist = 0, nlist_epl = 0;  // list length (a multiple of nlist_epl, its points per lane)
-    bool plist_identity = true;          // the list is 0, 1, ... (nothing uploaded; plist passed as null)
     double *ZPV = nullptr, *R = nullptr, *out = nullptr, *gpart = nullptr;
     size_t cap_zpv = 0, cap_r = 0, cap_out = 0, cap_gpart = 0;
     unsigned long long *stamps[3] = {nullptr, nullptr, nullptr};  // k_zpv, k_coefs, k_forward
     size_t cap_st[3] = {0, 0, 0};
-    size_t nst[3] = {0, 0, 0};
     // direct path: k_zrows / k_qrows tables (zs, row-major [row][k], depends
     // on the grid's c range)
     double *zs = nullptr, *sv = nullptr, *Qrow = nullptr, *Zg = nullptr;
@@ -111,16 +169,11 @@ struct DevCtx {
     uint32_t *islot = nullptr;  // k_qrows: each item's Pc slot
     uint32_t *itemB = nullptr, *qstart = nullptr, *qitem = nullptr;
     size_t cap_zs = 0, cap_zsq = 0, cap_qrow = 0, cap_zg = 0;
-    uint32_t zs_len = 0;    // doubles in zs = zs_kmax * nj
-    double *coltab = nullptr;  // fused kernel's column tables (plan offsets, zs last), 1 KiB padded
+    double *coltab = nullptr;  // fused kernel's column tables (MdpCTables::coltab)
     size_t cap_coltab = 0;
-    uint32_t ct_len = 0;       // doubles
-    uint32_t zs_kmax = 0;   // padded length of the longest pruned row
-    uint32_t qrows_cb = 1;  // c values per k_qrows workgroup for this grid
     bool qrows_attr_set = false;  // k_qrows' LDS limit raised on this device
-    double zs_cmax = -1.0;  // c bound the uploaded zs was pruned for (-1: none yet)
     // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
-    // reading at kJitKblockTall threads (tall grids, set_grid_dev)
+    // reading at kJitKblockTall threads (tall grids, mdp_plan_grid)
     hipModule_t jit_mod[3] = {nullptr, nullptr, nullptr};
     hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
     // a long series: one forward kernel per chunk of years, the state vector
@@ -130,9 +183,6 @@ struct DevCtx {
     std::vector<uint32_t *> cqidx;  // per chunk: gather indices into the Q row (null: whole row)
     double *vscr = nullptr;
     size_t cap_vscr = 0;
-    uint32_t ldv = 0;
-    bool fused = false;  // this grid runs the fused forward kernel (no k_qrows)
-    bool tall = false;   // this grid runs the reading kernel at kJitKblockTall threads
     uint32_t ncu = 0;    // the device's compute units (0: not asked yet)
     // wide path: per-chunk item factors, state-vector scratch, tables
     double *Pg = nullptr, *V = nullptr;
@@ -148,7 +198,6 @@ struct DevCtx {
     uint2 *hs_ppos = nullptr, *hs_dpk = nullptr;
     uint4 *hs_wplan = nullptr;
     uint4 *hs_pass = nullptr;
-    uint32_t wide_cb_items = 1, wide_cb_fwd = 1;  // c values per k_witems / k_fwd_wide launch
     std::vector<hipEvent_t> ev;  // kNumEv events per profiled run, reused
     std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
     size_t ev_used = 0;          // event sets recorded since the last collect
@@ -343,6 +392,90 @@ inline size_t fused_lds(const mdp_engine *eng, size_t ct_len)
 inline size_t wide_lds(const mdp_engine *eng) { return 2 * ((size_t)eng->maxA + 1) * kBlock * sizeof(double); }
 
 // ---------------------------------------------------------------------------
+// The instantiation set of each templated kernel family, written once: the
+// switch from the plan to the one instantiation it runs, as fn(tags...) with
+// std::integral_constant tags.  Raising the LDS limit, launching and naming a
+// launch (mdp_engine_launched) all go through these, so they cannot name
+// different instantiations.  The kFmt strings are note_launch's formats.
+// ---------------------------------------------------------------------------
+template <int V>
+using mdp_int = std::integral_constant<int, V>;
+template <bool V>
+using mdp_bool = std::integral_constant<bool, V>;
+
+constexpr const char *kFmtQrows = "k_qrows<%d,%d,%d>", *kFmtCoefs = "k_coefs<%d,%d,%d>", *kFmtWitems = "k_witems<%d>",
+                     *kFmtHs = "k_fwd_hs<%u,%u>", *kFmtMmt = "k_fwd_mmt<%u,%u,%s>", *kFmtMma = "k_fwd_mma<%u>",
+                     *kFmtJit = "mdp_fwd_jit<%s,maxA%u>", *kFmtJitTall = "mdp_fwd_jit<reading,kb%d>",
+                     *kFmtJitChunks = "mdp_fwd_jit<reading,maxA%u,chunks%zu%s>";
+
+// k_qrows<NV, EXACT, CB> for cb c values per workgroup: a power of two, at
+// most 4, 2, 1 by NV (the register budget at 1 024 threads; else one)
+template <typename F>
+auto for_qrows(const mdp_engine *eng, uint32_t cb, F &&fn)
+{
+    const uint32_t nvar = eng->nvar;
+    if ((cb != 2 && cb != 4) || cb > (nvar <= 8 ? 4u : nvar <= 16 ? 2u : 1u)) {
+        if (nvar == 8) return fn(mdp_int<8>(), mdp_bool<true>(), mdp_int<1>());
+        if (nvar < 8) return fn(mdp_int<8>(), mdp_bool<false>(), mdp_int<1>());
+        if (nvar <= 16) return fn(mdp_int<16>(), mdp_bool<false>(), mdp_int<1>());
+        return fn(mdp_int<24>(), mdp_bool<false>(), mdp_int<1>());
+    }
+    if (cb == 2) {
+        if (nvar == 8) return fn(mdp_int<8>(), mdp_bool<true>(), mdp_int<2>());
+        if (nvar < 8) return fn(mdp_int<8>(), mdp_bool<false>(), mdp_int<2>());
+        return fn(mdp_int<16>(), mdp_bool<false>(), mdp_int<2>());
+    }
+    return nvar == 8 ? fn(mdp_int<8>(), mdp_bool<true>(), mdp_int<4>()) : fn(mdp_int<8>(), mdp_bool<false>(), mdp_int<4>());
+}
+
+// the padded variable-column count of k_coefs and k_witems
+template <typename F>
+auto for_nv(const mdp_engine *eng, F &&fn)
+{
+    if (eng->nvar <= 8) return fn(mdp_int<8>());
+    if (eng->nvar <= 16) return fn(mdp_int<16>());
+    return fn(mdp_int<24>());
+}
+
+// k_coefs<LDS_ZPV, LDS_PART, NV>
+template <typename F>
+auto for_coefs(const mdp_engine *eng, F &&fn)
+{
+    if (eng->lds_zpv) return for_nv(eng, [&](auto nv) { return fn(mdp_bool<true>(), mdp_bool<true>(), nv); });
+    if (eng->lds_part) return for_nv(eng, [&](auto nv) { return fn(mdp_bool<false>(), mdp_bool<true>(), nv); });
+    return for_nv(eng, [&](auto nv) { return fn(mdp_bool<false>(), mdp_bool<false>(), nv); });
+}
+
+// k_fwd_hs<RT, NB, NW>
+template <typename F>
+auto for_hs(const mdp_engine *eng, F &&fn)
+{
+    if (eng->hs_nb == 8)
+        return eng->hs_nw == 8 ? fn(mdp_int<2>(), mdp_int<8>(), mdp_int<8>()) : fn(mdp_int<4>(), mdp_int<8>(), mdp_int<16>());
+    if (eng->hs_nb == 9) return fn(mdp_int<2>(), mdp_int<9>(), mdp_int<16>());
+    return fn(mdp_int<1>(), mdp_int<10>(), mdp_int<16>());
+}
+
+// k_fwd_mmt<RT, ROWS, DB>
+template <typename F>
+auto for_mmt(const mdp_engine *eng, F &&fn)
+{
+    if (eng->mmt_rows == 128) return fn(mdp_int<4>(), mdp_int<128>(), mdp_bool<true>());
+    if (eng->mmt_rows == 256) return fn(mdp_int<2>(), mdp_int<256>(), mdp_bool<false>());
+    if (eng->mmt_rows == 512) return fn(mdp_int<2>(), mdp_int<512>(), mdp_bool<false>());
+    return fn(mdp_int<1>(), mdp_int<1024>(), mdp_bool<false>());
+}
+
+// k_fwd_mma<NPM>
+template <typename F>
+auto for_mma(const mdp_engine *eng, F &&fn)
+{
+    if (eng->mma_npm == 64) return fn(mdp_int<64>());
+    if (eng->mma_npm == 128) return fn(mdp_int<128>());
+    return fn(mdp_int<256>());
+}
+
+// ---------------------------------------------------------------------------
 // planner entry points (spom_plan.cpp)
 // ---------------------------------------------------------------------------
 
@@ -363,6 +496,31 @@ enum class MdpPlanMode {
 // lds_max the device's LDS per workgroup (160 KiB on gfx950).  jit_t (may be
 // null) receives the steady-clock seconds around the hipRTC step.
 int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t);
+
+#define MDP_PLAN_GRID 1  // (plan_check.cpp also builds against planners without one: scripts/jit_sources.py --rev)
+// The grid plan of e[ne] x c[nc] on a device of ncu compute units: refuses a
+// c the engine does not take (MDP_EINVAL) and Z rows past k_zrows' LDS
+// (MDP_EUNSUPPORTED), rebuilds ct when the grid's |c| bound (at least
+// eng->cbound) is not the one it holds (g.tables_new), and fills g but for
+// the forward launch.  The engine's forward shape must be known (jit_source
+// of one variant has run: mdp_plan_engine's compile, or plan_check's digest).
+int mdp_plan_grid(const mdp_engine *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
+                  uint32_t ncu, MdpGridPlan &g);
+// The mdp_fwd_jit launch of g, once its variant's shape is known (jit_build or
+// jit_source of g.variant has run: the generator settles the fused shape).
+void mdp_plan_fwd_launch(const mdp_engine *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g);
+// Can any grid of this plan run the fused forward kernel?
+bool mdp_plan_fused_capable(const mdp_engine *eng);
+// The c-independent tables of the direct and wide paths: sv[row][b], the
+// colonisation sum of variable column b for row's hidden state (+inf for the
+// columns of j: pressure fmin(c inf, 1) = 1.0), and the packed items {B | row
+// << 24, j | (row >> 8) << 24}; one spare element each.
+void mdp_plan_item_tables(const mdp_engine *eng, std::vector<double> &sv, std::vector<uint2> &items);
+// Does kernel slot k (0: Q rows / k_zpv, 1: k_coefs, 2: forward) run on this path?
+bool mdp_plan_slot_active(const mdp_engine *eng, const MdpGridPlan &g, int k);
+// The kernel instantiations one run of the grid notes for mdp_engine_launched,
+// sorted (the generic path's forward kernel is left to its launcher).
+std::vector<std::string> mdp_plan_grid_kernels(const mdp_engine *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc);
 
 void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
              std::vector<uint32_t> *cols = nullptr);

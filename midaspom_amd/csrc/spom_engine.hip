@@ -5,11 +5,14 @@
 //   spom_engine.h    constants, types and size helpers shared by the planner,
 //                    the kernels and the launchers
 //   spom_plan.cpp    host planning: options, the plan tables the kernels
-//                    index, the hipRTC sources, the host-only C ABI functions;
-//                    no HIP runtime call
-//   spom_engine.hip  (this file) the kernels, device set-up (uploads,
-//                    set_grid_dev), the launch paths, run_dev, timing and the
-//                    rest of the C ABI
+//                    index, the hipRTC sources, per grid the c tables and the
+//                    grid plan (mdp_plan_grid: kernel variant, point list,
+//                    chunk widths, buffer sizes, launch shape), the host-only
+//                    C ABI functions; no HIP runtime call
+//   spom_engine.hip  (this file) the kernels, device set-up (uploads;
+//                    set_grid_dev grows and uploads what the grid plan says),
+//                    the launch paths, run_dev, timing and the rest of the C
+//                    ABI
 //   spom_jit.cpp     generator of the specialised forward kernel's source
 //   spom_jit_rtc.cpp its hipRTC compilation and code-object caches
 //
@@ -45,11 +48,8 @@
 
 namespace {
 
-constexpr int kZpvJ = 64;       // k_zpv: hidden states per workgroup
 constexpr int kZpvSlices = 4;   // k_zpv: waves splitting the zero-column product
-constexpr int kZpvCT = 2;       // k_zpv: c values per thread
 constexpr int kZpvUnroll = 8;   // k_zpv: S loads in flight per lane
-constexpr int kStampSlots = 8;      // diagnostic stamps per workgroup
 constexpr unsigned kWaitLgkm0 = 0xC07F;  // s_waitcnt lgkmcnt(0), other counters untouched
 #ifdef MDP_DIAG_BUILD
 constexpr bool kDiagBuild = true;  // the measurement-only options are accepted (parse_engine_opts)
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_zpv(
 // the fused forward kernel (four chains over k mod 8), so both variants give
 // identical bits.
 // Product of a Z row's small-column factors: exp(-c (P1 + c (P2/2 + ... +
-// c P8/8))), Horner from the top (upload_qrows_tables; the fused kernel
+// c P8/8))), Horner from the top (z_split's coefficients; the fused kernel
 // evaluates the same expression)
 __device__ __forceinline__ double zseries(const double (&p)[kZTermsDev], double c)
 {
@@ -242,7 +242,6 @@ __device__ __forceinline__ double zseries(const double (&p)[kZTermsDev], double 
     return exp(-(q * c));
 }
 
-constexpr uint32_t kZRows = kBlock / 64;  // rows per workgroup
 constexpr uint32_t kZStage = 4;           // staging loads in flight per thread
 constexpr uint32_t kZC = 2;               // c values per lane
 __global__ __launch_bounds__(kBlock) void k_zrows(const double *__restrict__ cvals, uint32_t nc,
@@ -269,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void k_zrows(const double *__restrict__ cva
     __syncthreads();
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
     if (w >= nr) return;
-    // the row's small columns: exp(-c (P1 + c (P2/2 + ...))) (upload_qrows_tables)
+    // the row's small columns: exp(-c (P1 + c (P2/2 + ...))) (z_split's coefficients)
     double zcoef[kZTermsDev];
 #pragma unroll
     for (int i = 0; i < kZTermsDev; ++i) zcoef[i] = zc[(size_t)(r0 + w) * kZTermsDev + i];
@@ -355,7 +354,6 @@ __device__ __forceinline__ double quad_dpp(double v)
 constexpr int kQLevels = 24;
 
 constexpr int kQrowsBlock = 1024;
-constexpr uint32_t kQrowsMaxC = 4;
 template <int NV, bool EXACT, int CB>  // EXACT: nvar == NV (no padded factor slots)
 __global__ __launch_bounds__(kQrowsBlock) void k_qrows(
     const double *__restrict__ cvals, uint32_t nc, uint32_t nvar, uint32_t nrows,
@@ -2215,14 +2213,6 @@ inline void note_launch(const mdp_engine *eng, const DevCtx &d, const char *fmt,
     note_launch_fmt(eng, fmt, a...);
 }
 
-// the k_fwd_mma instantiation of the engine's plan
-const void *mma_kernel(const mdp_engine *eng)
-{
-    if (eng->mma_npm == 64) return (const void *)k_fwd_mma<64>;
-    if (eng->mma_npm == 128) return (const void *)k_fwd_mma<128>;
-    return (const void *)k_fwd_mma<256>;
-}
-
 // the device's LDS per workgroup (the current device; 160 KiB on gfx950)
 size_t device_lds_max()
 {
@@ -2233,84 +2223,45 @@ size_t device_lds_max()
     return 160 * 1024;
 }
 
-const void *mmt_kernel(const mdp_engine *eng)
+// raise a kernel's dynamic LDS limit
+template <typename K>
+int set_lds_limit(K *kernel, size_t bytes)
 {
-    if (eng->mmt_rows == 128) return (const void *)k_fwd_mmt<4, 128, true>;
-    if (eng->mmt_rows == 256) return (const void *)k_fwd_mmt<2, 256, false>;
-    if (eng->mmt_rows == 512) return (const void *)k_fwd_mmt<2, 512, false>;
-    return (const void *)k_fwd_mmt<1, 1024, false>;
+    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return MDP_OK;
 }
 
-const void *hs_kernel(const mdp_engine *eng)
+// the LDS limits of the wide path's forward kernels: the plan's matrix-core
+// instantiation and k_fwd_wide
+int wide_lds_limits(const mdp_engine *eng)
 {
-    if (eng->hs_nb == 8) return eng->hs_nw == 8 ? (const void *)k_fwd_hs<2, 8, 8> : (const void *)k_fwd_hs<4, 8, 16>;
-    if (eng->hs_nb == 9) return (const void *)k_fwd_hs<2, 9, 16>;
-    return (const void *)k_fwd_hs<1, 10, 16>;
-}
-
-int upload_qrows_tables(const mdp_engine *eng, DevCtx &d, double cmax)
-{
-    const uint32_t n = eng->n, nj = eng->nj;
-    (void)n;
-    std::vector<std::vector<double>> rows(nj);
-    std::vector<double> zc((size_t)nj * kZTerms + 1, 0.0);
-    size_t kmax = 0;
-    for (uint32_t js = 0; js < nj; ++js) {
-        z_split(eng, js, cmax, rows[js], &zc[(size_t)js * kZTerms]);
-        kmax = std::max(kmax, rows[js].size());
-    }
-    kmax = (kmax + 7) & ~(size_t)7;
-    std::vector<double> zs(kmax * nj + 1, 0.0);  // [k][row]: the fused kernel's image
-    for (uint32_t js = 0; js < nj; ++js)
-        for (size_t k = 0; k < rows[js].size(); ++k) zs[k * nj + js] = rows[js][k];
-    std::vector<double> zsT(kmax * nj + 1, 0.0);  // [row][k]: k_zrows (device copy)
-    for (uint32_t js = 0; js < nj; ++js)
-        for (size_t k = 0; k < rows[js].size(); ++k) zsT[js * kmax + k] = rows[js][k];
     int rc;
-    if ((rc = dev_grow(d.zs, d.cap_zs, zsT.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zs, zsT.data(), zsT.size() * sizeof(double), hipMemcpyHostToDevice));
-    // k_qrows' copy: row js's product chain q (columns k = q mod 4) contiguous
-    std::vector<double> zsq(kmax * nj + 2, 0.0);  // + a double2 k_qrows may read at kmax 0
-    for (uint32_t js = 0; js < nj; ++js)
-        for (size_t k = 0; k < kmax; ++k) zsq[js * kmax + (k % 4) * (kmax / 4) + k / 4] = zsT[js * kmax + k];
-    if ((rc = dev_grow(d.zsq, d.cap_zsq, zsq.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zsq, zsq.data(), zsq.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = dev_grow(d.zc, d.cap_zc, zc.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zc, zc.data(), zc.size() * sizeof(double), hipMemcpyHostToDevice));
-    d.zs_cmax = cmax;
-    d.zs_len = (uint32_t)(kmax * nj);
-    d.zs_kmax = (uint32_t)kmax;
-    // no fused kernel on the wide path, for a chunked series or Q rows built in HBM
-    if (eng->wide || eng->qglobal || !eng->chunks.empty() || eng->jit_plan.vlds) return MDP_OK;
-    // the fused kernel's column tables: one contiguous image it copies to LDS
-    // (with zpad, all KZ zs rows, zero past kmax: the kernel reads them unmasked)
-    const MdpJitPlan &pl = eng->jit_plan;
-    const size_t kimg = pl.zpad ? std::max<size_t>(kmax, std::max<uint32_t>(8u, pl.kzmax)) : kmax;
-    const size_t ct = ((size_t)pl.off_zs + kimg * nj + 127) & ~(size_t)127;
-    std::vector<double> img(ct, 0.0);
-    for (uint32_t js = 0; js < nj; ++js)  // (the columns of j marked +inf: pressure fmin(c inf, 1) = 1.0)
-        for (uint32_t b = 0; b < eng->nvar; ++b)
-            img[(size_t)js * eng->nvar + b] = ((eng->cj_bits[js] >> (eng->nvar - 1 - b)) & 1u)
-                                                   ? HUGE_VAL
-                                                   : eng->Sj[(size_t)js * n + eng->var_cols[b]];
-    uint2 *it = (uint2 *)(img.data() + pl.off_it);
-    for (uint32_t i = 0; i < eng->nitems; ++i) {
-        const uint32_t r = eng->itemRow[i];
-        it[i] = make_uint2(eng->itemB[i] | ((r & 0xffu) << 24), eng->cj_bits[r] | ((r >> 8) << 24));
-    }
-    memcpy(img.data() + pl.off_qs, eng->qstart.data(), eng->qstart.size() * sizeof(uint32_t));
-    memcpy(img.data() + pl.off_zc, zc.data(), (size_t)nj * kZTerms * sizeof(double));
-    if (!eng->qitem.empty())
-        memcpy(img.data() + pl.off_qi, eng->qitem.data(), eng->qitem.size() * sizeof(uint32_t));
-    {
-        const std::vector<uint32_t> rq = mdp_jit_reversed_index(pl.udesc, pl.ldQ);
-        memcpy(img.data() + pl.off_rq, rq.data(), rq.size() * sizeof(uint32_t));
-    }
-    for (size_t k = 0; k < kmax; ++k)  // zs pairs (k, k+1) of a row adjacent: one ds_read_b128
-        for (uint32_t js = 0; js < nj; ++js) img[pl.off_zs + ((k / 2) * nj + js) * 2 + (k & 1)] = zs[k * nj + js];
-    if ((rc = dev_grow(d.coltab, d.cap_coltab, ct))) return rc;
-    HIP_TRY(hipMemcpy(d.coltab, img.data(), ct * sizeof(double), hipMemcpyHostToDevice));
-    d.ct_len = (uint32_t)ct;
+    if (eng->mma && (rc = for_mma(eng, [&](auto npm) { return set_lds_limit(k_fwd_mma<npm()>, mma_lds(eng)); }))) return rc;
+    if (eng->mmt && (rc = for_mmt(eng, [&](auto rt, auto rows, auto db) {
+            return set_lds_limit(k_fwd_mmt<rt(), rows(), db()>, mmt_lds(eng));
+        })))
+        return rc;
+    if (eng->hs && (rc = for_hs(eng, [&](auto rt, auto nb, auto nw) {
+            return set_lds_limit(k_fwd_hs<rt(), nb(), nw()>, hs_lds(eng));
+        })))
+        return rc;
+    return set_lds_limit(k_fwd_wide, wide_lds(eng));
+}
+
+// the c tables of a grid plan onto the device
+int upload_ctables(DevCtx &d)
+{
+    const MdpCTables &t = d.ct;
+    int rc;
+    if ((rc = dev_grow(d.zs, d.cap_zs, t.zs.size()))) return rc;
+    HIP_TRY(hipMemcpy(d.zs, t.zs.data(), t.zs.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = dev_grow(d.zsq, d.cap_zsq, t.zsq.size()))) return rc;
+    HIP_TRY(hipMemcpy(d.zsq, t.zsq.data(), t.zsq.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = dev_grow(d.zc, d.cap_zc, t.zc.size()))) return rc;
+    HIP_TRY(hipMemcpy(d.zc, t.zc.data(), t.zc.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (t.coltab.empty()) return MDP_OK;
+    if ((rc = dev_grow(d.coltab, d.cap_coltab, t.coltab.size()))) return rc;
+    HIP_TRY(hipMemcpy(d.coltab, t.coltab.data(), t.coltab.size() * sizeof(double), hipMemcpyHostToDevice));
     return MDP_OK;
 }
 
@@ -2387,10 +2338,6 @@ int jit_load(mdp_engine *eng, DevCtx &d, int variant)
     return MDP_OK;
 }
 
-constexpr size_t kWidePgBytes = 256ull << 20;  // wide path: item-factor chunk
-constexpr size_t kHsPgBytes = 2048ull << 20;   // k_fwd_hs: item factors of the columns of one launch
-constexpr size_t kWideVBytes = 1ull << 30;     // wide path: state-vector scratch
-
 int upload_binomials()  // into the current device's constant bank
 {
     double h[kMaxDeg + 1][kMaxDeg + 1] = {};
@@ -2434,17 +2381,10 @@ int init_generic(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(d.stream));
     (void)hipFree(dM);
-    if (eng->coef_lds > 64 * 1024) {
-        const void *fns[] = {
-            (const void *)k_coefs<true, true, 8>,   (const void *)k_coefs<true, true, 16>,
-            (const void *)k_coefs<true, true, 24>,  (const void *)k_coefs<false, true, 8>,
-            (const void *)k_coefs<false, true, 16>, (const void *)k_coefs<false, true, 24>,
-            (const void *)k_coefs<false, false, 8>, (const void *)k_coefs<false, false, 16>,
-            (const void *)k_coefs<false, false, 24>};
-        for (const void *fn : fns)
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)eng->coef_lds));
-    }
+    if (eng->coef_lds > 64 * 1024)
+        return for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) {
+            return set_lds_limit(k_coefs<ldsz(), ldsp(), nv()>, eng->coef_lds);
+        });
     return MDP_OK;
 }
 
@@ -2459,17 +2399,9 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
     // does not load the library's precompiled kernels at all (CLI start-up)
     if (!eng->jit && !eng->wide && (rc = init_generic(eng, d, p))) return rc;
     if (eng->jit || eng->wide) {
-        std::vector<double> sv((size_t)eng->nj * eng->nvar + 1, 0.0);
-        for (uint32_t js = 0; js < eng->nj; ++js)
-            for (uint32_t b = 0; b < eng->nvar; ++b)
-                sv[(size_t)js * eng->nvar + b] = ((eng->cj_bits[js] >> (eng->nvar - 1 - b)) & 1u)
-                                                      ? HUGE_VAL  // column of j: pC = fmin(c inf, 1) = 1.0
-                                                      : eng->Sj[(size_t)js * eng->n + eng->var_cols[b]];
-        std::vector<uint2> items(eng->nitems + 1, make_uint2(0u, 0u));
-        for (uint32_t i = 0; i < eng->nitems; ++i) {
-            const uint32_t r = eng->itemRow[i];
-            items[i] = make_uint2(eng->itemB[i] | ((r & 0xffu) << 24), eng->cj_bits[r] | ((r >> 8) << 24));
-        }
+        std::vector<double> sv;
+        std::vector<uint2> items;
+        mdp_plan_item_tables(eng, sv, items);
         std::vector<uint32_t> qitem = eng->qitem;
         qitem.push_back(0u);
         if ((rc = dev_upload(d.sv, sv)) || (rc = dev_upload(d.items, items)) ||
@@ -2484,14 +2416,10 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
                  (rc = dev_upload(d.mma_wplan, eng->mma_wplan)) ||
                  (rc = dev_upload(d.mma_desc, eng->mma_desc)) || (rc = dev_upload(d.mma_dbase, eng->mma_dbase))))
                 return rc;
-            if (eng->mma)
-                HIP_TRY(hipFuncSetAttribute(mma_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mma_lds(eng)));
             if (eng->mmt &&
                 ((rc = dev_upload(d.mmt_kt, eng->mmt_kt)) || (rc = dev_upload(d.mmt_ktile, eng->mmt_ktile)) ||
                  (rc = dev_upload(d.mmt_wplan, eng->mmt_wplan)) || (rc = dev_upload(d.mmt_cidx, eng->mmt_cidx))))
                 return rc;
-            if (eng->mmt)
-                HIP_TRY(hipFuncSetAttribute(mmt_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mmt_lds(eng)));
             if (eng->hs &&
                 ((rc = dev_upload(d.hs_kt, eng->hs_kt)) || (rc = dev_upload(d.hs_cidx, eng->hs_cidx)) ||
                  (rc = dev_upload(d.hs_pbase, eng->hs_pbase)) || (rc = dev_upload(d.hs_ppos, eng->hs_ppos)) ||
@@ -2500,11 +2428,7 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
                  (rc = dev_upload(d.hs_wplan, eng->hs_wplan)) || (rc = dev_upload(d.hs_pass, eng->hs_pass)) ||
                  (rc = dev_upload(d.hs_dpk, eng->hs_dpk))))
                 return rc;
-            if (eng->hs)
-                HIP_TRY(hipFuncSetAttribute(hs_kernel(eng), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_lds(eng)));
-            HIP_TRY(hipFuncSetAttribute((const void *)k_fwd_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)wide_lds(eng)));
-            return MDP_OK;
+            return wide_lds_limits(eng);
         }
         // (k_qrows' LDS attribute is set before its first launch and the
         // forward kernel loaded by set_grid_dev: nothing here loads a module)
@@ -2519,13 +2443,11 @@ int qrows_attrs(const mdp_engine *eng, DevCtx &d)
     if (d.qrows_attr_set) return MDP_OK;
     const size_t lds_max = qrows_lds(eng, kQrowsMaxC);
     if (lds_max > 64 * 1024)
-        for (const void *fn : {(const void *)k_qrows<8, true, 1>, (const void *)k_qrows<8, false, 1>,
-                               (const void *)k_qrows<16, false, 1>, (const void *)k_qrows<24, false, 1>,
-                               (const void *)k_qrows<8, true, 2>, (const void *)k_qrows<8, false, 2>,
-                               (const void *)k_qrows<16, false, 2>, (const void *)k_qrows<8, true, 4>,
-                               (const void *)k_qrows<8, false, 4>})
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)std::min(lds_max, kQrowsLdsMax)));
+        for (uint32_t cb = 1; cb <= kQrowsMaxC; cb *= 2)  // every instantiation a grid of this engine may run
+            if (int rc = for_qrows(eng, cb, [&](auto nv, auto ex, auto c) {
+                    return set_lds_limit(k_qrows<nv(), ex(), c()>, std::min(lds_max, kQrowsLdsMax));
+                }))
+                return rc;
     d.qrows_attr_set = true;
     return MDP_OK;
 }
@@ -2554,166 +2476,55 @@ void free_device(DevCtx &d)
     if (d.stream) (void)hipStreamDestroy(d.stream);
 }
 
-// The point list of forward kernels with `epl` points per lane: the e rows
-// whose ratio form is s (x < y, x = min(e, 1), y = 1 - x, as the kernel
-// computes them), then those of form t, each run padded to a multiple of epl
-// with duplicates of its last row (bit 31: computed, not stored), so every
-// lane's points share one form and so their coefficient reads.  A sorted
-// grid keeps its order (the kernels' stores stay coalesced).
-std::vector<uint32_t> point_list(const double *e, uint32_t ne, uint32_t epl)
-{
-    std::vector<uint32_t> s_rows, t_rows;
-    for (uint32_t i = 0; i < ne; ++i) {
-        const double x = e[i] > 1.0 ? 1.0 : e[i], y = 1.0 - x;
-        (x >= y ? t_rows : s_rows).push_back(i);
-    }
-    std::vector<uint32_t> pl;
-    pl.reserve(ne + 2 * epl);
-    for (const auto *rows : {&s_rows, &t_rows}) {
-        pl.insert(pl.end(), rows->begin(), rows->end());
-        while (!rows->empty() && pl.size() % epl) pl.push_back(rows->back() | 0x80000000u);
-    }
-    if (pl.empty()) pl.assign(epl, 0x80000000u);
-    return pl;
-}
-
+// A new grid: plan it on the host (mdp_plan_grid: the refusals, the kernel
+// variant, the point list, the chunk widths, every buffer size), then grow
+// and upload what the plan says and load the forward kernel it names.
 int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const double *c,
                  uint32_t nc)
 {
-    // c < 0 is refused: the item factors are folded as |n_b - pC_b| (k_qrows
-    // phase 2, k_witems, the fused prologue), which equals the reference's
-    // (1 - piold)(1 - pC) + piold pC (main_MIDASPOM.c:40) only for pC >= 0;
-    // at c < 0 the reference's pC = min(1, c S) is negative, not a probability
-    // (and a NaN or infinite c: the pressures min(1, c S) are then clamped
-    // by minNum, which drops NaN, where the reference would carry it)
-    for (uint32_t i = 0; i < nc; ++i)
-        if (!(c[i] >= 0.0) || std::isinf(c[i]))
-            return mdp_set_error(MDP_EINVAL, "colonisation rate c[%u] = %g (the engine takes finite c >= 0)", i, c[i]);
     HIP_TRY(hipSetDevice(d.device));
-    int rc;
-    if ((rc = dev_grow(d.e, d.cap_e, ne)) || (rc = dev_grow(d.c, d.cap_c, nc))) return rc;
-    d.ne_sform = 0;
-    for (uint32_t i = 0; i < ne; ++i) {  // the kernels' form test: x = min(e, 1), s-form where x < 1 - x
-        const double x = e[i] > 1.0 ? 1.0 : e[i];
-        d.ne_sform += x < 1.0 - x;
+    if (!d.ncu && eng->jit && !eng->wide) {
+        int v = 0;
+        d.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && v > 0
+                    ? (uint32_t)v : 256u;
     }
-    const bool qglobal = eng->wide || eng->qglobal;  // Q rows from k_zrows + k_witems + k_wq
-    if (eng->wide || eng->jit) {
-        double cmax = eng->cbound;
-        for (uint32_t i = 0; i < nc; ++i) cmax = std::isnan(c[i]) ? c[i] : std::max(cmax, std::fabs(c[i]));
-        if ((rc = dev_grow(d.Qrow, d.cap_qrow, (size_t)nc * eng->ldQ))) return rc;
-        if (!(d.zs_cmax == cmax) && (rc = upload_qrows_tables(eng, d, cmax))) return rc;
+    MdpGridPlan g;
+    int rc = mdp_plan_grid(eng, d.ct, e, ne, c, nc, d.ncu, g);
+    if (g.tables_new) {  // (also when the plan then refused the grid: d.ct holds the new bound)
+        const int urc = upload_ctables(d);
+        if (urc) {
+            d.ct.cmax = -1.0;  // nothing usable on the device: the next grid builds them again
+            return urc;
+        }
     }
-    if (qglobal) {
-        if ((rc = dev_grow(d.Zg, d.cap_zg, (size_t)nc * eng->nj + 1))) return rc;
-        // k_zrows stages kZRows rows of explicit columns in dynamic LDS
-        const size_t zl = (size_t)kZRows * d.zs_kmax * sizeof(double);
-        if (zl > kQrowsLdsMax)
-            return mdp_set_error(MDP_EUNSUPPORTED, "%u explicit colonisation columns per row exceed the LDS of k_zrows",
-                                 d.zs_kmax);
-        if (zl > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)k_zrows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zl));
-        // c values per k_witems launch: item factors within kWidePgBytes
-        const size_t cap_c = std::max<size_t>(1, std::min<size_t>(nc, 65535));
-        d.wide_cb_items = (uint32_t)std::min(cap_c, std::max<size_t>(1, kWidePgBytes / 8 / std::max<size_t>(1, eng->nitems)));
-        if (const char *cv = eng->opts.get("MDP_WIDE_CB"))  // tests: force several launches per slot
-            d.wide_cb_items = std::min(d.wide_cb_items, (uint32_t)std::max(1, atoi(cv)));
-        if (eng->hs) {  // k_fwd_hs reads the item factors of its columns: rows of nitems + 1 (zero slot)
-            const size_t ldp = (size_t)eng->nitems + 1;
-            d.wide_cb_items = (uint32_t)std::min<size_t>(nc, std::max<size_t>(1, kHsPgBytes / 8 / ldp));
-            if (const char *cv = eng->opts.get("MDP_WIDE_CB"))
-                d.wide_cb_items = std::min(d.wide_cb_items, (uint32_t)std::max(1, atoi(cv)));
-            if ((rc = dev_grow(d.Pg, d.cap_pg, (size_t)d.wide_cb_items * ldp))) return rc;
-            HIP_TRY(hipMemset(d.Pg, 0, (size_t)d.wide_cb_items * ldp * sizeof(double)));
-        } else if ((rc = dev_grow(d.Pg, d.cap_pg, (size_t)d.wide_cb_items * eng->nitems + 1))) {
+    if (rc) return rc;
+    if ((rc = dev_grow(d.e, d.cap_e, ne)) || (rc = dev_grow(d.c, d.cap_c, nc)) ||
+        (g.n_qrow && (rc = dev_grow(d.Qrow, d.cap_qrow, g.n_qrow))) || (g.n_zg && (rc = dev_grow(d.Zg, d.cap_zg, g.n_zg))) ||
+        (g.n_pg && (rc = dev_grow(d.Pg, d.cap_pg, g.n_pg))) || (g.n_v && (rc = dev_grow(d.V, d.cap_v, g.n_v))) ||
+        (g.n_vscr && (rc = dev_grow(d.vscr, d.cap_vscr, g.n_vscr))) || (g.n_zpv && (rc = dev_grow(d.ZPV, d.cap_zpv, g.n_zpv))) ||
+        (g.n_r && (rc = dev_grow(d.R, d.cap_r, g.n_r))) || (g.n_gpart && (rc = dev_grow(d.gpart, d.cap_gpart, g.n_gpart))))
+        return rc;
+    if (g.pg_zero && g.n_pg) HIP_TRY(hipMemset(d.Pg, 0, g.n_pg * sizeof(double)));
+    if (g.zrows_lds > 64 * 1024 && (rc = set_lds_limit(k_zrows, g.zrows_lds))) return rc;
+    if (!g.plist_identity) {
+        if ((rc = dev_grow(d.plist, d.cap_plist, g.plist.size())) || (rc = dev_grow(d.elist, d.cap_elist, g.elist.size())))
             return rc;
-        }
+        HIP_TRY(hipMemcpy(d.plist, g.plist.data(), g.plist.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.elist, g.elist.data(), g.elist.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (eng->wide) {
-        // c values per k_fwd_wide launch: the two state vectors of every
-        // point of a launch within kWideVBytes (k_fwd_mma keeps them in LDS)
-        const size_t ne_pad = (size_t)std::max<uint32_t>(1u, (ne + kBlock - 1) / kBlock) * kBlock;
-        const size_t cap_c = std::max<size_t>(1, std::min<size_t>(nc, 65535));
-        d.wide_cb_fwd = (uint32_t)std::min(cap_c, std::max<size_t>(1, kWideVBytes / 8 / (2 * (size_t)eng->npmax * ne_pad)));
-        if (const char *cv = eng->opts.get("MDP_WIDE_CB"))
-            d.wide_cb_fwd = std::min(d.wide_cb_fwd, (uint32_t)std::max(1, atoi(cv)));
-        if (!eng->mma && !eng->mmt && (rc = dev_grow(d.V, d.cap_v, 2 * (size_t)eng->npmax * d.wide_cb_fwd * ne_pad))) return rc;
-    } else if (eng->jit) {
-        // forward kernels with several points per lane read them from a list
-        // that puts only e rows of one ratio form in a lane (spom_jit.cpp)
-        const uint32_t epl_f = (uint32_t)eng->jit_epl;  // the fused variant's (jit_build: the reading variant's)
-        const uint32_t epl_max = std::max<uint32_t>((uint32_t)eng->jit_epl, epl_f);
-        d.plist_identity = true;
-        if (epl_max > 1) {
-            const std::vector<uint32_t> pl = point_list(e, ne, epl_max);
-            for (uint32_t i = 0; i < pl.size() && d.plist_identity; ++i) d.plist_identity = pl[i] == i;
-            if (!d.plist_identity) {  // an identity list is not uploaded: the kernels use the position
-                if ((rc = dev_grow(d.plist, d.cap_plist, pl.size()))) return rc;
-                HIP_TRY(hipMemcpy(d.plist, pl.data(), pl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                std::vector<double> el(pl.size() + 1);
-                for (size_t i = 0; i < pl.size(); ++i) el[i] = ne ? e[pl[i] & 0x7fffffffu] : 0.0;  // (no rows: never run)
-                el[pl.size()] = ne ? e[0] : 0.0;
-                if ((rc = dev_grow(d.elist, d.cap_elist, el.size()))) return rc;
-                HIP_TRY(hipMemcpy(d.elist, el.data(), el.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-            d.nlist = (uint32_t)pl.size();
-        } else {
-            d.nlist = ne;
-        }
-        d.nlist_epl = epl_max;
-        // one e block per c column and a small per-c problem: the forward
-        // kernel computes its column's Q itself (one launch); never for a
-        // chunked series or Q rows built in HBM
-        const uint32_t nl = eng->jit_epl > 1 ? d.nlist : ne;
-        const uint32_t gy = (nl + eng->jit_kblock * eng->jit_epl - 1) / (eng->jit_kblock * eng->jit_epl);
-        d.fused = eng->chunks.empty() && !eng->qglobal && !eng->jit_plan.vlds && fused_lds(eng, d.ct_len) <= kFusedLdsMax &&
-                  d.zs_kmax <= eng->jit_plan.kzmax && (eng->fused_mode == 1 || (eng->fused_mode == -1 && gy <= 1));
-        // a column of a tall grid (an even number of e blocks, so no lane more
-        // idles) in half the blocks of twice the threads: each block stages
-        // its column's Q row once (config 3: forward 45.7-46.9 -> 44.3 us) --
-        // while that still leaves a block for every CU (a column slab of
-        // config 3, 1 024 x 128: 128 tall blocks would idle half the chip)
-        if (!d.ncu) {
-            int v = 0;
-            d.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && v > 0
-                        ? (uint32_t)v : 256u;
-        }
-        d.tall = !d.fused && eng->chunks.empty() && !eng->jit_plan.vlds && !eng->jit_shape_env &&
-                 eng->jit_kblock * 2 == (uint32_t)kJitKblockTall && gy >= 2 && gy % 2 == 0 &&
-                 (uint64_t)nc * (gy / 2) >= d.ncu;
-        if ((rc = jit_load(eng, d, d.fused ? 1 : d.tall ? 2 : 0))) return rc;
-        if (!eng->chunks.empty()) {  // the state vectors handed between chunks
-            d.ldv = gy * eng->jit_kblock * (uint32_t)eng->jit_epl;
-            uint32_t nb = 1;  // most states at a chunk boundary
-            for (size_t i = 1; i < eng->chunks.size(); ++i) nb = std::max(nb, eng->chunks[i].np[0]);
-            if ((rc = dev_grow(d.vscr, d.cap_vscr, (size_t)nb * nc * d.ldv))) return rc;
-        }
-        // c values per k_qrows workgroup: enough workgroups for every CU, within the LDS
-        uint32_t cb = nc >= 1024 ? 4u : nc >= 512 ? 2u : 1u;  // power of two
-        cb = std::min(cb, eng->nvar <= 8 ? 4u : eng->nvar <= 16 ? 2u : 1u);  // registers (k_qrows)
-        while (cb > 1 && qrows_lds(eng, cb) > kQrowsLdsMax) cb >>= 1;
-        d.qrows_cb = cb;
-    } else if ((rc = dev_grow(d.ZPV, d.cap_zpv, (size_t)nc * (eng->nvar + 1) * eng->nstates)) ||
-               (rc = dev_grow(d.R, d.cap_r, (size_t)nc * ldR_of(eng)))) {
-        return rc;
+    if (eng->jit && !eng->wide) {
+        if ((rc = jit_load(eng, d, g.variant))) return rc;
+        mdp_plan_fwd_launch(eng, d.ct, ne, nc, g);  // (the variant's shape is settled once it is built)
     }
-    if (!eng->jit && !eng->wide && !eng->lds_part &&
-        (rc = dev_grow(d.gpart, d.cap_gpart, (size_t)nc * eng->partP.size() * (eng->nvar + 1))))
-        return rc;
-    if (eng->diag) {
-        d.nst[0] = eng->jit ? (size_t)nc
-                            : (size_t)((eng->nstates + kZpvJ - 1) / kZpvJ) * ((nc + kZpvCT - 1) / kZpvCT);
-        d.nst[1] = nc;
-        d.nst[2] = (size_t)nc * ((ne + kBlock - 1) / kBlock);  // >= the JIT grid (EPL >= 1)
-        for (int k = 0; k < 3; ++k) {
-            if ((rc = dev_grow(d.stamps[k], d.cap_st[k], d.nst[k] * kStampSlots))) return rc;
-            HIP_TRY(hipMemset(d.stamps[k], 0, d.cap_st[k] * sizeof(unsigned long long)));
-        }
+    for (int k = 0; k < 3 && eng->diag; ++k) {
+        if ((rc = dev_grow(d.stamps[k], d.cap_st[k], g.nst[k] * kStampSlots))) return rc;
+        HIP_TRY(hipMemset(d.stamps[k], 0, d.cap_st[k] * sizeof(unsigned long long)));
     }
     if (ne) HIP_TRY(hipMemcpy(d.e, e, ne * sizeof(double), hipMemcpyHostToDevice));
     if (nc) HIP_TRY(hipMemcpy(d.c, c, nc * sizeof(double), hipMemcpyHostToDevice));
     d.ne = ne;
     d.nc = nc;
+    d.plan = std::move(g);
     return MDP_OK;
 }
 
@@ -2760,42 +2571,31 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
 {
     int rc;
     if (eng->jit) {
-        // threads per e block: kb (x 2 with the split state-vector kernel)
-        const uint32_t kb = d.fused ? eng->jit_kblock_fused : d.tall ? (uint32_t)kJitKblockTall : eng->jit_kblock;
-        const uint32_t pro = d.fused ? eng->jit_pro_fused : 1u;
-        const uint32_t epl = d.fused ? (uint32_t)eng->jit_epl_fused : (uint32_t)eng->jit_epl;
-        const uint32_t spl = eng->jit_plan.vlds && (eng->jit_plan.vsplit == 2 || eng->jit_plan.vsplit == 4)
-                                 ? (uint32_t)eng->jit_plan.vsplit : 1u;
-        // several points per lane: the grid's point list (set_grid_dev)
-        const uint32_t *plist = epl > 1 && !d.plist_identity ? d.plist : nullptr;
-        uint32_t nlist = epl > 1 ? d.nlist : d.ne;
-        if (epl > 1 && ((!plist && !d.plist_identity) || d.nlist_epl % epl))
-            return mdp_set_error(MDP_EINVAL, "no point list for %u points per lane", epl);
-        const uint64_t gy = (nlist + kb * epl - 1) / (kb * epl);
-        const uint32_t fc = d.fused ? (uint32_t)eng->jit_plan.fused_cols : 1u;
-        const uint64_t nb = gy * ((d.nc + fc - 1) / fc);  // e blocks x column groups
-        if (nb * kb * fc * spl > 0xffffffffull)
+        // the launch as the grid plan shaped it (mdp_plan_fwd_launch)
+        const MdpGridPlan &g = d.plan;
+        if (g.fwd_threads > 0xffffffffull)
             return mdp_set_error(MDP_EUNSUPPORTED, "grid %u x %u too large", d.ne, d.nc);
+        const uint32_t nthreads = (uint32_t)(g.fwd_threads * g.fwd_pro);
         // mdp_fwd_jit's parameters (spom_jit.h declares them once, for the
         // generated signature and for this struct)
         MdpFwdJitArgs a;
-        a.tab = d.fused ? d.coltab : d.Qrow;  // the table the variant stages first
+        a.tab = g.fused ? d.coltab : d.Qrow;  // the table the variant stages first
         a.cvals = d.c;
-        a.evals = plist ? d.elist : d.e;  // a listed kernel reads e by list position
-        a.ct_len = d.ct_len;
-        a.nlist = nlist;
+        a.evals = g.fwd_listed ? d.elist : d.e;  // a listed kernel reads e by list position
+        a.ct_len = d.ct.ct_len;
+        a.nlist = g.fwd_nlist;
         a.ne = d.ne;
         a.nc = d.nc;
-        a.plist = plist;
-        a.nblk = (uint32_t)nb;
-        a.kmax = d.zs_kmax;
+        a.plist = g.fwd_listed ? d.plist : nullptr;
+        a.nblk = (uint32_t)g.fwd_nblk;
+        a.kmax = d.ct.kmax;
         a.one = 1;
         a.out = out;
         a.ld_out = os.se;
         a.out_cs = os.sc;
         a.prior0 = eng->prior0;
         a.vscr = d.vscr;
-        a.ldv = d.ldv;
+        a.ldv = g.ldv;
         a.stamps = d.stamps[2];
         auto args = a.params();
         static_assert(std::tuple_size<decltype(args)>::value == 19, "one kernelParams entry per parameter of mdp_fwd_jit");
@@ -2805,19 +2605,18 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
                 return mdp_set_error(MDP_EHIP, "forward chunks not loaded (%zu of %zu)", nch, eng->chunks.size());
             for (size_t i = 0; i < nch; ++i) {
                 a.qidx = d.cqidx[i];  // the chunk's gather list (args points at the member)
-                HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], (uint32_t)(nb * kb * spl), 1, 1, kb * spl, 1, 1, 0, s,
+                HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], nthreads, 1, 1, g.fwd_block, 1, 1, 0, s,
                                                  args.data(), nullptr, i == 0 ? t_kev.start : nullptr,
                                                  i + 1 == nch ? t_kev.stop : nullptr, 0));
             }
-            note_launch(eng, d, "mdp_fwd_jit<reading,maxA%u,chunks%zu%s>", eng->maxA, nch,
+            note_launch(eng, d, kFmtJitChunks, eng->maxA, nch,
                         eng->chunks[0].qidx.empty() ? "" : ",gather");
             return MDP_OK;
         }
-        const uint32_t dyn = d.fused ? (d.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
-        HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[d.fused ? 1 : d.tall ? 2 : 0], (uint32_t)(nb * kb * fc * spl * pro), 1, 1,
-                                         kb * fc * spl * pro, 1, 1, dyn, s, args.data(), nullptr, t_kev.start, t_kev.stop, 0));
-        note_launch(eng, d, "mdp_fwd_jit<%s,maxA%u>", d.fused ? "fused" : "reading", eng->maxA);
-        if (d.tall) note_launch(eng, d, "mdp_fwd_jit<reading,kb%d>", kJitKblockTall);
+        HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[g.variant], nthreads, 1, 1, g.fwd_block, 1, 1, g.fwd_lds, s, args.data(),
+                                         nullptr, t_kev.start, t_kev.stop, 0));
+        note_launch(eng, d, kFmtJit, g.fused ? "fused" : "reading", eng->maxA);
+        if (g.tall) note_launch(eng, d, kFmtJitTall, kJitKblockTall);
         return MDP_OK;
     }
     switch (eng->variant / 100) {
@@ -2833,30 +2632,15 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
     return MDP_OK;
 }
 
-template <bool LDSZ, bool LDSP, int NV>
-void launch_coefs_nv(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
-{
-    note_launch(eng, d, "k_coefs<%d,%d,%d>", (int)LDSZ, (int)LDSP, NV);
-    MDP_LAUNCH((k_coefs<LDSZ, LDSP, NV>), dim3(d.nc), dim3(kBlock), eng->coef_lds, s, d.ZPV,
-                       eng->nstates, eng->nvar, d.pairA, d.pairB, d.pairOff, d.pairPart0, eng->npairs,
-                       d.partP, d.partK0, (uint32_t)eng->partP.size(), eng->ncoef, d.udesc,
-                       eng->nuses, eng->deg, d.R, ldR_of(eng), d.gpart, d.stamps[1]);
-}
-
-template <bool LDSZ, bool LDSP>
-void launch_coefs_lds(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
-{
-    const uint32_t nv = eng->nvar;
-    if (nv <= 8) launch_coefs_nv<LDSZ, LDSP, 8>(eng, d, s);
-    else if (nv <= 16) launch_coefs_nv<LDSZ, LDSP, 16>(eng, d, s);
-    else launch_coefs_nv<LDSZ, LDSP, 24>(eng, d, s);
-}
-
 int launch_coefs(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
 {
-    if (eng->lds_zpv) launch_coefs_lds<true, true>(eng, d, s);
-    else if (eng->lds_part) launch_coefs_lds<false, true>(eng, d, s);
-    else launch_coefs_lds<false, false>(eng, d, s);
+    for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) {
+        note_launch(eng, d, kFmtCoefs, (int)ldsz(), (int)ldsp(), nv());
+        MDP_LAUNCH((k_coefs<ldsz(), ldsp(), nv()>), dim3(d.nc), dim3(kBlock), eng->coef_lds, s, d.ZPV, eng->nstates,
+                   eng->nvar, d.pairA, d.pairB, d.pairOff, d.pairPart0, eng->npairs, d.partP, d.partK0,
+                   (uint32_t)eng->partP.size(), eng->ncoef, d.udesc, eng->nuses, eng->deg, d.R, ldR_of(eng), d.gpart,
+                   d.stamps[1]);
+    });
     HIP_TRY(hipGetLastError());
     return MDP_OK;
 }
@@ -2871,19 +2655,17 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
     if (ev.start) HIP_TRY(hipEventRecord(ev.start, s));
     auto witems = [&](uint32_t c0, uint32_t n, uint32_t ldp) {
         const dim3 gi((eng->nitems + kBlock - 1) / kBlock, n);
-#define MDP_WITEMS(NV) \
-    do { note_launch(eng, d, "k_witems<%d>", NV); \
-    hipLaunchKernelGGL((k_witems<NV>), gi, dim3(kBlock), 0, s, d.c, d.nc, c0, eng->nvar, d.Zg, d.sv, eng->nitems, d.items, d.Pg, ldp); } while (0)
-        if (eng->nvar <= 8) MDP_WITEMS(8);
-        else if (eng->nvar <= 16) MDP_WITEMS(16);
-        else MDP_WITEMS(24);
-#undef MDP_WITEMS
+        for_nv(eng, [&](auto nv) {
+            note_launch(eng, d, kFmtWitems, nv());
+            hipLaunchKernelGGL((k_witems<nv()>), gi, dim3(kBlock), 0, s, d.c, d.nc, c0, eng->nvar, d.Zg, d.sv, eng->nitems,
+                               d.items, d.Pg, ldp);
+        });
     };
     if (eng->hs) {
         // slot 1: the item factors of every column when they fit one Pg
         // block (kHsPgBytes), else nothing; slot 2: k_fwd_hs, or per column
         // chunk k_witems then k_fwd_hs
-        const uint32_t cb = d.wide_cb_items, ldp = eng->nitems + 1;
+        const uint32_t cb = d.plan.wide_cb_items, ldp = eng->nitems + 1;
         const bool one = cb >= d.nc;
         if (k == 1) {
             if (one && eng->nitems) witems(0, d.nc, ldp);
@@ -2894,20 +2676,17 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
                 if (!one && eng->nitems) witems(c0, n, ldp);
                 const uint64_t nbk = (uint64_t)npb * n;
                 if (nbk > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_hs workgroups", (unsigned long long)nbk);
-                note_launch(eng, d, "k_fwd_hs<%u,%u>", rt, nb);
-#define MDP_HS(RT, NB, NW) \
-    hipLaunchKernelGGL((k_fwd_hs<RT, NB, NW>), dim3((uint32_t)nbk), dim3(NW * 64), hs_lds(eng), s, d.Pg, ldp, c0, d.np_d, \
-                       d.hs_kt, d.hs_cidx, d.hs_wplan, d.hs_pass, d.hs_pbase, d.hs_ppos, d.hs_dpos, \
-                       d.hs_dbase, d.hs_dpk, d.hs_pk, eng->tmax, eng->prior0, d.e, d.ne, out, os.se, os.sc, eng->hs_probe)
-                if (nb == 8 && eng->hs_nw == 8) MDP_HS(2, 8, 8);
-                else if (nb == 8) MDP_HS(4, 8, 16);
-                else if (nb == 9) MDP_HS(2, 9, 16);
-                else MDP_HS(1, 10, 16);
-#undef MDP_HS
+                note_launch(eng, d, kFmtHs, rt, nb);
+                for_hs(eng, [&](auto RT, auto NB, auto NW) {
+                    hipLaunchKernelGGL((k_fwd_hs<RT(), NB(), NW()>), dim3((uint32_t)nbk), dim3(NW() * 64), hs_lds(eng), s,
+                                       d.Pg, ldp, c0, d.np_d, d.hs_kt, d.hs_cidx, d.hs_wplan, d.hs_pass, d.hs_pbase,
+                                       d.hs_ppos, d.hs_dpos, d.hs_dbase, d.hs_dpk, d.hs_pk, eng->tmax, eng->prior0, d.e,
+                                       d.ne, out, os.se, os.sc, eng->hs_probe);
+                });
             }
         }
     } else if (k == 1) {
-        const uint32_t cb = d.wide_cb_items;
+        const uint32_t cb = d.plan.wide_cb_items;
         for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
             const uint32_t n = std::min(cb, d.nc - c0);
             witems(c0, n, eng->nitems);
@@ -2921,34 +2700,27 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
         const bool db = mmt_shape(eng).db;
         const uint64_t nb = (uint64_t)npb * d.nc;
         if (nb > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_mmt workgroups", (unsigned long long)nb);
-        note_launch(eng, d, "k_fwd_mmt<%u,%u,%s>", rt, rows, db ? "2buf" : "1buf");
-#define MDP_MMT(RT, ROWS, DB) \
-    hipLaunchKernelGGL((k_fwd_mmt<RT, ROWS, DB>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, \
-                       d.np_d, d.mmt_kt, d.mmt_cidx, d.mmt_ktile, d.mmt_wplan, eng->tmax, eng->prior0, d.e, d.ne, \
-                       eng->maxA, out, os.se, os.sc)
-        if (rows == 128) MDP_MMT(4, 128, true);
-        else if (rows == 256) MDP_MMT(2, 256, false);
-        else if (rows == 512) MDP_MMT(2, 512, false);
-        else MDP_MMT(1, 1024, false);
-#undef MDP_MMT
+        note_launch(eng, d, kFmtMmt, rt, rows, db ? "2buf" : "1buf");
+        for_mmt(eng, [&](auto RT, auto ROWS, auto DB) {
+            hipLaunchKernelGGL((k_fwd_mmt<RT(), ROWS(), DB()>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s,
+                               d.Qrow, (uint32_t)eng->ldQ, d.np_d, d.mmt_kt, d.mmt_cidx, d.mmt_ktile, d.mmt_wplan,
+                               eng->tmax, eng->prior0, d.e, d.ne, eng->maxA, out, os.se, os.sc);
+        });
     } else if (eng->mma) {  // round 5's matrix-core forward (MDP_WIDE_MMA=1; years of up to 256 states)
         uint32_t se = os.se, sc = os.sc;
         for (uint32_t c0 = 0; c0 < d.nc; c0 += 65535) {
             const uint32_t n = std::min(65535u, d.nc - c0);
             const uint32_t pts = mma_pts(eng->mma_npm);
             const dim3 g((d.ne + pts - 1) / pts, n);
-            note_launch(eng, d, "k_fwd_mma<%u>", eng->mma_npm);
-#define MDP_MMA(NPM) \
-    hipLaunchKernelGGL((k_fwd_mma<NPM>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, d.np_d, \
-                       d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan, eng->tmax, eng->prior0, d.e, d.ne, c0, eng->maxA, \
-                       eng->mma_ktmax, eng->ncoef_d, out, se, sc)
-            if (eng->mma_npm == 64) MDP_MMA(64);
-            else if (eng->mma_npm == 128) MDP_MMA(128);
-            else MDP_MMA(256);
-#undef MDP_MMA
+            note_launch(eng, d, kFmtMma, eng->mma_npm);
+            for_mma(eng, [&](auto NPM) {
+                hipLaunchKernelGGL((k_fwd_mma<NPM()>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ,
+                                   d.np_d, d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan, eng->tmax,
+                                   eng->prior0, d.e, d.ne, c0, eng->maxA, eng->mma_ktmax, eng->ncoef_d, out, se, sc);
+            });
         }
     } else {
-        const uint32_t cb = d.wide_cb_fwd;
+        const uint32_t cb = d.plan.wide_cb_fwd;
         uint32_t se = os.se, sc = os.sc;
         for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
             const uint32_t n = std::min(cb, d.nc - c0);
@@ -2963,15 +2735,7 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
     return MDP_OK;
 }
 
-// Does kernel slot k (0: Q rows / k_zpv, 1: k_coefs, 2: forward) run on this path?
-bool slot_active(const mdp_engine *eng, const DevCtx &d, int k)
-{
-    if (eng->wide || (eng->jit && eng->qglobal)) return k == 2 || eng->nitems;
-    // the direct path computes its Z rows inside k_qrows (slot 0 idle); the
-    // wide path (and Q rows built in HBM) keeps k_zrows for its item kernel
-    if (eng->jit) return k == 2 || (k == 1 && eng->nitems && !d.fused);
-    return k != 1 || eng->nuses;
-}
+bool slot_active(const mdp_engine *eng, const DevCtx &d, int k) { return mdp_plan_slot_active(eng, d.plan, k); }
 
 int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, hipStream_t s)
 {
@@ -2979,7 +2743,7 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
     if ((eng->wide && k > 0) || (eng->jit && eng->qglobal && k == 1)) return launch_wide(eng, d, k, out, os, s);
     if (k == 2) return launch_forward(eng, d, out, os, s);
     if ((eng->jit || eng->wide) && k == 0) {  // Z rows
-        const uint32_t kmax = d.zs_kmax;
+        const uint32_t kmax = d.ct.kmax;
         const dim3 grid((d.nc + 64 * kZC - 1) / (64 * kZC), (eng->nj + kZRows - 1) / kZRows);
         note_launch(eng, d, "k_zrows");
         MDP_LAUNCH(k_zrows, grid, dim3(kBlock), (size_t)kZRows * kmax * sizeof(double), s, d.c, d.nc, eng->nj,
@@ -2989,33 +2753,17 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
     }
     if (eng->jit) {  // k == 1: Q rows
         if (int rc = qrows_attrs(eng, d)) return rc;
-        const uint32_t cb = d.qrows_cb;
+        const uint32_t cb = d.plan.qrows_cb;
         const dim3 grid((d.nc + cb - 1) / cb);
         const size_t lds = qrows_lds(eng, cb);
-#define MDP_QROWS_CB(NV, EX, CB)                                                                        \
-    do {                                                                                                \
-    note_launch(eng, d, "k_qrows<%d,%d,%d>", NV, (int)EX, CB);                                              \
-    MDP_LAUNCH((k_qrows<NV, EX, CB>), grid, dim3(kQrowsBlock), lds, s, d.c, d.nc, eng->nvar, eng->nj,         \
-               d.zs_kmax, d.zsq, d.zc, d.sv, eng->nitems, d.items, eng->ncoef_d, d.qstart,                     \
-               (uint32_t)eng->qitem.size(), d.qitem, d.Qrow, (uint32_t)eng->ldQ, d.stamps[1],                 \
-               (uint32_t)(eng->qrows_xcd ? 1u : 0u), d.qslot, (uint32_t)eng->qslot.size(), eng->qslot_lglmax,   \
-               (const uint4 *)d.qlane, d.islot, eng->npl_slots); } while (0)
-        // c values per workgroup: <= qrows_maxcb(nvar) (register budget at 1024 threads)
-        if (eng->nvar == 8) {
-            if (cb == 4) MDP_QROWS_CB(8, true, 4);
-            else if (cb == 2) MDP_QROWS_CB(8, true, 2);
-            else MDP_QROWS_CB(8, true, 1);
-        } else if (eng->nvar < 8) {
-            if (cb == 4) MDP_QROWS_CB(8, false, 4);
-            else if (cb == 2) MDP_QROWS_CB(8, false, 2);
-            else MDP_QROWS_CB(8, false, 1);
-        } else if (eng->nvar <= 16) {
-            if (cb == 2) MDP_QROWS_CB(16, false, 2);
-            else MDP_QROWS_CB(16, false, 1);
-        } else {
-            MDP_QROWS_CB(24, false, 1);
-        }
-#undef MDP_QROWS_CB
+        for_qrows(eng, cb, [&](auto nv, auto ex, auto CB) {
+            note_launch(eng, d, kFmtQrows, nv(), (int)ex(), CB());
+            MDP_LAUNCH((k_qrows<nv(), ex(), CB()>), grid, dim3(kQrowsBlock), lds, s, d.c, d.nc, eng->nvar, eng->nj,
+                       d.ct.kmax, d.zsq, d.zc, d.sv, eng->nitems, d.items, eng->ncoef_d, d.qstart,
+                       (uint32_t)eng->qitem.size(), d.qitem, d.Qrow, (uint32_t)eng->ldQ, d.stamps[1],
+                       (uint32_t)(eng->qrows_xcd ? 1u : 0u), d.qslot, (uint32_t)eng->qslot.size(), eng->qslot_lglmax,
+                       (const uint4 *)d.qlane, d.islot, eng->npl_slots);
+        });
         HIP_TRY(hipGetLastError());
         return MDP_OK;
     }
@@ -3300,21 +3048,21 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
         names[2] = "k_forward(jit)";
         slots[0] = 0;
         slots[1] = 6;  // k_qrows stamps slots 4 and 5 inside phase 1
-        slots[2] = d.fused ? 6 : 4;
+        slots[2] = d.plan.fused ? 6 : 4;
     }
     size_t used = 0;
     for (int k = 0; k < 3; ++k) {
-        if (!d.stamps[k] || !d.nst[k] || !slots[k]) continue;
-        std::vector<unsigned long long> h(d.nst[k] * kStampSlots);
+        if (!d.stamps[k] || !d.plan.nst[k] || !slots[k]) continue;
+        std::vector<unsigned long long> h(d.plan.nst[k] * kStampSlots);
         HIP_TRY(hipMemcpy(h.data(), d.stamps[k], h.size() * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull, t1 = 0, rs0 = ~0ull, rs1 = 0, re1 = 0;
         double rdur = 0.0;
         std::vector<double> mean(slots[k], 0.0);
         size_t nb = 0;
-        for (size_t b = 0; b < d.nst[k]; ++b) {
+        for (size_t b = 0; b < d.plan.nst[k]; ++b) {
             const unsigned long long *st = &h[b * kStampSlots];
-            const int last = ((k == 2 && d.fused) || k == 1) && eng->jit ? 3 : slots[k] - 1;
+            const int last = ((k == 2 && d.plan.fused) || k == 1) && eng->jit ? 3 : slots[k] - 1;
             if (!st[0] || !st[last] || st[last] < st[0]) continue;
             ++nb;
             rs0 = std::min(rs0, st[6]);
@@ -3324,7 +3072,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
             t0 = std::min(t0, st[0]);
             t1 = std::max(t1, st[last]);
             // the fused forward kernel stamps slots 4 and 5 between 0 and 1
-            const bool fz = ((k == 2 && eng->devs[0].fused) || k == 1) && eng->jit && slots[k] == 6;
+            const bool fz = ((k == 2 && d.plan.fused) || k == 1) && eng->jit && slots[k] == 6;
             static const int seq_plain[6] = {0, 1, 2, 3, 4, 5}, seq_fused[6] = {0, 4, 5, 1, 2, 3};
             const int *seq = fz ? seq_fused : seq_plain;
             for (int q = 1; q < slots[k]; ++q) mean[q] += (double)(st[seq[q]] - st[seq[q - 1]]);
@@ -3341,7 +3089,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
         {   // block start / end spread (wall clock): percentiles, and the latest start per XCD
             std::vector<double> st0, en;
             double xmax[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (size_t b = 0; b < d.nst[k]; ++b) {
+            for (size_t b = 0; b < d.plan.nst[k]; ++b) {
                 const unsigned long long *st = &h[b * kStampSlots];
                 if (!st[6] || !st[7] || st[7] < st[6] || st[6] < rs0) continue;
                 st0.push_back((st[6] - rs0) * 0.01);
@@ -3362,7 +3110,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
         }
         if (k == 2 && nb && !eng->jit) {  // forward: cycles summed over run ops / general ops (wave 0)
             double cr = 0, cg = 0;
-            for (size_t b = 0; b < d.nst[k]; ++b) {
+            for (size_t b = 0; b < d.plan.nst[k]; ++b) {
                 const unsigned long long *st = &h[b * kStampSlots];
                 if (!st[0] || !st[2]) continue;
                 cr += (double)st[3];
@@ -3426,7 +3174,7 @@ const char *mdp_engine_kernel_name(const mdp_engine *eng, int k)
     if (eng->jit && eng->qglobal)  // Q rows built in HBM, then the hipRTC forward kernel
         return k < 2 && !eng->nitems ? "" : k == 2 ? "k_forward" : kKernelNames[2][k];
     // direct path: Z rows inside k_qrows (slot 0 idle); fused: one kernel
-    if (eng->jit && (k == 0 || (k == 1 && (eng->devs.empty() || eng->devs[0].fused)))) return "";
+    if (eng->jit && (k == 0 || (k == 1 && (eng->devs.empty() || eng->devs[0].plan.fused)))) return "";
     return kKernelNames[eng->jit ? 1 : 0][k];
 }
 

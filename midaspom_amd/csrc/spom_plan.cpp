@@ -1,10 +1,12 @@
 // midaspom_amd/csrc/spom_plan.cpp -- host planning of the posterior engine:
 // option parsing, the generic / direct / chunked / wide plan tables the
 // kernels index (spom_engine.h holds the shared constants), the hipRTC
-// forward sources and the host-only part of the C ABI (work counts, engine
-// info).  No HIP runtime call: the device's LDS limit arrives as an
-// argument, so this unit links into a stand-alone program (plan_check.cpp) as
-// it links into libmidaspom.so.
+// forward sources, per grid the c tables and the grid plan (mdp_plan_grid:
+// the forward variant, the point list, the chunk widths, every buffer size
+// and the forward launch's shape) and the host-only part of the C ABI (work
+// counts, engine info).  No HIP runtime call: the device's LDS limit and its
+// CU count arrive as arguments, so this unit links into a stand-alone program
+// (plan_check.cpp) as it links into libmidaspom.so.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -1136,6 +1138,298 @@ void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double
         for (int i = 0; i < kZTerms; ++i) coef[i] = pw[i] / (double)(i + 1);
 }
 
+void mdp_plan_item_tables(const mdp_engine *eng, std::vector<double> &sv, std::vector<uint2> &items)
+{
+    sv.assign((size_t)eng->nj * eng->nvar + 1, 0.0);
+    for (uint32_t js = 0; js < eng->nj; ++js)
+        for (uint32_t b = 0; b < eng->nvar; ++b)
+            sv[(size_t)js * eng->nvar + b] = ((eng->cj_bits[js] >> (eng->nvar - 1 - b)) & 1u)
+                                                  ? HUGE_VAL  // column of j: pC = fmin(c inf, 1) = 1.0
+                                                  : eng->Sj[(size_t)js * eng->n + eng->var_cols[b]];
+    items.assign(eng->nitems + 1, make_uint2(0u, 0u));
+    for (uint32_t i = 0; i < eng->nitems; ++i) {
+        const uint32_t r = eng->itemRow[i];
+        items[i] = make_uint2(eng->itemB[i] | ((r & 0xffu) << 24), eng->cj_bits[r] | ((r >> 8) << 24));
+    }
+}
+
+namespace {
+
+// no fused kernel on the wide path, for a chunked series, Q rows built in HBM
+// or state vectors in LDS
+bool fused_path(const mdp_engine *eng)
+{
+    return eng->jit && !eng->wide && !eng->qglobal && eng->chunks.empty() && !eng->jit_plan.vlds;
+}
+
+// The c tables for the bound cmax.
+void plan_ctables(const mdp_engine *eng, double cmax, MdpCTables &t)
+{
+    const uint32_t nj = eng->nj;
+    std::vector<std::vector<double>> rows(nj);
+    t.zc.assign((size_t)nj * kZTerms + 1, 0.0);
+    size_t kmax = 0;
+    for (uint32_t js = 0; js < nj; ++js) {
+        z_split(eng, js, cmax, rows[js], &t.zc[(size_t)js * kZTerms]);
+        kmax = std::max(kmax, rows[js].size());
+    }
+    kmax = (kmax + 7) & ~(size_t)7;
+    t.zs.assign(kmax * nj + 1, 0.0);
+    for (uint32_t js = 0; js < nj; ++js)
+        for (size_t k = 0; k < rows[js].size(); ++k) t.zs[js * kmax + k] = rows[js][k];
+    // k_qrows' copy: row js's product chain q (columns k = q mod 4) contiguous
+    t.zsq.assign(kmax * nj + 2, 0.0);  // + a double2 k_qrows may read at kmax 0
+    for (uint32_t js = 0; js < nj; ++js)
+        for (size_t k = 0; k < kmax; ++k) t.zsq[js * kmax + (k % 4) * (kmax / 4) + k / 4] = t.zs[js * kmax + k];
+    t.cmax = cmax;
+    t.kmax = (uint32_t)kmax;
+    t.coltab.clear();
+    t.ct_len = 0;
+    if (!fused_path(eng)) return;
+    // the fused kernel's column tables: one contiguous image it copies to LDS
+    // (with zpad, all KZ zs rows, zero past kmax: the kernel reads them unmasked)
+    const MdpJitPlan &pl = eng->jit_plan;
+    const size_t kimg = pl.zpad ? std::max<size_t>(kmax, std::max<uint32_t>(8u, pl.kzmax)) : kmax;
+    const size_t ct = ((size_t)pl.off_zs + kimg * nj + 127) & ~(size_t)127;
+    std::vector<double> &img = t.coltab;
+    img.assign(ct, 0.0);
+    std::vector<double> sv;
+    std::vector<uint2> items;
+    mdp_plan_item_tables(eng, sv, items);
+    memcpy(img.data(), sv.data(), (size_t)nj * eng->nvar * sizeof(double));
+    memcpy(img.data() + pl.off_it, items.data(), (size_t)eng->nitems * sizeof(uint2));
+    memcpy(img.data() + pl.off_qs, eng->qstart.data(), eng->qstart.size() * sizeof(uint32_t));
+    memcpy(img.data() + pl.off_zc, t.zc.data(), (size_t)nj * kZTerms * sizeof(double));
+    if (!eng->qitem.empty())
+        memcpy(img.data() + pl.off_qi, eng->qitem.data(), eng->qitem.size() * sizeof(uint32_t));
+    {
+        const std::vector<uint32_t> rq = mdp_jit_reversed_index(pl.udesc, pl.ldQ);
+        memcpy(img.data() + pl.off_rq, rq.data(), rq.size() * sizeof(uint32_t));
+    }
+    for (size_t k = 0; k < kmax; ++k)  // zs pairs (k, k+1) of a row adjacent: one ds_read_b128
+        for (uint32_t js = 0; js < nj; ++js) img[pl.off_zs + ((k / 2) * nj + js) * 2 + (k & 1)] = t.zs[js * kmax + k];
+    t.ct_len = (uint32_t)ct;
+}
+
+// The point list of forward kernels with `epl` points per lane: the e rows
+// whose ratio form is s (x < y, x = min(e, 1), y = 1 - x, as the kernel
+// computes them), then those of form t, each run padded to a multiple of epl
+// with duplicates of its last row (bit 31: computed, not stored), so every
+// lane's points share one form and so their coefficient reads.  A sorted
+// grid keeps its order (the kernels' stores stay coalesced).
+std::vector<uint32_t> point_list(const double *e, uint32_t ne, uint32_t epl)
+{
+    std::vector<uint32_t> s_rows, t_rows;
+    for (uint32_t i = 0; i < ne; ++i) {
+        const double x = e[i] > 1.0 ? 1.0 : e[i], y = 1.0 - x;
+        (x >= y ? t_rows : s_rows).push_back(i);
+    }
+    std::vector<uint32_t> pl;
+    pl.reserve(ne + 2 * epl);
+    for (const auto *rows : {&s_rows, &t_rows}) {
+        pl.insert(pl.end(), rows->begin(), rows->end());
+        while (!rows->empty() && pl.size() % epl) pl.push_back(rows->back() | 0x80000000u);
+    }
+    if (pl.empty()) pl.assign(epl, 0x80000000u);
+    return pl;
+}
+
+// c values per launch of a wide-path kernel that takes at most `fit` of them
+// in its scratch (MDP_WIDE_CB: tests force several launches per slot)
+uint32_t wide_cb(size_t most, size_t fit, int forced)
+{
+    const uint32_t cb = (uint32_t)std::min(most, std::max<size_t>(1, fit));
+    return forced ? std::min(cb, (uint32_t)std::max(1, forced)) : cb;
+}
+
+}  // namespace
+
+bool mdp_plan_fused_capable(const mdp_engine *eng)
+{
+    return fused_path(eng) && fused_lds(eng, eng->jit_plan.ct_max) <= kFusedLdsMax;
+}
+
+int mdp_plan_grid(const mdp_engine *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
+                  uint32_t ncu, MdpGridPlan &g)
+{
+    // c < 0 is refused: the item factors are folded as |n_b - pC_b| (k_qrows
+    // phase 2, k_witems, the fused prologue), which equals the reference's
+    // (1 - piold)(1 - pC) + piold pC (main_MIDASPOM.c:40) only for pC >= 0;
+    // at c < 0 the reference's pC = min(1, c S) is negative, not a probability
+    // (and a NaN or infinite c: the pressures min(1, c S) are then clamped
+    // by minNum, which drops NaN, where the reference would carry it)
+    for (uint32_t i = 0; i < nc; ++i)
+        if (!(c[i] >= 0.0) || std::isinf(c[i]))
+            return mdp_set_error(MDP_EINVAL, "colonisation rate c[%u] = %g (the engine takes finite c >= 0)", i, c[i]);
+    g = MdpGridPlan();
+    for (uint32_t i = 0; i < ne; ++i) {  // the kernels' form test: x = min(e, 1), s-form where x < 1 - x
+        const double x = e[i] > 1.0 ? 1.0 : e[i];
+        g.ne_sform += x < 1.0 - x;
+    }
+    const bool qglobal = eng->wide || eng->qglobal;  // Q rows from k_zrows + k_witems + k_wq
+    if (eng->wide || eng->jit) {
+        double cmax = eng->cbound;
+        for (uint32_t i = 0; i < nc; ++i) cmax = std::max(cmax, std::fabs(c[i]));
+        g.n_qrow = (size_t)nc * eng->ldQ;
+        if (!(ct.cmax == cmax)) {
+            plan_ctables(eng, cmax, ct);
+            g.tables_new = true;
+        }
+    }
+    if (qglobal) {
+        g.n_zg = (size_t)nc * eng->nj + 1;
+        // k_zrows stages kZRows rows of explicit columns in dynamic LDS
+        g.zrows_lds = (size_t)kZRows * ct.kmax * sizeof(double);
+        if (g.zrows_lds > kQrowsLdsMax)
+            return mdp_set_error(MDP_EUNSUPPORTED, "%u explicit colonisation columns per row exceed the LDS of k_zrows",
+                                 ct.kmax);
+    }
+    const char *cv = qglobal ? eng->opts.get("MDP_WIDE_CB") : nullptr;
+    const int forced_cb = cv ? std::max(1, atoi(cv)) : 0;
+    const size_t most_c = std::max<size_t>(1, std::min<size_t>(nc, 65535));  // a launch's grid y
+    if (qglobal && eng->hs) {  // k_fwd_hs reads the item factors of its columns: rows of nitems + 1 (zero slot)
+        const size_t ldp = (size_t)eng->nitems + 1;
+        g.wide_cb_items = wide_cb(nc, kHsPgBytes / 8 / ldp, forced_cb);
+        g.n_pg = (size_t)g.wide_cb_items * ldp;
+        g.pg_zero = true;
+    } else if (qglobal) {  // c values per k_witems launch: item factors within kWidePgBytes
+        g.wide_cb_items = wide_cb(most_c, kWidePgBytes / 8 / std::max<size_t>(1, eng->nitems), forced_cb);
+        g.n_pg = (size_t)g.wide_cb_items * eng->nitems + 1;
+    }
+    if (eng->wide) {
+        // c values per k_fwd_wide launch: the two state vectors of every
+        // point of a launch within kWideVBytes (the matrix-core forwards keep
+        // them in LDS)
+        const size_t ne_pad = (size_t)std::max<uint32_t>(1u, (ne + kBlock - 1) / kBlock) * kBlock;
+        g.wide_cb_fwd = wide_cb(most_c, kWideVBytes / 8 / (2 * (size_t)eng->npmax * ne_pad), forced_cb);
+        if (!eng->mma && !eng->mmt) g.n_v = 2 * (size_t)eng->npmax * g.wide_cb_fwd * ne_pad;
+    } else if (eng->jit) {
+        // forward kernels with several points per lane read them from a list
+        // that puts only e rows of one ratio form in a lane (spom_jit.cpp)
+        const uint32_t epl = (uint32_t)eng->jit_epl;  // (the fused variant lists at the reading variant's: jit_source)
+        if (epl > 1) {
+            g.plist = point_list(e, ne, epl);
+            for (uint32_t i = 0; i < g.plist.size() && g.plist_identity; ++i) g.plist_identity = g.plist[i] == i;
+            g.nlist = (uint32_t)g.plist.size();
+            if (!g.plist_identity) {  // an identity list is not uploaded: the kernels use the position
+                g.elist.resize(g.plist.size() + 1);
+                for (size_t i = 0; i < g.plist.size(); ++i)
+                    g.elist[i] = ne ? e[g.plist[i] & 0x7fffffffu] : 0.0;  // (no rows: never run)
+                g.elist[g.plist.size()] = ne ? e[0] : 0.0;
+            }
+        } else {
+            g.nlist = ne;
+        }
+        g.nlist_epl = epl;
+        // one e block per c column and a small per-c problem: the forward
+        // kernel computes its column's Q itself (one launch); never for a
+        // chunked series or Q rows built in HBM
+        g.gy = (g.nlist + eng->jit_kblock * epl - 1) / (eng->jit_kblock * epl);
+        g.fused = fused_path(eng) && fused_lds(eng, ct.ct_len) <= kFusedLdsMax && ct.kmax <= eng->jit_plan.kzmax &&
+                  (eng->fused_mode == 1 || (eng->fused_mode == -1 && g.gy <= 1));
+        // a column of a tall grid (an even number of e blocks, so no lane more
+        // idles) in half the blocks of twice the threads: each block stages
+        // its column's Q row once (config 3: forward 45.7-46.9 -> 44.3 us) --
+        // while that still leaves a block for every CU (a column slab of
+        // config 3, 1 024 x 128: 128 tall blocks would idle half the chip)
+        g.tall = !g.fused && eng->chunks.empty() && !eng->jit_plan.vlds && !eng->jit_shape_env &&
+                 eng->jit_kblock * 2 == (uint32_t)kJitKblockTall && g.gy >= 2 && g.gy % 2 == 0 &&
+                 (uint64_t)nc * (g.gy / 2) >= ncu;
+        g.variant = g.fused ? 1 : g.tall ? 2 : 0;
+        if (!eng->chunks.empty()) {  // the state vectors handed between chunks
+            g.ldv = g.gy * eng->jit_kblock * epl;
+            uint32_t nb = 1;  // most states at a chunk boundary
+            for (size_t i = 1; i < eng->chunks.size(); ++i) nb = std::max(nb, eng->chunks[i].np[0]);
+            g.n_vscr = (size_t)nb * nc * g.ldv;
+        }
+        // c values per k_qrows workgroup: enough workgroups for every CU, within the LDS
+        uint32_t cb = nc >= 1024 ? kQrowsMaxC : nc >= 512 ? 2u : 1u;  // power of two
+        cb = std::min(cb, eng->nvar <= 8 ? 4u : eng->nvar <= 16 ? 2u : 1u);  // registers (k_qrows)
+        while (cb > 1 && qrows_lds(eng, cb) > kQrowsLdsMax) cb >>= 1;
+        g.qrows_cb = cb;
+    } else {
+        g.n_zpv = (size_t)nc * (eng->nvar + 1) * eng->nstates;
+        g.n_r = (size_t)nc * ldR_of(eng);
+        if (!eng->lds_part) g.n_gpart = (size_t)nc * eng->partP.size() * (eng->nvar + 1);
+    }
+    if (eng->diag) {
+        g.nst[0] = eng->jit ? (size_t)nc : (size_t)((eng->nstates + kZpvJ - 1) / kZpvJ) * ((nc + kZpvCT - 1) / kZpvCT);
+        g.nst[1] = nc;
+        g.nst[2] = (size_t)nc * ((ne + kBlock - 1) / kBlock);  // >= the JIT grid (EPL >= 1)
+    }
+    return MDP_OK;
+}
+
+void mdp_plan_fwd_launch(const mdp_engine *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g)
+{
+    // threads per e block: kb (x spl with the split state-vector kernel)
+    const uint32_t kb = g.fused ? eng->jit_kblock_fused : g.tall ? (uint32_t)kJitKblockTall : eng->jit_kblock;
+    const uint32_t pro = g.fused ? eng->jit_pro_fused : 1u;
+    const uint32_t epl = g.fused ? (uint32_t)eng->jit_epl_fused : (uint32_t)eng->jit_epl;
+    const uint32_t spl = eng->jit_plan.vlds && (eng->jit_plan.vsplit == 2 || eng->jit_plan.vsplit == 4)
+                             ? (uint32_t)eng->jit_plan.vsplit : 1u;
+    const uint32_t fc = g.fused ? (uint32_t)eng->jit_plan.fused_cols : 1u;
+    // several points per lane: the grid's point list
+    g.fwd_listed = epl > 1 && !g.plist_identity;
+    g.fwd_nlist = epl > 1 ? g.nlist : ne;
+    const uint64_t gy = (g.fwd_nlist + kb * epl - 1) / (kb * epl);
+    g.fwd_nblk = gy * ((nc + fc - 1) / fc);  // e blocks x column groups
+    g.fwd_pro = pro;
+    g.fwd_threads = g.fwd_nblk * kb * fc * spl;
+    g.fwd_block = kb * fc * spl * pro;
+    g.fwd_lds = g.fused ? (ct.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
+}
+
+bool mdp_plan_slot_active(const mdp_engine *eng, const MdpGridPlan &g, int k)
+{
+    if (eng->wide || (eng->jit && eng->qglobal)) return k == 2 || eng->nitems;
+    // the direct path computes its Z rows inside k_qrows (slot 0 idle); the
+    // wide path (and Q rows built in HBM) keeps k_zrows for its item kernel
+    if (eng->jit) return k == 2 || (k == 1 && eng->nitems && !g.fused);
+    return k != 1 || eng->nuses;
+}
+
+std::vector<std::string> mdp_plan_grid_kernels(const mdp_engine *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc)
+{
+    std::set<std::string> names;
+    auto note = [&](const char *fmt, auto... a) {
+        char b[96];
+        snprintf(b, sizeof b, fmt, a...);
+        names.insert(b);
+    };
+    auto witems = [&]() { for_nv(eng, [&](auto nv) { note(kFmtWitems, nv()); }); };
+    const bool qglobal = eng->wide || (eng->jit && eng->qglobal);
+    for (int k = 0; k < 3 && ne && nc; ++k) {
+        if (!mdp_plan_slot_active(eng, g, k)) continue;
+        if (k == 0) {
+            names.insert(eng->jit || eng->wide ? "k_zrows" : "k_zpv");
+        } else if (k == 1 && qglobal) {
+            // k_fwd_hs: the item factors of every column in slot 1 when they fit one Pg block
+            if (!eng->hs || (g.wide_cb_items >= nc && eng->nitems)) witems();
+            if (!eng->hs) names.insert("k_wq");
+        } else if (k == 1 && eng->jit) {
+            for_qrows(eng, g.qrows_cb, [&](auto nv, auto ex, auto cb) { note(kFmtQrows, nv(), (int)ex(), cb()); });
+        } else if (k == 1) {
+            for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) { note(kFmtCoefs, (int)ldsz(), (int)ldsp(), nv()); });
+        } else if (eng->wide && eng->hs) {
+            if (g.wide_cb_items < nc && eng->nitems) witems();
+            note(kFmtHs, eng->hs_rt, eng->hs_nb);
+        } else if (eng->wide && eng->mmt) {
+            note(kFmtMmt, eng->mmt_rt, eng->mmt_rows, mmt_shape(eng).db ? "2buf" : "1buf");
+        } else if (eng->wide && eng->mma) {
+            note(kFmtMma, eng->mma_npm);
+        } else if (eng->wide) {
+            names.insert("k_fwd_wide");
+        } else if (eng->jit && !eng->chunks.empty()) {
+            note(kFmtJitChunks, eng->maxA, eng->chunks.size(), eng->chunks[0].qidx.empty() ? "" : ",gather");
+        } else if (eng->jit) {
+            note(kFmtJit, g.fused ? "fused" : "reading", eng->maxA);
+            if (g.tall) note(kFmtJitTall, kJitKblockTall);
+        }
+    }
+    return std::vector<std::string>(names.begin(), names.end());
+}
+
 // The source of the engine's forward kernel: variant 0 reading, 1 fused, 2
 // reading at kJitKblockTall threads (a column of a tall grid in half the
 // blocks: its Q row staged half as often).  Sets the engine's launch shape of
@@ -1151,7 +1445,7 @@ std::string jit_source(mdp_engine *eng, int variant)
         return mdp_jit_forward_source(plan);
     }
     // the reading variant's shape (e rows per block = kblock x epl, which
-    // set_grid_dev's block count uses before it picks the variant)
+    // mdp_plan_grid's block count uses before it picks the variant)
     const int epl_r = plan.epl > 0 ? plan.epl : mdp_jit_default_epl(plan.udesc);
     const int kb_r = plan.kblock > 0 ? plan.kblock : kBlock;
     eng->jit_epl = epl_r;
@@ -1404,7 +1698,7 @@ int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPl
             }
             // compile now the variant the first grid most likely runs (the
             // fused kernel wherever its tables fit: every grid of at most one
-            // e block per column takes it), the other on demand (set_grid_dev)
+            // e block per column takes it), the other on demand (set_grid_dev's jit_load)
             const bool fused_first = eng->fused_mode == 1 ||
                                      (eng->fused_mode == -1 && !vlds && !eng->qglobal &&
                                       fused_lds(eng, plan.ct_max) <= kFusedLdsMax);
@@ -1480,7 +1774,7 @@ int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_wo
     *w = mdp_work{};
     // per c value (the direct plan's tables; zero on the generic path, which
     // has none): Z rows, var-column pressures, item factors, Q sums
-    double cmax = eng->devs.empty() ? 1.0 : eng->devs[0].zs_cmax;
+    double cmax = eng->devs.empty() ? 1.0 : eng->devs[0].ct.cmax;
     if (!(cmax >= 0.0)) cmax = 1.0;  // no grid yet: the default [0, 1]
     std::vector<double> large;
     double coef[kZTerms];
@@ -1531,7 +1825,7 @@ int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_wo
     const MdpRatioWork rw = mdp_jit_ratio_work(pl);
     double ns = 0.0, nall = 0.0;
     for (const DevCtx &d : eng->devs) {
-        ns += d.ne_sform;
+        ns += d.plan.ne_sform;
         nall += d.ne;
     }
     const double fs = nall > 0.0 ? ns / nall : 0.5;

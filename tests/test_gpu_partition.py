@@ -2,9 +2,10 @@
 
 A slab of the (e, c) grid computed alone has the bits of the same cells of a
 one-rank run (midaspom_amd/dist.py, mdp_engine_set_cbound in
-include/midaspom.h, README): the multi-GPU drop-ins rest on it.  set_grid_dev
-(csrc/spom_engine.hip) picks its kernels from the slab's own shape, so the
-slabs here are cut where those choices change:
+include/midaspom.h, README): the multi-GPU drop-ins rest on it.  The grid
+planner (mdp_plan_grid, csrc/spom_plan.cpp; tests/test_grid_plan_host.py
+holds it to its table on the CPU) picks a grid's kernels from the slab's own
+shape, so the slabs here are cut where those choices change:
 
   * fused (one e block a column) <-> k_qrows + the reading kernel;
   * the reading kernel's tall variant (kb512: an even number of e blocks and a
