@@ -11,6 +11,11 @@ extern "C" {
 /* printf-style setter for the thread-local error string; returns code. */
 int mdp_set_error(int code, const char *fmt, ...);
 
+/* bytes of device memory the engines of this process hold (every live DevBuf,
+ * spom_dev.h): 0 once every handle is destroyed.  For the leak tests; not
+ * part of the public ABI. */
+unsigned long long mdp_dev_live_bytes(void);
+
 struct mdp_model {
     uint32_t n, tmax, nvar, nextid;
     int32_t *obs;          /* [tmax][n]                    */

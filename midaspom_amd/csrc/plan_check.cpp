@@ -32,6 +32,10 @@
 
 #include "spom_engine.h"
 
+#ifndef MDP_ENGINE_PLAN  // a planner from before the plan / engine split (scripts/jit_sources.py --rev)
+using MdpEnginePlan = mdp_engine;
+#endif
+
 namespace {
 
 uint64_t g_h = 0xcbf29ce484222325ull;  // FNV-1a, 64 bit
@@ -63,8 +67,8 @@ void source(const char *name, const std::string &src, double flops_pt)
     g_src_lines += b;
 }
 
-// every plan vector of mdp_engine in declaration order, then the sources
-void digest(mdp_engine *e)
+// every plan vector of MdpEnginePlan in declaration order, then the sources
+void digest(MdpEnginePlan *e)
 {
     for (MdpJitPlan &c : e->chunks) {
         mix(c.np), mix(c.udesc), mix(c.qidx);
@@ -96,7 +100,7 @@ void digest(mdp_engine *e)
 // The tall variant's source, after the digest (which it is no part of).
 // jit_source reports no flop count for it, so the same plan goes through the
 // generator once more for the count; the two texts must agree.
-int tall_source(mdp_engine *e)
+int tall_source(MdpEnginePlan *e)
 {
     const uint64_t h = g_h;
     const std::string src = jit_source(e, 2);
@@ -113,7 +117,7 @@ int tall_source(mdp_engine *e)
     return 0;
 }
 
-std::string path_of(const mdp_engine *e)
+std::string path_of(const MdpEnginePlan *e)
 {
     char b[64];
     if (e->wide) {
@@ -154,7 +158,7 @@ struct GridArgs {
 #ifdef MDP_PLAN_GRID
 // the --grid mode: plan the grid and print its line (after digest(): the
 // generator has settled the forward shapes)
-int grid_line(mdp_engine *eng, const GridArgs &a)
+int grid_line(MdpEnginePlan *eng, const GridArgs &a)
 {
     if (!eng->chunks.empty()) {  // the chunks' shape, as jit_build_chunks takes it from the generator
         MdpJitPlan c0 = eng->chunks[0];
@@ -192,7 +196,7 @@ int grid_line(mdp_engine *eng, const GridArgs &a)
 }
 
 #else
-int grid_line(mdp_engine *, const GridArgs &)
+int grid_line(MdpEnginePlan *, const GridArgs &)
 {
     fprintf(stderr, "plan_check: this planner plans no grid\n");
     return 2;
@@ -238,7 +242,7 @@ int main(int argc, char **argv)
     std::unique_ptr<mdp_model, void (*)(mdp_model *)> model_owner(model, mdp_model_free);
     mdp_problem prob;
     if (mdp_model_problem(model, &prob)) return fail();
-    auto eng = std::make_unique<mdp_engine>();
+    auto eng = std::make_unique<MdpEnginePlan>();
     if (parse_engine_opts(argv[4], eng->opts, diag)) return fail();
     if (mdp_plan_engine(eng.get(), &prob, 160 * 1024, MdpPlanMode::TablesOnly, nullptr)) return fail();
     digest(eng.get());

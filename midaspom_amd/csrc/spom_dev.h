@@ -1,9 +1,11 @@
 // midaspom_amd/csrc/spom_dev.h -- what the four HIP units share of their host
-// side: the check of a HIP call and the device buffers.
+// side: the check of a HIP call and the owning device buffer.
 #ifndef SPOM_DEV_H
 #define SPOM_DEV_H
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <utility>
 #include <vector>
 
 #include "mdp_internal.h"
@@ -16,36 +18,87 @@
                                  __FILE__, __LINE__);                                        \
     } while (0)
 
-// grow-only device buffer of `need` elements of `elem` bytes (one element at
-// the least): kept while it holds them, reallocated -- its contents dropped
-// -- when it does not.  After a failed hipMalloc (MDP_ENOMEM) the pointer is
-// null and the capacity 0.
-template <typename T>
-int dev_grow(T *&p, size_t &cap, size_t need, size_t elem = sizeof(T))
-{
-    if (p && need <= cap) return MDP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (need == 0) need = 1;
-    const hipError_t e = hipMalloc((void **)&p, need * elem);
-    if (e != hipSuccess) {
-        p = nullptr;
-        return mdp_set_error(MDP_ENOMEM, "hipMalloc(%zu bytes) failed: %s", need * elem, hipGetErrorString(e));
-    }
-    cap = need;
-    return MDP_OK;
-}
+// bytes held by every live DevBuf of the process (mdp_dev_live_bytes)
+inline std::atomic<unsigned long long> g_dev_live_bytes{0};
 
-// a fresh device buffer holding h (what p pointed to is not freed)
+// One device allocation and its capacity in elements; the destructor frees it.
+// Move-only: a launch that takes its arguments by value (hipExtLaunchKernelGGL
+// packs them into a tuple) cannot be handed a buffer by mistake, the sites
+// pass get().
 template <typename T>
-int dev_upload(T *&p, const std::vector<T> &h)
-{
-    size_t cap = 0;
-    p = nullptr;
-    if (int rc = dev_grow(p, cap, h.size())) return rc;
-    if (!h.empty()) HIP_TRY(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MDP_OK;
-}
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { return swap(o), *this; }  // (o frees what this held)
+    ~DevBuf() { reset(); }
+
+    void swap(DevBuf &o) noexcept { std::swap(p_, o.p_), std::swap(cap_, o.cap_); }
+    T *get() const { return p_; }
+    size_t cap() const { return cap_; }  // elements
+    bool empty() const { return !p_; }
+    void reset()
+    {
+        if (!p_) return;
+        (void)hipFree(p_);
+        g_dev_live_bytes.fetch_sub(cap_ * sizeof(T), std::memory_order_relaxed);
+        p_ = nullptr, cap_ = 0;
+    }
+    // grow-only: `need` elements (one at the least), kept while the allocation
+    // holds them, reallocated -- the contents dropped -- when it does not.
+    // After a failed hipMalloc (MDP_ENOMEM) the buffer is null and empty.
+    int grow(size_t need)
+    {
+        if (p_ && need <= cap_) return MDP_OK;
+        reset();
+        if (need == 0) need = 1;
+        const hipError_t e = hipMalloc((void **)&p_, need * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            return mdp_set_error(MDP_ENOMEM, "hipMalloc(%zu bytes) failed: %s", need * sizeof(T), hipGetErrorString(e));
+        }
+        cap_ = need;
+        g_dev_live_bytes.fetch_add(cap_ * sizeof(T), std::memory_order_relaxed);
+        return MDP_OK;
+    }
+    // grow, then copy h[n] in
+    int assign(const T *h, size_t n)
+    {
+        if (int rc = grow(n)) return rc;
+        if (n) HIP_TRY(hipMemcpy(p_, h, n * sizeof(T), hipMemcpyHostToDevice));
+        return MDP_OK;
+    }
+    int assign(const std::vector<T> &h) { return assign(h.data(), h.size()); }
+
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// The device, stream and timing events of a handle, as the BASE of the struct
+// that holds its DevBufs.  The release order is by declaration: the handle's
+// destructor body calls drain() (the device current, the stream drained), then
+// its members go (the buffers), then this base (the events, the stream).
+struct DevQueue {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevQueue() = default;
+    DevQueue(const DevQueue &) = delete;
+    DevQueue &operator=(const DevQueue &) = delete;
+    void drain() const
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
+    ~DevQueue()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
 
 #endif

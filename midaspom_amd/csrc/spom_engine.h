@@ -3,23 +3,21 @@
 //   spom_plan.cpp    host planning: options, plan tables, hipRTC sources, and
 //                    per grid the c tables and the grid plan (kernel variant,
 //                    point list, chunk widths, buffer sizes, launch shape)
-//   spom_engine.hip  the kernels; device set-up, uploads and launches as the
-//                    plans say; timing
+//   spom_engine.hip  the kernels; the engine (the plan plus its device contexts
+//                    and run-time state); device set-up, uploads and launches
+//                    as the plans say; timing
 //   plan_check.cpp   the planner's stand-alone driver
 // (the forward kernel's generator and its hipRTC unit, spom_jit.cpp and
 // spom_jit_rtc.cpp, share spom_jit.h, included here)
-// Plain C++17: the HIP headers below give the vector and handle types only.
+// Plain C++17: the HIP header below gives the vector types (uint2, uint4) only.
 #ifndef MDP_SPOM_ENGINE_H
 #define MDP_SPOM_ENGINE_H
 
-#include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 
 #include <cstddef>
 #include <cstdint>
 #include <map>
-#include <mutex>
-#include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -76,13 +74,6 @@ constexpr size_t kWideVBytes = 1ull << 30;     // wide path: state-vector scratc
 // ---------------------------------------------------------------------------
 // types
 // ---------------------------------------------------------------------------
-// a kernel instantiation a context has noted (note_launch): the launch
-// site's format string, by address, and its arguments
-struct LaunchNote {
-    const char *fmt;
-    uint64_t a[4];
-};
-
 // The tables that depend on the grid's |c| bound (mdp_plan_grid builds them;
 // z_split prunes the Z rows for the bound).  Cached by cmax: a grid under the
 // same bound neither rebuilds nor re-uploads them.
@@ -133,76 +124,6 @@ struct MdpGridPlan {
     bool fwd_listed = false;    // the kernel reads plist / elist
 };
 
-struct DevCtx {
-    int device = 0;
-    mutable std::vector<LaunchNote> noted;  // what this context has reported to mdp_engine::launched
-    hipStream_t stream = nullptr;
-    double *S = nullptr;
-    uint32_t *var_cols = nullptr, *row_col = nullptr;
-    uint32_t *pairA = nullptr, *pairB = nullptr, *pairOff = nullptr;
-    uint32_t *udesc = nullptr, *prog = nullptr, *pairPart0 = nullptr, *partP = nullptr, *partK0 = nullptr;
-    double *e = nullptr, *c = nullptr;
-    size_t cap_e = 0, cap_c = 0;
-    uint32_t ne = 0, nc = 0;
-    MdpCTables ct;     // the c tables on the device (host copy and the bound they hold for)
-    MdpGridPlan plan;  // the current grid's plan (set_grid_dev)
-    // the plan's point list and its e values by position: a listed kernel
-    // loads its e values by position, beside the list, instead of through it
-    // (position -> row -> e would be two round trips in series)
-    uint32_t *plist = nullptr;
-    size_t cap_plist = 0;
-    double *elist = nullptr;
-    size_t cap_elist = 0;
-    double *ZPV = nullptr, *R = nullptr, *out = nullptr, *gpart = nullptr;
-    size_t cap_zpv = 0, cap_r = 0, cap_out = 0, cap_gpart = 0;
-    unsigned long long *stamps[3] = {nullptr, nullptr, nullptr};  // k_zpv, k_coefs, k_forward
-    size_t cap_st[3] = {0, 0, 0};
-    // direct path: k_zrows / k_qrows tables (zs, row-major [row][k], depends
-    // on the grid's c range)
-    double *zs = nullptr, *sv = nullptr, *Qrow = nullptr, *Zg = nullptr;
-    double *zsq = nullptr;  // zs chain-major, [row][k mod 4][k / 4] (k_qrows: a lane's chain contiguous)
-    double *zc = nullptr;   // Z-row series coefficients [row][kZTerms]
-    size_t cap_zc = 0;
-    uint2 *items = nullptr;  // per item {B | row << 24, j | (row >> 8) << 24}
-    uint2 *qslot = nullptr;  // k_qrows phase-3 lane table
-    uint32_t *qlane = nullptr;  // k_qrows phase-3 Pc slots per lane (nvar <= 8)
-    uint32_t *islot = nullptr;  // k_qrows: each item's Pc slot
-    uint32_t *itemB = nullptr, *qstart = nullptr, *qitem = nullptr;
-    size_t cap_zs = 0, cap_zsq = 0, cap_qrow = 0, cap_zg = 0;
-    double *coltab = nullptr;  // fused kernel's column tables (MdpCTables::coltab)
-    size_t cap_coltab = 0;
-    bool qrows_attr_set = false;  // k_qrows' LDS limit raised on this device
-    // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
-    // reading at kJitKblockTall threads (tall grids, mdp_plan_grid)
-    hipModule_t jit_mod[3] = {nullptr, nullptr, nullptr};
-    hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};
-    // a long series: one forward kernel per chunk of years, the state vector
-    // handed over in vscr[state][c][e] (ldv e values per (state, c))
-    std::vector<hipModule_t> cmod;
-    std::vector<hipFunction_t> cfn;
-    std::vector<uint32_t *> cqidx;  // per chunk: gather indices into the Q row (null: whole row)
-    double *vscr = nullptr;
-    size_t cap_vscr = 0;
-    uint32_t ncu = 0;    // the device's compute units (0: not asked yet)
-    // wide path: per-chunk item factors, state-vector scratch, tables
-    double *Pg = nullptr, *V = nullptr;
-    size_t cap_pg = 0, cap_v = 0;
-    uint32_t *np_d = nullptr, *udesc_w = nullptr;
-    uint2 *mma_kt = nullptr, *mma_wplan = nullptr;
-    uint32_t *mma_kbase = nullptr, *mma_desc = nullptr, *mma_dbase = nullptr;
-    uint2 *mmt_kt = nullptr, *mmt_ktile = nullptr, *mmt_wplan = nullptr;  // k_fwd_mmt tables
-    uint32_t *mmt_cidx = nullptr;
-    // k_fwd_hs tables
-    uint32_t *hs_kt = nullptr, *hs_cidx = nullptr, *hs_pbase = nullptr, *hs_dpos = nullptr, *hs_dbase = nullptr,
-             *hs_pk = nullptr;
-    uint2 *hs_ppos = nullptr, *hs_dpk = nullptr;
-    uint4 *hs_wplan = nullptr;
-    uint4 *hs_pass = nullptr;
-    std::vector<hipEvent_t> ev;  // kNumEv events per profiled run, reused
-    std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
-    size_t ev_used = 0;          // event sets recorded since the last collect
-};
-
 struct EngineOpts {
     std::map<std::string, std::string> kv;
     const char *get(const char *name) const
@@ -212,7 +133,10 @@ struct EngineOpts {
     }
 };
 
-struct mdp_engine {
+// Everything the planner writes or reads of an engine.  The engine itself
+// (spom_engine.hip) derives from it and adds the device contexts and the
+// run-time state: nothing that uploads or launches takes a plan.
+struct MdpEnginePlan {
     uint32_t n = 0, tmax = 0, nvar = 0, nstates = 0, nextid = 0;
     uint32_t npairs = 0, nuses = 0, ncoef = 0, npmax = 1, variant = 0;
     uint32_t deg = 0;         // homogeneous transition degree D
@@ -239,13 +163,12 @@ struct mdp_engine {
     bool jit_shape_env = false;  // MDP_EPL / MDP_JIT_KBLOCK set: one shape for both variants
     double jit_flops_pt = 0;  // its FP64 flops per grid point (counted by the generator)
     size_t ldQ = 0;           // per-c Q block (doubles, even) read by the JIT kernel
-    std::vector<char> jit_code[3];  // forward kernel code objects [variant, as DevCtx::jit_fn], compiled on demand
+    std::vector<char> jit_code[3];  // forward kernel code objects [variant: jit_load's index], compiled on demand
     std::string jit_src[3];         // their sources (a cached object the runtime refuses is rebuilt)
     std::vector<std::string> chunk_src;
     std::vector<MdpJitPlan> chunks;               // > 1: the series runs as chunks of years
     std::vector<std::vector<char>> chunk_code;    // their code objects
     bool qglobal = false;     // Q rows built by k_zrows + k_witems + k_wq (k_qrows' tables exceed the LDS)
-    int layout = MDP_LAYOUT_EC;  // mdp_engine_run's output layout (mdp_engine_set_layout)
     double cbound = 0.0;         // the per-c tables' |c| bound at least this (mdp_engine_set_cbound)
     int fused_mode = -1;            // MDP_FUSED: -1 auto, 0, 1
     MdpJitPlan jit_plan;
@@ -299,14 +222,7 @@ struct mdp_engine {
     size_t lds_max = 160 * 1024;  // the device's LDS per workgroup (mdp_plan_engine's argument; 160 KiB on gfx950)
     double prior0 = 1.0;
     std::vector<uint32_t> np, pairA, pairB, pairOff, use_pair, prog, udesc, pairPart0, partP, partK0;
-    std::vector<DevCtx> devs;
     EngineOpts opts;          // mdp_engine_create_opts (variant selection; no environment reads)
-    mutable std::set<std::string, std::less<>> launched;  // kernel instantiations launched so far (mdp_engine_launched)
-    mutable std::mutex launched_mu;                         // engines may be driven from several host threads
-    int profiling = 0;
-    double last_ms[3] = {0, 0, 0};  // mean per run over the last collected runs
-    int nlast = 0;
-    uint64_t runs_collected = 0;
 };
 
 // The forward kernels' output strides: log L of point (ie, ic) at
@@ -328,12 +244,12 @@ inline OutStrides layout_strides(int layout, uint32_t ld)
 // ---------------------------------------------------------------------------
 // per-c coefficient stride: every forward use (deg+1 coefficients padded to
 // an even count) plus two zero transitions of prefetch padding
-inline size_t rsp_of(const mdp_engine *eng) { return (eng->deg + 2) & ~1u; }
-inline size_t ldR_of(const mdp_engine *eng) { return ((size_t)eng->nuses + 2) * rsp_of(eng); }
+inline size_t rsp_of(const MdpEnginePlan *eng) { return (eng->deg + 2) & ~1u; }
+inline size_t ldR_of(const MdpEnginePlan *eng) { return ((size_t)eng->nuses + 2) * rsp_of(eng); }
 
 // k_fwd_mma: two state buffers and the power tables of the block's points,
 // and (LDS staging) three years' K entries
-inline size_t mma_lds(const mdp_engine *eng)
+inline size_t mma_lds(const MdpEnginePlan *eng)
 {
     const uint32_t npm = eng->mma_npm;
     return (2 * (size_t)mma_rows(npm) * mma_pts(npm) + 2 * ((size_t)eng->maxA + 1) * mma_ps(npm)) * sizeof(double) +
@@ -349,7 +265,7 @@ struct MmtShape {
 // (measured, profiles/r06/wide: years of up to 128 states run 25 % faster on
 // <4, 128, 2buf> than on <2, 256, 1buf>; a 256-state problem 6 % faster on
 // one buffer than on <2, 256, 2buf>)
-inline MmtShape mmt_shape(const mdp_engine *eng)
+inline MmtShape mmt_shape(const MdpEnginePlan *eng)
 {
     const uint32_t npmax = eng->npmax;
     if (npmax <= 128) return {4u, 128u, true};
@@ -358,7 +274,7 @@ inline MmtShape mmt_shape(const mdp_engine *eng)
     return {1u, 1024u, false};
 }
 
-inline size_t mmt_lds(const mdp_engine *eng)
+inline size_t mmt_lds(const MdpEnginePlan *eng)
 {
     const MmtShape sh = mmt_shape(eng);
     return ((sh.db ? 2 : 1) * (size_t)sh.rows * mmt_pts(sh.rt) + 2 * ((size_t)eng->maxA + 1) * mmt_ps(sh.rt)) *
@@ -366,13 +282,13 @@ inline size_t mmt_lds(const mdp_engine *eng)
 }
 
 // k_fwd_hs: the cube of the block's points (128 KiB for each shape)
-inline size_t hs_lds(const mdp_engine *eng)
+inline size_t hs_lds(const MdpEnginePlan *eng)
 {
     return (((size_t)1 << eng->hs_nb) + eng->hs_nb + 1) * mmt_pts(eng->hs_rt) * sizeof(double);  // + y^k table
 }
 
 // k_qrows LDS for cb c values per workgroup: Z, var-column S, Pc, Q CSR
-inline size_t qrows_lds(const mdp_engine *eng, uint32_t cb)
+inline size_t qrows_lds(const MdpEnginePlan *eng, uint32_t cb)
 {
     const size_t nv = eng->nvar <= 8 ? 8 : eng->nvar <= 16 ? 16 : 24;  // k_qrows NV
     return ((((size_t)cb * eng->nj + 1) & ~(size_t)1) + (size_t)eng->nj * (cb * nv + 2) + (size_t)cb * eng->npl_slots) *
@@ -382,14 +298,14 @@ inline size_t qrows_lds(const mdp_engine *eng, uint32_t cb)
 
 // The fused forward kernel keeps its column's tables (ct_len doubles,
 // dynamic LDS), Z, Pc and Q in LDS.
-inline size_t fused_lds(const mdp_engine *eng, size_t ct_len)
+inline size_t fused_lds(const MdpEnginePlan *eng, size_t ct_len)
 {
     const size_t fc = (size_t)eng->jit_plan.fused_cols;
     return (ct_len + 2 + fc * (eng->nj + eng->nitems + 2 * eng->ldQ)) * sizeof(double);  // + staging scratch
 }
 
 // k_fwd_wide: per-lane x^r, y^r tables, r <= maxA
-inline size_t wide_lds(const mdp_engine *eng) { return 2 * ((size_t)eng->maxA + 1) * kBlock * sizeof(double); }
+inline size_t wide_lds(const MdpEnginePlan *eng) { return 2 * ((size_t)eng->maxA + 1) * kBlock * sizeof(double); }
 
 // ---------------------------------------------------------------------------
 // The instantiation set of each templated kernel family, written once: the
@@ -411,7 +327,7 @@ constexpr const char *kFmtQrows = "k_qrows<%d,%d,%d>", *kFmtCoefs = "k_coefs<%d,
 // k_qrows<NV, EXACT, CB> for cb c values per workgroup: a power of two, at
 // most 4, 2, 1 by NV (the register budget at 1 024 threads; else one)
 template <typename F>
-auto for_qrows(const mdp_engine *eng, uint32_t cb, F &&fn)
+auto for_qrows(const MdpEnginePlan *eng, uint32_t cb, F &&fn)
 {
     const uint32_t nvar = eng->nvar;
     if ((cb != 2 && cb != 4) || cb > (nvar <= 8 ? 4u : nvar <= 16 ? 2u : 1u)) {
@@ -430,7 +346,7 @@ auto for_qrows(const mdp_engine *eng, uint32_t cb, F &&fn)
 
 // the padded variable-column count of k_coefs and k_witems
 template <typename F>
-auto for_nv(const mdp_engine *eng, F &&fn)
+auto for_nv(const MdpEnginePlan *eng, F &&fn)
 {
     if (eng->nvar <= 8) return fn(mdp_int<8>());
     if (eng->nvar <= 16) return fn(mdp_int<16>());
@@ -439,7 +355,7 @@ auto for_nv(const mdp_engine *eng, F &&fn)
 
 // k_coefs<LDS_ZPV, LDS_PART, NV>
 template <typename F>
-auto for_coefs(const mdp_engine *eng, F &&fn)
+auto for_coefs(const MdpEnginePlan *eng, F &&fn)
 {
     if (eng->lds_zpv) return for_nv(eng, [&](auto nv) { return fn(mdp_bool<true>(), mdp_bool<true>(), nv); });
     if (eng->lds_part) return for_nv(eng, [&](auto nv) { return fn(mdp_bool<false>(), mdp_bool<true>(), nv); });
@@ -448,7 +364,7 @@ auto for_coefs(const mdp_engine *eng, F &&fn)
 
 // k_fwd_hs<RT, NB, NW>
 template <typename F>
-auto for_hs(const mdp_engine *eng, F &&fn)
+auto for_hs(const MdpEnginePlan *eng, F &&fn)
 {
     if (eng->hs_nb == 8)
         return eng->hs_nw == 8 ? fn(mdp_int<2>(), mdp_int<8>(), mdp_int<8>()) : fn(mdp_int<4>(), mdp_int<8>(), mdp_int<16>());
@@ -458,7 +374,7 @@ auto for_hs(const mdp_engine *eng, F &&fn)
 
 // k_fwd_mmt<RT, ROWS, DB>
 template <typename F>
-auto for_mmt(const mdp_engine *eng, F &&fn)
+auto for_mmt(const MdpEnginePlan *eng, F &&fn)
 {
     if (eng->mmt_rows == 128) return fn(mdp_int<4>(), mdp_int<128>(), mdp_bool<true>());
     if (eng->mmt_rows == 256) return fn(mdp_int<2>(), mdp_int<256>(), mdp_bool<false>());
@@ -468,7 +384,7 @@ auto for_mmt(const mdp_engine *eng, F &&fn)
 
 // k_fwd_mma<NPM>
 template <typename F>
-auto for_mma(const mdp_engine *eng, F &&fn)
+auto for_mma(const MdpEnginePlan *eng, F &&fn)
 {
     if (eng->mma_npm == 64) return fn(mdp_int<64>());
     if (eng->mma_npm == 128) return fn(mdp_int<128>());
@@ -487,45 +403,56 @@ enum class MdpPlanMode {
     Compile,       // compile the forward kernel the first grid most likely runs
     OfflineCheck,  // MDP_JIT_CHECK=1 without a device: compile every kernel, then MDP_ENODEV
     // no hipRTC: the specialised kernel is taken to compile, so eng->jit is
-    // set with no code object behind it.  For plan_check only: an engine
-    // planned this way must never reach init_device or a launch.
+    // set with no code object behind it.  For plan_check, which plans a bare
+    // MdpEnginePlan: a plan is not an engine, and nothing that uploads or
+    // launches takes one.
     TablesOnly
 };
 // Plan the engine for problem p (eng->opts parsed): the generic plan, then the
 // direct / chunked / vlds / wide one the problem and the options select, with
 // lds_max the device's LDS per workgroup (160 KiB on gfx950).  jit_t (may be
 // null) receives the steady-clock seconds around the hipRTC step.
-int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t);
+int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t);
 
-#define MDP_PLAN_GRID 1  // (plan_check.cpp also builds against planners without one: scripts/jit_sources.py --rev)
+#define MDP_PLAN_GRID 1    // (plan_check.cpp also builds against planners without these: scripts/jit_sources.py --rev)
+#define MDP_ENGINE_PLAN 1  // the planner takes an MdpEnginePlan
 // The grid plan of e[ne] x c[nc] on a device of ncu compute units: refuses a
 // c the engine does not take (MDP_EINVAL) and Z rows past k_zrows' LDS
 // (MDP_EUNSUPPORTED), rebuilds ct when the grid's |c| bound (at least
 // eng->cbound) is not the one it holds (g.tables_new), and fills g but for
 // the forward launch.  The engine's forward shape must be known (jit_source
 // of one variant has run: mdp_plan_engine's compile, or plan_check's digest).
-int mdp_plan_grid(const mdp_engine *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
+int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
                   uint32_t ncu, MdpGridPlan &g);
 // The mdp_fwd_jit launch of g, once its variant's shape is known (jit_build or
 // jit_source of g.variant has run: the generator settles the fused shape).
-void mdp_plan_fwd_launch(const mdp_engine *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g);
+void mdp_plan_fwd_launch(const MdpEnginePlan *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g);
 // Can any grid of this plan run the fused forward kernel?
-bool mdp_plan_fused_capable(const mdp_engine *eng);
+bool mdp_plan_fused_capable(const MdpEnginePlan *eng);
 // The c-independent tables of the direct and wide paths: sv[row][b], the
 // colonisation sum of variable column b for row's hidden state (+inf for the
 // columns of j: pressure fmin(c inf, 1) = 1.0), and the packed items {B | row
 // << 24, j | (row >> 8) << 24}; one spare element each.
-void mdp_plan_item_tables(const mdp_engine *eng, std::vector<double> &sv, std::vector<uint2> &items);
+void mdp_plan_item_tables(const MdpEnginePlan *eng, std::vector<double> &sv, std::vector<uint2> &items);
 // Does kernel slot k (0: Q rows / k_zpv, 1: k_coefs, 2: forward) run on this path?
-bool mdp_plan_slot_active(const mdp_engine *eng, const MdpGridPlan &g, int k);
+bool mdp_plan_slot_active(const MdpEnginePlan *eng, const MdpGridPlan &g, int k);
 // The kernel instantiations one run of the grid notes for mdp_engine_launched,
 // sorted (the generic path's forward kernel is left to its launcher).
-std::vector<std::string> mdp_plan_grid_kernels(const mdp_engine *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc);
+std::vector<std::string> mdp_plan_grid_kernels(const MdpEnginePlan *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc);
 
-void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
+// The arithmetic of mdp_engine_get_info / _work / _work_fact; from the device
+// contexts: their count, the |c| bound the first one's c tables hold for
+// (< 0: none yet), the current grids' e rows on the s-form (ns of nall).
+void mdp_plan_info(const MdpEnginePlan *eng, int n_devices, mdp_engine_info *info);
+void mdp_plan_work(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double *flop_impl, double *flop_survey,
+                   double *bytes_min);
+void mdp_plan_work_fact(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double cmax, double ns, double nall,
+                        mdp_work *w);
+
+void z_split(const MdpEnginePlan *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
              std::vector<uint32_t> *cols = nullptr);
-std::string jit_source(mdp_engine *eng, int variant);  // the forward kernel's source (no hipRTC)
-int jit_build(mdp_engine *eng, int variant);
-int jit_build_chunks(mdp_engine *eng);
+std::string jit_source(MdpEnginePlan *eng, int variant);  // the forward kernel's source (no hipRTC)
+int jit_build(MdpEnginePlan *eng, int variant);
+int jit_build_chunks(MdpEnginePlan *eng);
 
 #endif

@@ -2,17 +2,19 @@
 // likelihood engine for the stochastic patch occupancy model: the device unit.
 //
 // Files of the engine:
-//   spom_engine.h    constants, types and size helpers shared by the planner,
-//                    the kernels and the launchers
+//   spom_engine.h    constants, the plan types (MdpEnginePlan, MdpCTables,
+//                    MdpGridPlan) and size helpers shared by the planner, the
+//                    kernels and the launchers
 //   spom_plan.cpp    host planning: options, the plan tables the kernels
 //                    index, the hipRTC sources, per grid the c tables and the
 //                    grid plan (mdp_plan_grid: kernel variant, point list,
-//                    chunk widths, buffer sizes, launch shape), the host-only
-//                    C ABI functions; no HIP runtime call
-//   spom_engine.hip  (this file) the kernels, device set-up (uploads;
+//                    chunk widths, buffer sizes, launch shape), the work
+//                    counts; no HIP runtime call, no sight of a device context
+//   spom_engine.hip  (this file) the kernels, the engine (mdp_engine: the plan
+//                    plus its device contexts, DevCtx, whose buffers own their
+//                    memory: DevBuf, spom_dev.h), device set-up (uploads;
 //                    set_grid_dev grows and uploads what the grid plan says),
-//                    the launch paths, run_dev, timing and the rest of the C
-//                    ABI
+//                    the launch paths, run_dev, timing and the C ABI
 //   spom_jit.cpp     generator of the specialised forward kernel's source
 //   spom_jit_rtc.cpp its hipRTC compilation and code-object caches
 //
@@ -40,11 +42,108 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <set>
 #include <string>
 #include <vector>
 
 #include "spom_dev.h"
 #include "spom_engine.h"
+
+// ---------------------------------------------------------------------------
+// the engine: its plan, its device contexts, its run-time state
+// ---------------------------------------------------------------------------
+// a kernel instantiation a context has noted (note_launch): the launch
+// site's format string, by address, and its arguments
+struct LaunchNote {
+    const char *fmt;
+    uint64_t a[4];
+};
+
+// The handles of a device context, as the BASE of DevCtx, which holds the
+// buffers.  The release order is by declaration: ~DevCtx's body makes the
+// device current, then DevCtx's members go (the buffers), then this base: the
+// events, the modules, the stream.
+struct DevHandles {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
+    // reading at kJitKblockTall threads (tall grids, mdp_plan_grid)
+    hipModule_t jit_mod[3] = {nullptr, nullptr, nullptr};
+    std::vector<hipModule_t> cmod;  // a long series: one forward kernel per chunk of years
+    std::vector<hipEvent_t> ev;     // kNumEv events per profiled run, reused
+    DevHandles() = default;
+    DevHandles(const DevHandles &) = delete;
+    DevHandles &operator=(const DevHandles &) = delete;
+    ~DevHandles()
+    {
+        for (hipEvent_t x : ev) (void)hipEventDestroy(x);
+        for (hipModule_t m : jit_mod)
+            if (m) (void)hipModuleUnload(m);
+        for (hipModule_t m : cmod) (void)hipModuleUnload(m);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// One device of an engine.  Neither copied nor moved (mdp_engine::devs is
+// built at its final size): the base's handles are released exactly once.
+struct DevCtx : DevHandles {
+    mutable std::vector<LaunchNote> noted;  // what this context has reported to mdp_engine::launched
+    DevBuf<double> S;
+    DevBuf<uint32_t> var_cols, row_col, pairA, pairB, pairOff, udesc, prog, pairPart0, partP, partK0;
+    DevBuf<double> e, c;
+    uint32_t ne = 0, nc = 0;
+    MdpCTables ct;     // the c tables on the device (host copy and the bound they hold for)
+    MdpGridPlan plan;  // the current grid's plan (set_grid_dev)
+    // the plan's point list and its e values by position: a listed kernel
+    // loads its e values by position, beside the list, instead of through it
+    // (position -> row -> e would be two round trips in series)
+    DevBuf<uint32_t> plist;
+    DevBuf<double> elist, ZPV, R, out, gpart;
+    DevBuf<unsigned long long> stamps[3];  // k_zpv, k_coefs, k_forward
+    // direct path: k_zrows / k_qrows tables (zs, row-major [row][k], depends
+    // on the grid's c range)
+    DevBuf<double> zs, sv, Qrow, Zg;
+    DevBuf<double> zsq;  // zs chain-major, [row][k mod 4][k / 4] (k_qrows: a lane's chain contiguous)
+    DevBuf<double> zc;   // Z-row series coefficients [row][kZTerms]
+    DevBuf<uint2> items;  // per item {B | row << 24, j | (row >> 8) << 24}
+    DevBuf<uint2> qslot;  // k_qrows phase-3 lane table
+    DevBuf<uint32_t> qlane;  // k_qrows phase-3 Pc slots per lane (nvar <= 8)
+    DevBuf<uint32_t> islot;  // k_qrows: each item's Pc slot
+    DevBuf<uint32_t> qstart, qitem;
+    DevBuf<double> coltab;  // fused kernel's column tables (MdpCTables::coltab)
+    bool qrows_attr_set = false;  // k_qrows' LDS limit raised on this device
+    hipFunction_t jit_fn[3] = {nullptr, nullptr, nullptr};  // of jit_mod
+    // the chunks of a long series (cmod): the state vector handed over in
+    // vscr[state][c][e] (ldv e values per (state, c))
+    std::vector<hipFunction_t> cfn;
+    std::vector<DevBuf<uint32_t>> cqidx;  // per chunk: gather indices into the Q row (empty: whole row)
+    DevBuf<double> vscr;
+    uint32_t ncu = 0;    // the device's compute units (0: not asked yet)
+    // wide path: per-chunk item factors, state-vector scratch, tables
+    DevBuf<double> Pg, V;
+    DevBuf<uint32_t> np_d, udesc_w;
+    DevBuf<uint2> mma_kt, mma_wplan;
+    DevBuf<uint32_t> mma_kbase, mma_desc, mma_dbase;
+    DevBuf<uint2> mmt_kt, mmt_ktile, mmt_wplan;  // k_fwd_mmt tables
+    DevBuf<uint32_t> mmt_cidx;
+    DevBuf<uint32_t> hs_kt, hs_cidx, hs_pbase, hs_dpos, hs_dbase, hs_pk;
+    DevBuf<uint2> hs_ppos, hs_dpk;
+    DevBuf<uint4> hs_wplan, hs_pass;  // (hs_*: k_fwd_hs tables)
+    std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
+    size_t ev_used = 0;          // event sets recorded since the last collect
+    ~DevCtx() { (void)hipSetDevice(device); }
+};
+
+struct mdp_engine : MdpEnginePlan {
+    std::vector<DevCtx> devs;
+    int layout = MDP_LAYOUT_EC;  // mdp_engine_run's output layout (mdp_engine_set_layout)
+    mutable std::set<std::string, std::less<>> launched;  // kernel instantiations launched so far (mdp_engine_launched)
+    mutable std::mutex launched_mu;                         // engines may be driven from several host threads
+    int profiling = 0;
+    double last_ms[3] = {0, 0, 0};  // mean per run over the last collected runs
+    int nlast = 0;
+    uint64_t runs_collected = 0;
+};
 
 namespace {
 
@@ -2253,16 +2352,8 @@ int upload_ctables(DevCtx &d)
 {
     const MdpCTables &t = d.ct;
     int rc;
-    if ((rc = dev_grow(d.zs, d.cap_zs, t.zs.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zs, t.zs.data(), t.zs.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = dev_grow(d.zsq, d.cap_zsq, t.zsq.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zsq, t.zsq.data(), t.zsq.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = dev_grow(d.zc, d.cap_zc, t.zc.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.zc, t.zc.data(), t.zc.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (t.coltab.empty()) return MDP_OK;
-    if ((rc = dev_grow(d.coltab, d.cap_coltab, t.coltab.size()))) return rc;
-    HIP_TRY(hipMemcpy(d.coltab, t.coltab.data(), t.coltab.size() * sizeof(double), hipMemcpyHostToDevice));
-    return MDP_OK;
+    if ((rc = d.zs.assign(t.zs)) || (rc = d.zsq.assign(t.zsq)) || (rc = d.zc.assign(t.zc))) return rc;
+    return t.coltab.empty() ? MDP_OK : d.coltab.assign(t.coltab);
 }
 
 // Load a code object; if the runtime refuses it (a stale or foreign object
@@ -2290,12 +2381,8 @@ int jit_load(mdp_engine *eng, DevCtx &d, int variant)
         // loaded, so a later call retries instead of running some chunks
         std::vector<hipModule_t> mods;
         std::vector<hipFunction_t> fns;
-        std::vector<uint32_t *> qidx;
-        auto unload = [&]() {
-            for (hipModule_t m : mods) (void)hipModuleUnload(m);
-            for (uint32_t *q : qidx)
-                if (q) (void)hipFree(q);
-        };
+        std::vector<DevBuf<uint32_t>> qidx(nch);  // (freed with this scope unless committed)
+        auto unload = [&]() { for (hipModule_t m : mods) (void)hipModuleUnload(m); };
         for (size_t i = 0; i < nch; ++i) {
             hipModule_t m;
             hipFunction_t f;
@@ -2309,12 +2396,10 @@ int jit_load(mdp_engine *eng, DevCtx &d, int variant)
                 return mdp_set_error(MDP_EHIP, "loading forward chunk %zu failed: %s", i, hipGetErrorString(e));
             }
             fns.push_back(f);
-            uint32_t *qi = nullptr;
-            if (!eng->chunks[i].qidx.empty() && (rc = dev_upload(qi, eng->chunks[i].qidx))) {
+            if (!eng->chunks[i].qidx.empty() && (rc = qidx[i].assign(eng->chunks[i].qidx))) {
                 unload();
                 return rc;
             }
-            qidx.push_back(qi);
         }
         d.cmod = std::move(mods);
         d.cfn = std::move(fns);
@@ -2362,25 +2447,21 @@ int init_generic(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
         if (!isvar[k]) row_col.push_back(k);
     for (uint32_t b = 0; b < p->nvar; ++b) row_col.push_back(p->var_cols[b]);
     std::vector<double> M(p->M, p->M + (size_t)p->n * p->n);
-    double *dM = nullptr;
-    size_t cap_S = 0;  // d.S is allocated once
-    if ((rc = dev_upload(dM, M))) return rc;
-    if ((rc = dev_upload(d.var_cols, var)) || (rc = dev_upload(d.row_col, row_col)) ||
-        (rc = dev_upload(d.pairA, eng->pairA)) || (rc = dev_upload(d.pairB, eng->pairB)) ||
-        (rc = dev_upload(d.pairOff, eng->pairOff)) || (rc = dev_upload(d.udesc, eng->udesc)) ||
-        (rc = dev_upload(d.pairPart0, eng->pairPart0)) || (rc = dev_upload(d.partP, eng->partP)) ||
-        (rc = dev_upload(d.partK0, eng->partK0)) ||
-        (rc = dev_upload(d.prog, eng->prog)) ||
-        (rc = dev_grow(d.S, cap_S, (size_t)p->n * eng->nstates))) {
-        (void)hipFree(dM);
+    DevBuf<double> dM;  // k_colsum's input only
+    if ((rc = dM.assign(M))) return rc;
+    if ((rc = d.var_cols.assign(var)) || (rc = d.row_col.assign(row_col)) ||
+        (rc = d.pairA.assign(eng->pairA)) || (rc = d.pairB.assign(eng->pairB)) ||
+        (rc = d.pairOff.assign(eng->pairOff)) || (rc = d.udesc.assign(eng->udesc)) ||
+        (rc = d.pairPart0.assign(eng->pairPart0)) || (rc = d.partP.assign(eng->partP)) ||
+        (rc = d.partK0.assign(eng->partK0)) ||
+        (rc = d.prog.assign(eng->prog)) ||
+        (rc = d.S.grow((size_t)p->n * eng->nstates)))
         return rc;
-    }
     dim3 grid((eng->nstates + kBlock - 1) / kBlock, p->n);
-    hipLaunchKernelGGL(k_colsum, grid, dim3(kBlock), 0, d.stream, dM, d.var_cols, d.row_col, p->n,
-                       p->nvar, eng->nstates, d.S);
+    hipLaunchKernelGGL(k_colsum, grid, dim3(kBlock), 0, d.stream, dM.get(), d.var_cols.get(), d.row_col.get(), p->n, p->nvar,
+                       eng->nstates, d.S.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(d.stream));
-    (void)hipFree(dM);
     if (eng->coef_lds > 64 * 1024)
         return for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) {
             return set_lds_limit(k_coefs<ldsz(), ldsp(), nv()>, eng->coef_lds);
@@ -2404,29 +2485,29 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
         mdp_plan_item_tables(eng, sv, items);
         std::vector<uint32_t> qitem = eng->qitem;
         qitem.push_back(0u);
-        if ((rc = dev_upload(d.sv, sv)) || (rc = dev_upload(d.items, items)) ||
-            (rc = dev_upload(d.qstart, eng->qstart)) || (rc = dev_upload(d.qitem, qitem)) ||
-            (rc = dev_upload(d.qslot, eng->qslot)) || (rc = dev_upload(d.qlane, eng->qlane)) ||
-            (rc = dev_upload(d.islot, eng->islot)))
+        if ((rc = d.sv.assign(sv)) || (rc = d.items.assign(items)) ||
+            (rc = d.qstart.assign(eng->qstart)) || (rc = d.qitem.assign(qitem)) ||
+            (rc = d.qslot.assign(eng->qslot)) || (rc = d.qlane.assign(eng->qlane)) ||
+            (rc = d.islot.assign(eng->islot)))
             return rc;
         if (eng->wide) {
-            if ((rc = dev_upload(d.np_d, eng->np)) || (rc = dev_upload(d.udesc_w, eng->udesc_d))) return rc;
+            if ((rc = d.np_d.assign(eng->np)) || (rc = d.udesc_w.assign(eng->udesc_d))) return rc;
             if (eng->mma &&
-                ((rc = dev_upload(d.mma_kt, eng->mma_kt)) || (rc = dev_upload(d.mma_kbase, eng->mma_kbase)) ||
-                 (rc = dev_upload(d.mma_wplan, eng->mma_wplan)) ||
-                 (rc = dev_upload(d.mma_desc, eng->mma_desc)) || (rc = dev_upload(d.mma_dbase, eng->mma_dbase))))
+                ((rc = d.mma_kt.assign(eng->mma_kt)) || (rc = d.mma_kbase.assign(eng->mma_kbase)) ||
+                 (rc = d.mma_wplan.assign(eng->mma_wplan)) ||
+                 (rc = d.mma_desc.assign(eng->mma_desc)) || (rc = d.mma_dbase.assign(eng->mma_dbase))))
                 return rc;
             if (eng->mmt &&
-                ((rc = dev_upload(d.mmt_kt, eng->mmt_kt)) || (rc = dev_upload(d.mmt_ktile, eng->mmt_ktile)) ||
-                 (rc = dev_upload(d.mmt_wplan, eng->mmt_wplan)) || (rc = dev_upload(d.mmt_cidx, eng->mmt_cidx))))
+                ((rc = d.mmt_kt.assign(eng->mmt_kt)) || (rc = d.mmt_ktile.assign(eng->mmt_ktile)) ||
+                 (rc = d.mmt_wplan.assign(eng->mmt_wplan)) || (rc = d.mmt_cidx.assign(eng->mmt_cidx))))
                 return rc;
             if (eng->hs &&
-                ((rc = dev_upload(d.hs_kt, eng->hs_kt)) || (rc = dev_upload(d.hs_cidx, eng->hs_cidx)) ||
-                 (rc = dev_upload(d.hs_pbase, eng->hs_pbase)) || (rc = dev_upload(d.hs_ppos, eng->hs_ppos)) ||
-                 (rc = dev_upload(d.hs_dpos, eng->hs_dpos)) || (rc = dev_upload(d.hs_dbase, eng->hs_dbase)) ||
-                 (rc = dev_upload(d.hs_pk, eng->hs_pk)) ||
-                 (rc = dev_upload(d.hs_wplan, eng->hs_wplan)) || (rc = dev_upload(d.hs_pass, eng->hs_pass)) ||
-                 (rc = dev_upload(d.hs_dpk, eng->hs_dpk))))
+                ((rc = d.hs_kt.assign(eng->hs_kt)) || (rc = d.hs_cidx.assign(eng->hs_cidx)) ||
+                 (rc = d.hs_pbase.assign(eng->hs_pbase)) || (rc = d.hs_ppos.assign(eng->hs_ppos)) ||
+                 (rc = d.hs_dpos.assign(eng->hs_dpos)) || (rc = d.hs_dbase.assign(eng->hs_dbase)) ||
+                 (rc = d.hs_pk.assign(eng->hs_pk)) ||
+                 (rc = d.hs_wplan.assign(eng->hs_wplan)) || (rc = d.hs_pass.assign(eng->hs_pass)) ||
+                 (rc = d.hs_dpk.assign(eng->hs_dpk))))
                 return rc;
             return wide_lds_limits(eng);
         }
@@ -2452,30 +2533,6 @@ int qrows_attrs(const mdp_engine *eng, DevCtx &d)
     return MDP_OK;
 }
 
-void free_device(DevCtx &d)
-{
-    (void)hipSetDevice(d.device);
-    void *ptrs[] = {d.S, d.var_cols, d.row_col, d.pairA, d.pairB, d.pairOff, d.udesc, d.prog,
-                    d.pairPart0, d.partP, d.partK0, d.e, d.c, d.ZPV, d.R, d.out, d.gpart,
-                    d.zs, d.zsq, d.sv, d.Qrow, d.Zg, d.coltab, d.items, d.itemB, d.qstart, d.qitem,
-                    d.Pg, d.V, d.np_d, d.udesc_w, d.zc, d.plist, d.elist, d.qslot, d.qlane, d.islot,
-                    d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan,
-                    d.mmt_kt, d.mmt_ktile, d.mmt_wplan, d.mmt_cidx,
-                    d.hs_kt, d.hs_cidx, d.hs_pbase, d.hs_ppos, d.hs_dpos, d.hs_dbase, d.hs_pk,
-                    d.hs_wplan, d.hs_pass, d.hs_dpk,
-                    d.stamps[0], d.stamps[1], d.stamps[2]};
-    for (void *ptr : ptrs)
-        if (ptr) (void)hipFree(ptr);
-    for (hipEvent_t ev : d.ev) (void)hipEventDestroy(ev);
-    for (hipModule_t m : d.jit_mod)
-        if (m) (void)hipModuleUnload(m);
-    for (hipModule_t m : d.cmod) (void)hipModuleUnload(m);
-    for (uint32_t *q : d.cqidx)
-        if (q) (void)hipFree(q);
-    if (d.vscr) (void)hipFree(d.vscr);
-    if (d.stream) (void)hipStreamDestroy(d.stream);
-}
-
 // A new grid: plan it on the host (mdp_plan_grid: the refusals, the kernel
 // variant, the point list, the chunk widths, every buffer size), then grow
 // and upload what the plan says and load the forward kernel it names.
@@ -2498,30 +2555,22 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
         }
     }
     if (rc) return rc;
-    if ((rc = dev_grow(d.e, d.cap_e, ne)) || (rc = dev_grow(d.c, d.cap_c, nc)) ||
-        (g.n_qrow && (rc = dev_grow(d.Qrow, d.cap_qrow, g.n_qrow))) || (g.n_zg && (rc = dev_grow(d.Zg, d.cap_zg, g.n_zg))) ||
-        (g.n_pg && (rc = dev_grow(d.Pg, d.cap_pg, g.n_pg))) || (g.n_v && (rc = dev_grow(d.V, d.cap_v, g.n_v))) ||
-        (g.n_vscr && (rc = dev_grow(d.vscr, d.cap_vscr, g.n_vscr))) || (g.n_zpv && (rc = dev_grow(d.ZPV, d.cap_zpv, g.n_zpv))) ||
-        (g.n_r && (rc = dev_grow(d.R, d.cap_r, g.n_r))) || (g.n_gpart && (rc = dev_grow(d.gpart, d.cap_gpart, g.n_gpart))))
+    if ((rc = d.e.assign(e, ne)) || (rc = d.c.assign(c, nc)) || (g.n_qrow && (rc = d.Qrow.grow(g.n_qrow))) ||
+        (g.n_zg && (rc = d.Zg.grow(g.n_zg))) || (g.n_pg && (rc = d.Pg.grow(g.n_pg))) || (g.n_v && (rc = d.V.grow(g.n_v))) ||
+        (g.n_vscr && (rc = d.vscr.grow(g.n_vscr))) || (g.n_zpv && (rc = d.ZPV.grow(g.n_zpv))) ||
+        (g.n_r && (rc = d.R.grow(g.n_r))) || (g.n_gpart && (rc = d.gpart.grow(g.n_gpart))))
         return rc;
-    if (g.pg_zero && g.n_pg) HIP_TRY(hipMemset(d.Pg, 0, g.n_pg * sizeof(double)));
+    if (g.pg_zero && g.n_pg) HIP_TRY(hipMemset(d.Pg.get(), 0, g.n_pg * sizeof(double)));
     if (g.zrows_lds > 64 * 1024 && (rc = set_lds_limit(k_zrows, g.zrows_lds))) return rc;
-    if (!g.plist_identity) {
-        if ((rc = dev_grow(d.plist, d.cap_plist, g.plist.size())) || (rc = dev_grow(d.elist, d.cap_elist, g.elist.size())))
-            return rc;
-        HIP_TRY(hipMemcpy(d.plist, g.plist.data(), g.plist.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d.elist, g.elist.data(), g.elist.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
+    if (!g.plist_identity && ((rc = d.plist.assign(g.plist)) || (rc = d.elist.assign(g.elist)))) return rc;
     if (eng->jit && !eng->wide) {
         if ((rc = jit_load(eng, d, g.variant))) return rc;
         mdp_plan_fwd_launch(eng, d.ct, ne, nc, g);  // (the variant's shape is settled once it is built)
     }
     for (int k = 0; k < 3 && eng->diag; ++k) {
-        if ((rc = dev_grow(d.stamps[k], d.cap_st[k], g.nst[k] * kStampSlots))) return rc;
-        HIP_TRY(hipMemset(d.stamps[k], 0, d.cap_st[k] * sizeof(unsigned long long)));
+        if ((rc = d.stamps[k].grow(g.nst[k] * kStampSlots))) return rc;
+        HIP_TRY(hipMemset(d.stamps[k].get(), 0, d.stamps[k].cap() * sizeof(unsigned long long)));
     }
-    if (ne) HIP_TRY(hipMemcpy(d.e, e, ne * sizeof(double), hipMemcpyHostToDevice));
-    if (nc) HIP_TRY(hipMemcpy(d.c, c, nc * sizeof(double), hipMemcpyHostToDevice));
     d.ne = ne;
     d.nc = nc;
     d.plan = std::move(g);
@@ -2537,11 +2586,11 @@ void launch_fwd_epl(const mdp_engine *eng, const DevCtx &d, double *out, OutStri
     note_launch(eng, d, "%s<%d,%d,%d>", eng->fwd_lds ? "k_forward_lds" : "k_forward", NP, DEG, EPL);
     if (eng->fwd_lds)
         MDP_LAUNCH((k_forward_lds<NP, DEG, EPL>), grid, dim3(kBlock), eng->fwd_lds_bytes, s,
-                           d.R, ldR_of(eng), d.prog, nprog, eng->np[0], eng->prior0, d.e, d.ne, out, se,
-                           sc, d.stamps[2]);
+                           d.R.get(), ldR_of(eng), d.prog.get(), nprog, eng->np[0], eng->prior0, d.e.get(), d.ne, out, se,
+                           sc, d.stamps[2].get());
     else
-        MDP_LAUNCH((k_forward<NP, DEG, EPL>), grid, dim3(kBlock), 0, s, d.R, ldR_of(eng),
-                           d.prog, nprog, eng->np[0], eng->prior0, d.e, d.ne, out, se, sc);
+        MDP_LAUNCH((k_forward<NP, DEG, EPL>), grid, dim3(kBlock), 0, s, d.R.get(), ldR_of(eng),
+                           d.prog.get(), nprog, eng->np[0], eng->prior0, d.e.get(), d.ne, out, se, sc);
 }
 
 template <int NP, int DEG>
@@ -2579,14 +2628,14 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
         // mdp_fwd_jit's parameters (spom_jit.h declares them once, for the
         // generated signature and for this struct)
         MdpFwdJitArgs a;
-        a.tab = g.fused ? d.coltab : d.Qrow;  // the table the variant stages first
-        a.cvals = d.c;
-        a.evals = g.fwd_listed ? d.elist : d.e;  // a listed kernel reads e by list position
+        a.tab = g.fused ? d.coltab.get() : d.Qrow.get();  // the table the variant stages first
+        a.cvals = d.c.get();
+        a.evals = g.fwd_listed ? d.elist.get() : d.e.get();  // a listed kernel reads e by list position
         a.ct_len = d.ct.ct_len;
         a.nlist = g.fwd_nlist;
         a.ne = d.ne;
         a.nc = d.nc;
-        a.plist = g.fwd_listed ? d.plist : nullptr;
+        a.plist = g.fwd_listed ? d.plist.get() : nullptr;
         a.nblk = (uint32_t)g.fwd_nblk;
         a.kmax = d.ct.kmax;
         a.one = 1;
@@ -2594,9 +2643,9 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
         a.ld_out = os.se;
         a.out_cs = os.sc;
         a.prior0 = eng->prior0;
-        a.vscr = d.vscr;
+        a.vscr = d.vscr.get();
         a.ldv = g.ldv;
-        a.stamps = d.stamps[2];
+        a.stamps = d.stamps[2].get();
         auto args = a.params();
         static_assert(std::tuple_size<decltype(args)>::value == 19, "one kernelParams entry per parameter of mdp_fwd_jit");
         if (!eng->chunks.empty()) {  // a long series: its chunks in order on the stream
@@ -2604,7 +2653,7 @@ int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
             if (nch != eng->chunks.size() || d.cqidx.size() != nch)
                 return mdp_set_error(MDP_EHIP, "forward chunks not loaded (%zu of %zu)", nch, eng->chunks.size());
             for (size_t i = 0; i < nch; ++i) {
-                a.qidx = d.cqidx[i];  // the chunk's gather list (args points at the member)
+                a.qidx = d.cqidx[i].get();  // the chunk's gather list (args points at the member)
                 HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], nthreads, 1, 1, g.fwd_block, 1, 1, 0, s,
                                                  args.data(), nullptr, i == 0 ? t_kev.start : nullptr,
                                                  i + 1 == nch ? t_kev.stop : nullptr, 0));
@@ -2636,10 +2685,10 @@ int launch_coefs(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
 {
     for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) {
         note_launch(eng, d, kFmtCoefs, (int)ldsz(), (int)ldsp(), nv());
-        MDP_LAUNCH((k_coefs<ldsz(), ldsp(), nv()>), dim3(d.nc), dim3(kBlock), eng->coef_lds, s, d.ZPV, eng->nstates,
-                   eng->nvar, d.pairA, d.pairB, d.pairOff, d.pairPart0, eng->npairs, d.partP, d.partK0,
-                   (uint32_t)eng->partP.size(), eng->ncoef, d.udesc, eng->nuses, eng->deg, d.R, ldR_of(eng), d.gpart,
-                   d.stamps[1]);
+        MDP_LAUNCH((k_coefs<ldsz(), ldsp(), nv()>), dim3(d.nc), dim3(kBlock), eng->coef_lds, s, d.ZPV.get(), eng->nstates,
+                   eng->nvar, d.pairA.get(), d.pairB.get(), d.pairOff.get(), d.pairPart0.get(), eng->npairs, d.partP.get(),
+                   d.partK0.get(), (uint32_t)eng->partP.size(), eng->ncoef, d.udesc.get(), eng->nuses, eng->deg, d.R.get(),
+                   ldR_of(eng), d.gpart.get(), d.stamps[1].get());
     });
     HIP_TRY(hipGetLastError());
     return MDP_OK;
@@ -2657,8 +2706,8 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
         const dim3 gi((eng->nitems + kBlock - 1) / kBlock, n);
         for_nv(eng, [&](auto nv) {
             note_launch(eng, d, kFmtWitems, nv());
-            hipLaunchKernelGGL((k_witems<nv()>), gi, dim3(kBlock), 0, s, d.c, d.nc, c0, eng->nvar, d.Zg, d.sv, eng->nitems,
-                               d.items, d.Pg, ldp);
+            hipLaunchKernelGGL((k_witems<nv()>), gi, dim3(kBlock), 0, s, d.c.get(), d.nc, c0, eng->nvar, d.Zg.get(), d.sv.get(),
+                               eng->nitems, d.items.get(), d.Pg.get(), ldp);
         });
     };
     if (eng->hs) {
@@ -2679,8 +2728,9 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
                 note_launch(eng, d, kFmtHs, rt, nb);
                 for_hs(eng, [&](auto RT, auto NB, auto NW) {
                     hipLaunchKernelGGL((k_fwd_hs<RT(), NB(), NW()>), dim3((uint32_t)nbk), dim3(NW() * 64), hs_lds(eng), s,
-                                       d.Pg, ldp, c0, d.np_d, d.hs_kt, d.hs_cidx, d.hs_wplan, d.hs_pass, d.hs_pbase,
-                                       d.hs_ppos, d.hs_dpos, d.hs_dbase, d.hs_dpk, d.hs_pk, eng->tmax, eng->prior0, d.e,
+                                       d.Pg.get(), ldp, c0, d.np_d.get(), d.hs_kt.get(), d.hs_cidx.get(), d.hs_wplan.get(),
+                                       d.hs_pass.get(), d.hs_pbase.get(), d.hs_ppos.get(), d.hs_dpos.get(), d.hs_dbase.get(),
+                                       d.hs_dpk.get(), d.hs_pk.get(), eng->tmax, eng->prior0, d.e.get(),
                                        d.ne, out, os.se, os.sc, eng->hs_probe);
                 });
             }
@@ -2692,8 +2742,8 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
             witems(c0, n, eng->nitems);
             const dim3 gq((uint32_t)((eng->ldQ + kBlock - 1) / kBlock), n);
             note_launch(eng, d, "k_wq");
-            hipLaunchKernelGGL(k_wq, gq, dim3(kBlock), 0, s, c0, eng->nitems, d.Pg, eng->ncoef_d, d.qstart, d.qitem,
-                               d.Qrow, (uint32_t)eng->ldQ);
+            hipLaunchKernelGGL(k_wq, gq, dim3(kBlock), 0, s, c0, eng->nitems, d.Pg.get(), eng->ncoef_d, d.qstart.get(), d.qitem.get(),
+                               d.Qrow.get(), (uint32_t)eng->ldQ);
         }
     } else if (eng->mmt) {  // the matrix-core forward: every c in one launch, blocks dealt XCD-aware
         const uint32_t rt = eng->mmt_rt, rows = eng->mmt_rows, npb = (d.ne + mmt_pts(rt) - 1) / mmt_pts(rt);
@@ -2703,8 +2753,8 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
         note_launch(eng, d, kFmtMmt, rt, rows, db ? "2buf" : "1buf");
         for_mmt(eng, [&](auto RT, auto ROWS, auto DB) {
             hipLaunchKernelGGL((k_fwd_mmt<RT(), ROWS(), DB()>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s,
-                               d.Qrow, (uint32_t)eng->ldQ, d.np_d, d.mmt_kt, d.mmt_cidx, d.mmt_ktile, d.mmt_wplan,
-                               eng->tmax, eng->prior0, d.e, d.ne, eng->maxA, out, os.se, os.sc);
+                               d.Qrow.get(), (uint32_t)eng->ldQ, d.np_d.get(), d.mmt_kt.get(), d.mmt_cidx.get(), d.mmt_ktile.get(),
+                               d.mmt_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, eng->maxA, out, os.se, os.sc);
         });
     } else if (eng->mma) {  // round 5's matrix-core forward (MDP_WIDE_MMA=1; years of up to 256 states)
         uint32_t se = os.se, sc = os.sc;
@@ -2714,9 +2764,10 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
             const dim3 g((d.ne + pts - 1) / pts, n);
             note_launch(eng, d, kFmtMma, eng->mma_npm);
             for_mma(eng, [&](auto NPM) {
-                hipLaunchKernelGGL((k_fwd_mma<NPM()>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ,
-                                   d.np_d, d.mma_kt, d.mma_kbase, d.mma_desc, d.mma_dbase, d.mma_wplan, eng->tmax,
-                                   eng->prior0, d.e, d.ne, c0, eng->maxA, eng->mma_ktmax, eng->ncoef_d, out, se, sc);
+                hipLaunchKernelGGL((k_fwd_mma<NPM()>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ,
+                                   d.np_d.get(), d.mma_kt.get(), d.mma_kbase.get(), d.mma_desc.get(), d.mma_dbase.get(),
+                                   d.mma_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, eng->mma_ktmax,
+                                   eng->ncoef_d, out, se, sc);
             });
         }
     } else {
@@ -2726,8 +2777,9 @@ int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutS
             const uint32_t n = std::min(cb, d.nc - c0);
             const dim3 g((d.ne + kBlock - 1) / kBlock, n);
             note_launch(eng, d, "k_fwd_wide");
-            hipLaunchKernelGGL(k_fwd_wide, g, dim3(kBlock), wide_lds(eng), s, d.Qrow, (uint32_t)eng->ldQ, d.udesc_w,
-                               d.np_d, eng->tmax, eng->prior0, d.e, d.ne, c0, eng->maxA, d.V, eng->npmax, out, se, sc);
+            hipLaunchKernelGGL(k_fwd_wide, g, dim3(kBlock), wide_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ, d.udesc_w.get(),
+                               d.np_d.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, d.V.get(), eng->npmax, out, se,
+                               sc);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -2746,8 +2798,8 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
         const uint32_t kmax = d.ct.kmax;
         const dim3 grid((d.nc + 64 * kZC - 1) / (64 * kZC), (eng->nj + kZRows - 1) / kZRows);
         note_launch(eng, d, "k_zrows");
-        MDP_LAUNCH(k_zrows, grid, dim3(kBlock), (size_t)kZRows * kmax * sizeof(double), s, d.c, d.nc, eng->nj,
-                   kmax, d.zs, d.zc, d.Zg);
+        MDP_LAUNCH(k_zrows, grid, dim3(kBlock), (size_t)kZRows * kmax * sizeof(double), s, d.c.get(), d.nc, eng->nj,
+                   kmax, d.zs.get(), d.zc.get(), d.Zg.get());
         HIP_TRY(hipGetLastError());
         return MDP_OK;
     }
@@ -2758,11 +2810,11 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
         const size_t lds = qrows_lds(eng, cb);
         for_qrows(eng, cb, [&](auto nv, auto ex, auto CB) {
             note_launch(eng, d, kFmtQrows, nv(), (int)ex(), CB());
-            MDP_LAUNCH((k_qrows<nv(), ex(), CB()>), grid, dim3(kQrowsBlock), lds, s, d.c, d.nc, eng->nvar, eng->nj,
-                       d.ct.kmax, d.zsq, d.zc, d.sv, eng->nitems, d.items, eng->ncoef_d, d.qstart,
-                       (uint32_t)eng->qitem.size(), d.qitem, d.Qrow, (uint32_t)eng->ldQ, d.stamps[1],
-                       (uint32_t)(eng->qrows_xcd ? 1u : 0u), d.qslot, (uint32_t)eng->qslot.size(), eng->qslot_lglmax,
-                       (const uint4 *)d.qlane, d.islot, eng->npl_slots);
+            MDP_LAUNCH((k_qrows<nv(), ex(), CB()>), grid, dim3(kQrowsBlock), lds, s, d.c.get(), d.nc, eng->nvar, eng->nj,
+                       d.ct.kmax, d.zsq.get(), d.zc.get(), d.sv.get(), eng->nitems, d.items.get(), eng->ncoef_d, d.qstart.get(),
+                       (uint32_t)eng->qitem.size(), d.qitem.get(), d.Qrow.get(), (uint32_t)eng->ldQ, d.stamps[1].get(),
+                       (uint32_t)(eng->qrows_xcd ? 1u : 0u), d.qslot.get(), (uint32_t)eng->qslot.size(), eng->qslot_lglmax,
+                       (const uint4 *)d.qlane.get(), d.islot.get(), eng->npl_slots);
         });
         HIP_TRY(hipGetLastError());
         return MDP_OK;
@@ -2770,8 +2822,8 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
     if (k == 0) {
         dim3 grid((eng->nstates + kZpvJ - 1) / kZpvJ, (d.nc + kZpvCT - 1) / kZpvCT);
         note_launch(eng, d, "k_zpv");
-        MDP_LAUNCH(k_zpv, grid, dim3(kBlock), 0, s, d.S, eng->nstates, eng->n - eng->nvar, eng->nvar, d.c,
-                   d.nc, d.ZPV, d.stamps[0]);
+        MDP_LAUNCH(k_zpv, grid, dim3(kBlock), 0, s, d.S.get(), eng->nstates, eng->n - eng->nvar, eng->nvar, d.c.get(),
+                   d.nc, d.ZPV.get(), d.stamps[0].get());
         HIP_TRY(hipGetLastError());
         return MDP_OK;
     }
@@ -2924,13 +2976,13 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
             delete eng;
             return mdp_set_error(MDP_ENODEV, "device %d not present (%d visible)", id, ndev);
         }
-    eng->devs.resize(ids.size());
+    eng->devs = std::vector<DevCtx>(ids.size());  // at its final size: a context is neither copied nor moved
     const double st_dev0 = st_now();
     for (size_t i = 0; i < ids.size(); ++i) {
         eng->devs[i].device = ids[i];
         rc = init_device(eng, eng->devs[i], p);
         if (rc) {
-            mdp_engine_destroy(eng);
+            delete eng;
             return rc;
         }
     }
@@ -2943,9 +2995,7 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
 
 void mdp_engine_destroy(mdp_engine *eng)
 {
-    if (!eng) return;
-    for (auto &d : eng->devs) free_device(d);
-    delete eng;
+    delete eng;  // (every device context releases its own: ~DevCtx)
 }
 
 int mdp_engine_set_grid(mdp_engine *eng, const double *e, uint32_t ne, const double *c, uint32_t nc)
@@ -3008,20 +3058,20 @@ int mdp_loglik_grid_layout(mdp_engine *eng, const double *e, uint32_t ne, const 
         DevCtx &d = eng->devs[r];
         const uint32_t rows = r1[r] - r0[r];
         if ((rc = set_grid_dev(eng, d, e + r0[r], rows, c, nc))) return rc;
-        if ((rc = dev_grow(d.out, d.cap_out, (size_t)rows * nc))) return rc;
+        if ((rc = d.out.grow((size_t)rows * nc))) return rc;
         // the layout asked of this call (not the engine's mdp_engine_run
         // layout): the slab [e][c] (ld nc) or [c][e] (ld = the slab's rows)
-        if ((rc = run_dev(eng, d, d.out, ce ? OutStrides{1u, rows} : OutStrides{nc, 1u}, d.stream))) return rc;
+        if ((rc = run_dev(eng, d, d.out.get(), ce ? OutStrides{1u, rows} : OutStrides{nc, 1u}, d.stream))) return rc;
     }
     for (uint32_t r = 0; r < nd; ++r) {
         DevCtx &d = eng->devs[r];
         const uint32_t rows = r1[r] - r0[r];
         HIP_TRY(hipSetDevice(d.device));
         if (rows && !ce)
-            HIP_TRY(hipMemcpyAsync(out + (size_t)r0[r] * nc, d.out, (size_t)rows * nc * sizeof(double),
+            HIP_TRY(hipMemcpyAsync(out + (size_t)r0[r] * nc, d.out.get(), (size_t)rows * nc * sizeof(double),
                                    hipMemcpyDeviceToHost, d.stream));
         else if (rows && nc)  // the slab's columns into out[c][e] at e offset r0
-            HIP_TRY(hipMemcpy2DAsync(out + r0[r], (size_t)ne * sizeof(double), d.out, (size_t)rows * sizeof(double),
+            HIP_TRY(hipMemcpy2DAsync(out + r0[r], (size_t)ne * sizeof(double), d.out.get(), (size_t)rows * sizeof(double),
                                      (size_t)rows * sizeof(double), nc, hipMemcpyDeviceToHost, d.stream));
     }
     for (uint32_t r = 0; r < nd; ++r) {
@@ -3052,9 +3102,9 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
     }
     size_t used = 0;
     for (int k = 0; k < 3; ++k) {
-        if (!d.stamps[k] || !d.plan.nst[k] || !slots[k]) continue;
+        if (d.stamps[k].empty() || !d.plan.nst[k] || !slots[k]) continue;
         std::vector<unsigned long long> h(d.plan.nst[k] * kStampSlots);
-        HIP_TRY(hipMemcpy(h.data(), d.stamps[k], h.size() * sizeof(unsigned long long),
+        HIP_TRY(hipMemcpy(h.data(), d.stamps[k].get(), h.size() * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull, t1 = 0, rs0 = ~0ull, rs1 = 0, re1 = 0;
         double rdur = 0.0;
@@ -3121,7 +3171,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
         }
         w = snprintf(buf + used, len - used, "\n");
         if (w > 0) used = std::min(len - 1, used + (size_t)w);
-        HIP_TRY(hipMemset(d.stamps[k], 0, h.size() * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(d.stamps[k].get(), 0, h.size() * sizeof(unsigned long long)));
     }
     return (int)used;
 }
@@ -3188,7 +3238,7 @@ int mdp_log_check(const double *x, double *y, size_t n)
         return mdp_set_error(MDP_EHIP, "hipRTC compilation of mdp_log failed: %s", log.c_str());
     hipModule_t mod = nullptr;
     hipFunction_t fn;
-    double *dx = nullptr, *dy = nullptr;
+    DevBuf<double> dx, dy;
     int rc = MDP_OK;
     auto fail = [&](hipError_t e, const char *what) {
         rc = mdp_set_error(MDP_EHIP, "%s failed: %s", what, hipGetErrorString(e));
@@ -3196,22 +3246,48 @@ int mdp_log_check(const double *x, double *y, size_t n)
     hipError_t e;
     if ((e = hipModuleLoadData(&mod, code.data())) != hipSuccess) fail(e, "hipModuleLoadData");
     else if ((e = hipModuleGetFunction(&fn, mod, "mdp_log_apply")) != hipSuccess) fail(e, "hipModuleGetFunction");
-    else if ((e = hipMalloc((void **)&dx, n * sizeof(double))) != hipSuccess) fail(e, "hipMalloc");
-    else if ((e = hipMalloc((void **)&dy, n * sizeof(double))) != hipSuccess) fail(e, "hipMalloc");
-    else if ((e = hipMemcpy(dx, x, n * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) fail(e, "hipMemcpy");
-    else {
+    else if (!(rc = dx.assign(x, n)) && !(rc = dy.grow(n))) {
         unsigned long long nn = n;
-        void *args[] = {(void *)&dx, (void *)&dy, (void *)&nn};
+        double *px = dx.get(), *py = dy.get();
+        void *args[] = {(void *)&px, (void *)&py, (void *)&nn};
         const uint32_t nb = (uint32_t)((n + kBlock - 1) / kBlock);
         if ((e = hipModuleLaunchKernel(fn, nb, 1, 1, kBlock, 1, 1, 0, nullptr, args, nullptr)) != hipSuccess)
             fail(e, "hipModuleLaunchKernel");
-        else if ((e = hipMemcpy(y, dy, n * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) fail(e, "hipMemcpy");
+        else if ((e = hipMemcpy(y, py, n * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) fail(e, "hipMemcpy");
     }
-    (void)hipFree(dx);
-    (void)hipFree(dy);
+    dx.reset(), dy.reset();  // (as before: the buffers, then the module)
     if (mod) (void)hipModuleUnload(mod);
     return rc;
 }
+
+int mdp_engine_get_info(const mdp_engine *eng, mdp_engine_info *info)
+{
+    if (!eng || !info) return mdp_set_error(MDP_EINVAL, "null argument");
+    mdp_plan_info(eng, (int)eng->devs.size(), info);
+    return MDP_OK;
+}
+
+int mdp_engine_work(const mdp_engine *eng, uint64_t ne, uint64_t nc, double *flop_impl, double *flop_survey,
+                    double *bytes_min)
+{
+    if (!eng) return mdp_set_error(MDP_EINVAL, "null engine");
+    mdp_plan_work(eng, ne, nc, flop_impl, flop_survey, bytes_min);
+    return MDP_OK;
+}
+
+int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_work *w)
+{
+    if (!eng || !w) return mdp_set_error(MDP_EINVAL, "null argument");
+    double ns = 0.0, nall = 0.0;
+    for (const DevCtx &d : eng->devs) {
+        ns += d.plan.ne_sform;
+        nall += d.ne;
+    }
+    mdp_plan_work_fact(eng, ne, nc, eng->devs.empty() ? -1.0 : eng->devs[0].ct.cmax, ns, nall, w);
+    return MDP_OK;
+}
+
+unsigned long long mdp_dev_live_bytes(void) { return g_dev_live_bytes.load(std::memory_order_relaxed); }
 
 int mdp_engine_launched(const mdp_engine *eng, char *buf, size_t len)
 {

@@ -701,33 +701,28 @@ __global__ __launch_bounds__(256) void k_future_split(const unsigned long long *
 }
 
 }  // namespace
-struct mdp_future {
-    int device = 0;
+// (DevQueue: the device, stream and events, released after the buffers below)
+struct mdp_future : DevQueue {
     uint32_t n = 0, nm = 0, nmiss = 0, necstep = 0, lvalid = 0;
     uint64_t occ0 = 0;
     double K = 1.0, pscale = 0.0;
-    double *dMK = nullptr, *dsrc = nullptr, *dpcum = nullptr, *dT = nullptr;
-    uint64_t *dmiss = nullptr;
-    uint32_t *dpartial = nullptr, *derr = nullptr;
-    size_t partial_cap = 0;
-    unsigned long long *dcounts = nullptr;
-    size_t counts_cap = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevBuf<double> dMK, dsrc, dpcum, dT;
+    DevBuf<uint64_t> dmiss;
+    DevBuf<uint32_t> dpartial, derr;
+    DevBuf<unsigned long long> dcounts;
     // k_future_wide<np> (np > 0): its tables instead of dMK / dmiss / dT
     uint32_t np = 0, wlen = 0, ks0 = 0;
-    double *dimage = nullptr;
-    uint32_t *docc0 = nullptr, *dwmiss = nullptr, *dstates = nullptr;
-    size_t states_cap = 0;
+    DevBuf<double> dimage;
+    DevBuf<uint32_t> docc0, dwmiss, dstates;  // dstates: 64 lane words a replicate
     char kname[32] = "";
     // the summary path: its window cap (MDP_FUT_SUM_YEARS), the global table
-    // [tfut][2n+1] and the records of a launch's replicates
+    // [tfut][2n+1] and the records of a launch's replicates (drec_occ: one
+    // 64-bit word a replicate, or k_future_wide_tab's 64 lane words = 32)
     uint32_t sum_years = 0;
-    unsigned long long *dtab = nullptr;
-    size_t tab_cap = 0;
-    void *drec_occ = nullptr;
-    uint32_t *drec_idx = nullptr;
-    size_t rec_occ_cap = 0, rec_idx_cap = 0;
+    DevBuf<unsigned long long> dtab;
+    DevBuf<uint64_t> drec_occ;
+    DevBuf<uint32_t> drec_idx;
+    ~mdp_future() { drain(); }
 };
 
 namespace {
@@ -780,8 +775,8 @@ int fut_grid(const mdp_future *f, uint64_t nrep)
 
 int fut_reserve(mdp_future *f, int nwg, uint32_t tfut)
 {
-    if (int rc = dev_grow(f->dpartial, f->partial_cap, (size_t)nwg * tfut, sizeof(uint32_t))) return rc;
-    return dev_grow(f->dcounts, f->counts_cap, tfut, sizeof(unsigned long long));
+    if (int rc = f->dpartial.grow((size_t)nwg * tfut)) return rc;
+    return f->dcounts.grow(tfut);
 }
 
 FutArgs fut_args(const mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut)
@@ -835,8 +830,8 @@ int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, 
     const int nwg = fut_grid(f, nrep);
     const size_t lds = fut_wide_lds(f, tfut);
     if (int rc = fut_for_np(f->np, [&](auto NP) {
-            hipLaunchKernelGGL(k_future_wide<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage,
-                               f->dsrc, f->dpcum, f->docc0, f->dwmiss, f->dpartial, d_states, derr);
+            hipLaunchKernelGGL(k_future_wide<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage.get(),
+                               f->dsrc.get(), f->dpcum.get(), f->docc0.get(), f->dwmiss.get(), f->dpartial.get(), d_states, derr);
             return MDP_OK;
         }))
         return rc;
@@ -855,15 +850,15 @@ int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint3
         const FutArgs a = fut_args(f, seed, rep0, nrep, tfut);
         const size_t lds = (size_t)tfut * sizeof(uint32_t) + (f->nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0);
         if (int rc = fut_for_nm(f->nm, [&](auto NM) {
-                hipLaunchKernelGGL(k_future<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dMK,
-                                   f->dsrc, f->dpcum, f->dmiss, f->dT, f->dpartial, derr);
+                hipLaunchKernelGGL(k_future<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dMK.get(),
+                                   f->dsrc.get(), f->dpcum.get(), f->dmiss.get(), f->dT.get(), f->dpartial.get(), derr);
                 return MDP_OK;
             }))
             return rc;
         HIP_TRY(hipGetLastError());
     }
     if (sum) {
-        hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial, (uint32_t)nwg, tfut, d_counts);
+        hipLaunchKernelGGL(k_future_sum, dim3(tfut), dim3(256), 0, st, f->dpartial.get(), (uint32_t)nwg, tfut, d_counts);
         HIP_TRY(hipGetLastError());
     }
     return MDP_OK;
@@ -878,14 +873,14 @@ int fut_check_args(mdp_future *f, uint64_t nrep, uint32_t tfut)
     return MDP_OK;
 }
 
-// the whole summary of replicates [rep0, rep0 + nrep) into f->dtab on st:
+// the whole summary of replicates [rep0, rep0 + nrep) into f->dtab.get() on st:
 // the table zeroed, then for every range of p.reps replicates one launch per
 // window of years
 int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
                     hipStream_t st, uint32_t *derr)
 {
     const size_t ncell = (size_t)tfut * (2 * f->n + 1);
-    HIP_TRY(hipMemsetAsync(f->dtab, 0, ncell * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(f->dtab.get(), 0, ncell * sizeof(unsigned long long), st));
     const uint64_t per = fut_per_wg(f);
     const size_t lds = (size_t)p.lds;
     for (uint64_t done = 0; done < nrep; done += p.reps) {
@@ -902,16 +897,16 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
                 const FutWideArgs a = fut_wide_args(f, seed, rep0 + done, cnt, tfut);
                 rc = fut_for_np(f->np, [&](auto NP) {
                     hipLaunchKernelGGL(k_future_wide_tab<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a,
-                                       w, f->dimage, f->dsrc, f->dpcum, f->docc0, f->dwmiss,
-                                       (uint32_t *)f->drec_occ, f->drec_idx, f->dtab, derr);
+                                       w, f->dimage.get(), f->dsrc.get(), f->dpcum.get(), f->docc0.get(), f->dwmiss.get(),
+                                       (uint32_t *)f->drec_occ.get(), f->drec_idx.get(), f->dtab.get(), derr);
                     return MDP_OK;
                 });
             } else {
                 const FutArgs a = fut_args(f, seed, rep0 + done, cnt, tfut);
                 rc = fut_for_nm(f->nm, [&](auto NM) {
                     hipLaunchKernelGGL(k_future_tab<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, w,
-                                       f->dMK, f->dsrc, f->dpcum, f->dmiss, f->dT, (uint64_t *)f->drec_occ,
-                                       f->drec_idx, f->dtab, derr);
+                                       f->dMK.get(), f->dsrc.get(), f->dpcum.get(), f->dmiss.get(), f->dT.get(), (uint64_t *)f->drec_occ.get(),
+                                       f->drec_idx.get(), f->dtab.get(), derr);
                     return MDP_OK;
                 });
             }
@@ -930,11 +925,10 @@ int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan 
     if (nrep > (1ull << 62)) return mdp_set_error(MDP_EINVAL, "replicate count too large");
     if (int rc = fut_sum_plan(f->n, f->np, f->wlen, tfut, f->sum_years, p)) return rc;
     HIP_TRY(hipSetDevice(f->device));
-    if (int rc = dev_grow(f->dtab, f->tab_cap, (size_t)tfut * (2 * f->n + 1), sizeof(unsigned long long))) return rc;
+    if (int rc = f->dtab.grow((size_t)tfut * (2 * f->n + 1))) return rc;
     const size_t recs = p->windows > 1 ? (size_t)std::min<uint64_t>(nrep, p->reps) : 0;
-    if (int rc = dev_grow(f->drec_occ, f->rec_occ_cap, recs, f->np ? 64 * sizeof(uint32_t) : sizeof(uint64_t)))
-        return rc;
-    return dev_grow(f->drec_idx, f->rec_idx_cap, recs, sizeof(uint32_t));
+    if (int rc = f->drec_occ.grow(recs * (f->np ? 32 : 1))) return rc;
+    return f->drec_idx.grow(recs);
 }
 
 // the mean time in ms of `reps` runs of launch() on f->stream, after one
@@ -962,10 +956,10 @@ int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp
     const int device = f->device;
     if (hipSetDevice(device) != hipSuccess) return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
     int rc;
-    if ((rc = dev_upload(f->dpcum, pp.pcum))) return rc;
+    if ((rc = f->dpcum.assign(pp.pcum))) return rc;
     if (f->np) {
-        if ((rc = dev_upload(f->dimage, wp.image)) || (rc = dev_upload(f->dsrc, wp.src)) ||
-            (rc = dev_upload(f->docc0, wp.occ0)) || (rc = dev_upload(f->dwmiss, wp.miss)))
+        if ((rc = f->dimage.assign(wp.image)) || (rc = f->dsrc.assign(wp.src)) ||
+            (rc = f->docc0.assign(wp.occ0)) || (rc = f->dwmiss.assign(wp.miss)))
             return rc;
         // the image and kFutMaxT year counters pass 64 KB of dynamic LDS; the
         // summary kernel: the image and one window's table
@@ -982,21 +976,20 @@ int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp
                 return mdp_set_error(MDP_EHIP, "%s: %zu bytes of LDS refused on device %d%s", f->kname, lds[i], device,
                                      i ? " (summary)" : "");
     } else {
-        if ((rc = dev_upload(f->dMK, lp.MK)) || (rc = dev_upload(f->dsrc, lp.src)) || (rc = dev_upload(f->dmiss, lp.miss)))
+        if ((rc = f->dMK.assign(lp.MK)) || (rc = f->dsrc.assign(lp.src)) || (rc = f->dmiss.assign(lp.miss)))
             return rc;
         if (f->nm == kTabN) {
-            if (hipMalloc((void **)&f->dT, sizeof(double) * (kTabN << kTabN)) != hipSuccess)
-                return mdp_set_error(MDP_EHIP, "device allocation failed on device %d", device);
-            hipLaunchKernelGGL(k_future_table, dim3((kTabN << kTabN) / 256), dim3(256), 0, nullptr, f->dMK, f->dsrc,
-                               f->n, f->dT);
+            if ((rc = f->dT.grow((size_t)kTabN << kTabN))) return rc;
+            hipLaunchKernelGGL(k_future_table, dim3((kTabN << kTabN) / 256), dim3(256), 0, nullptr, f->dMK.get(), f->dsrc.get(),
+                               f->n, f->dT.get());
             if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
                 return mdp_set_error(MDP_EHIP, "colonisation table kernel failed on device %d", device);
         }
     }
     // look-back overflow flags: [0] the device path (read and cleared by
     // mdp_future_check), [1] the host-returning calls (their own)
-    if (hipMalloc((void **)&f->derr, 2 * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(f->derr, 0, 2 * sizeof(uint32_t)) != hipSuccess ||
+    if ((rc = f->derr.grow(2))) return rc;
+    if (hipMemset(f->derr.get(), 0, 2 * sizeof(uint32_t)) != hipSuccess ||
         hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&f->ev0) != hipSuccess || hipEventCreate(&f->ev1) != hipSuccess)
         return mdp_set_error(MDP_EHIP, "device setup failed on device %d", device);
@@ -1029,7 +1022,7 @@ static int fut_create(const int32_t *last_row, uint32_t n, const double *post, u
         return rc;
     if (int rc = fut_post_plan(post, necstep, &pp)) return rc;
     // from here the engine owns what it holds: destroyed on every exit but the last
-    std::unique_ptr<mdp_future, void (*)(mdp_future *)> f(new (std::nothrow) mdp_future(), mdp_future_destroy);
+    std::unique_ptr<mdp_future> f(new (std::nothrow) mdp_future());
     if (!f) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     f->device = device;
     f->n = n;
@@ -1089,14 +1082,14 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
     HIP_TRY(hipSetDevice(f->device));
     int rc;
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
-    if ((rc = dev_grow(f->dstates, f->states_cap, (size_t)nrep, 64 * sizeof(uint32_t)))) return rc;
-    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
-    if ((rc = fut_launch_wide(f, seed, rep0, nrep, tfut, f->stream, f->dstates, f->derr + 1))) return rc;
+    if ((rc = f->dstates.grow((size_t)nrep * 64))) return rc;
+    HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = fut_launch_wide(f, seed, rep0, nrep, tfut, f->stream, f->dstates.get(), f->derr.get() + 1))) return rc;
     std::vector<uint32_t> lanes((size_t)nrep * 64);
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(lanes.data(), f->dstates, lanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(lanes.data(), f->dstates.get(), lanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            f->stream));
-    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr.get() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     fut_wide_unpack(lanes.data(), nrep, f->n, f->np, words);
@@ -1105,28 +1098,7 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
 
 void mdp_future_destroy(mdp_future *f)
 {
-    if (!f) return;
-    (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    (void)hipFree(f->dMK);
-    (void)hipFree(f->dsrc);
-    (void)hipFree(f->dpcum);
-    (void)hipFree(f->dT);
-    (void)hipFree(f->dmiss);
-    (void)hipFree(f->dpartial);
-    (void)hipFree(f->derr);
-    (void)hipFree(f->dcounts);
-    (void)hipFree(f->dimage);
-    (void)hipFree(f->docc0);
-    (void)hipFree(f->dwmiss);
-    (void)hipFree(f->dstates);
-    (void)hipFree(f->dtab);
-    (void)hipFree(f->drec_occ);
-    (void)hipFree(f->drec_idx);
-    if (f->ev0) (void)hipEventDestroy(f->ev0);
-    if (f->ev1) (void)hipEventDestroy(f->ev1);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
+    delete f;  // (its destructor releases the device side)
 }
 
 int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
@@ -1140,7 +1112,7 @@ int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     // the look-back overflow flag is sticky: mdp_future_check reads and
     // clears it, so one check covers every launch since the previous check
-    return fut_launch(f, seed, rep0, nrep, tfut, (unsigned long long *)d_counts, st, true, f->derr);
+    return fut_launch(f, seed, rep0, nrep, tfut, (unsigned long long *)d_counts, st, true, f->derr.get());
 }
 
 int mdp_future_check(mdp_future *f, void *stream)
@@ -1149,8 +1121,8 @@ int mdp_future_check(mdp_future *f, void *stream)
     HIP_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(&err, f->derr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemsetAsync(f->derr, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemsetAsync(f->derr.get(), 0, sizeof(uint32_t), st));
     HIP_TRY(hipStreamSynchronize(st));
     return fut_lookback(err, true);
 }
@@ -1164,12 +1136,12 @@ int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nr
     HIP_TRY(hipSetDevice(f->device));
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if (nrep == 0) return MDP_OK;
-    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
-    if ((rc = fut_launch(f, seed, rep0, nrep, tfut, f->dcounts, f->stream, true, f->derr + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = fut_launch(f, seed, rep0, nrep, tfut, f->dcounts.get(), f->stream, true, f->derr.get() + 1))) return rc;
     std::vector<unsigned long long> h(tfut);
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(h.data(), f->dcounts, tfut * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), f->dcounts.get(), tfut * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr.get() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) counts[t] += h[t];
@@ -1184,7 +1156,7 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     HIP_TRY(hipSetDevice(f->device));
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     return fut_time(f, reps, ms, [&]() {
-        return fut_launch(f, seed, 0, nrep, tfut, f->dcounts, f->stream, false, f->derr + 1);
+        return fut_launch(f, seed, 0, nrep, tfut, f->dcounts.get(), f->stream, false, f->derr.get() + 1);
     });
 }
 
@@ -1197,9 +1169,9 @@ int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint6
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
     // the sticky look-back flag of the device path (mdp_future_check)
-    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, st, f->derr))) return rc;
+    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, st, f->derr.get()))) return rc;
     const uint32_t ncell = tfut * (2 * f->n + 1);
-    hipLaunchKernelGGL(k_future_split, dim3((ncell + 255) / 256), dim3(256), 0, st, f->dtab, ncell, f->n,
+    hipLaunchKernelGGL(k_future_split, dim3((ncell + 255) / 256), dim3(256), 0, st, f->dtab.get(), ncell, f->n,
                        (unsigned long long *)d_hist, (unsigned long long *)d_occ);
     HIP_TRY(hipGetLastError());
     return MDP_OK;
@@ -1213,13 +1185,13 @@ int mdp_future_summary(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nre
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (nrep == 0) return MDP_OK;
-    HIP_TRY(hipMemsetAsync(f->derr + 1, 0, sizeof(uint32_t), f->stream));
-    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, f->stream, f->derr + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
+    if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, f->stream, f->derr.get() + 1))) return rc;
     const uint32_t n = f->n, cells = 2 * n + 1;
     std::vector<unsigned long long> h((size_t)tfut * cells);
     uint32_t err = 0;
-    HIP_TRY(hipMemcpyAsync(h.data(), f->dtab, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    HIP_TRY(hipMemcpyAsync(&err, f->derr + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), f->dtab.get(), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipMemcpyAsync(&err, f->derr.get() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(hipStreamSynchronize(f->stream));
     if ((rc = fut_lookback(err, false))) return rc;
     for (uint32_t t = 0; t < tfut; ++t) {
@@ -1236,7 +1208,7 @@ int mdp_future_time_summary(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
-    return fut_time(f, reps, ms, [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr + 1); });
+    return fut_time(f, reps, ms, [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr.get() + 1); });
 }
 
 int mdp_future_philox(uint64_t key, const uint32_t *ctr, uint32_t *out)

@@ -75,7 +75,7 @@ constexpr size_t kJitChunkQ = kJitMaxLds / sizeof(double) - 2;  // gathered coef
 
 constexpr int kDegBuckets[] = {4, 8, 16, 24};
 
-int select_variant(mdp_engine *eng)
+int select_variant(MdpEnginePlan *eng)
 {
     uint32_t np = 0;
     for (uint32_t b : {1u, 2u, 4u, 8u, 16u})
@@ -95,7 +95,7 @@ int select_variant(mdp_engine *eng)
 // Host plan: distinct transition pairs (sorted by |A&B| descending for load
 // balance in k_coefs), Q offsets, the per-use pair index in forward order, and
 // the step program (runs of 1x1 transitions / general years).
-int build_plan(mdp_engine *eng, const mdp_problem *p)
+int build_plan(MdpEnginePlan *eng, const mdp_problem *p)
 {
     eng->n = p->n;
     eng->tmax = p->tmax;
@@ -220,7 +220,7 @@ int build_plan(mdp_engine *eng, const mdp_problem *p)
 // share Q; each (X, B) group needs Pc[j][B] for every j <= X.  Items are the
 // distinct (j, B), numbered by j ascending then B ascending; qstart / qitem
 // list, for every Q entry (group, m), its items with |j| = m in ascending j.
-int build_direct_plan(mdp_engine *eng, const mdp_problem *p)
+int build_direct_plan(MdpEnginePlan *eng, const mdp_problem *p)
 {
     std::map<uint64_t, uint32_t> group;  // (X, B) -> Q offset
     std::vector<std::pair<uint32_t, uint32_t>> groups;
@@ -554,7 +554,7 @@ void plan_waves(const std::vector<uint32_t> &nch, uint32_t tmaxit, uint32_t inpl
 //    smaller years give every tile a wave and the spare waves to the tiles
 //    with the longest lists, each tile's list split into as many slices
 //    (at least two chunks each).
-void build_mmt_plan(mdp_engine *eng)
+void build_mmt_plan(MdpEnginePlan *eng)
 {
     if (eng->npmax > 1024 || eng->maxA > 24 || eng->tmax < 2) return;
     const MmtShape shp = mmt_shape(eng);
@@ -632,7 +632,7 @@ void build_mmt_plan(mdp_engine *eng)
 //    park blocks (no state of the year in them), the wave plan.
 // Year 0's positions head dpos.  Refused (hs = false: k_fwd_mmt runs) for a
 // year with a repeated state or an item the direct plan lacks.
-void build_hs_plan(mdp_engine *eng)
+void build_hs_plan(MdpEnginePlan *eng)
 {
     eng->hs = false;
     if (eng->nvar > 10 || eng->tmax < 2 || eng->npmax > 1024 || eng->ystate.size() < eng->tmax) return;
@@ -916,7 +916,7 @@ void build_hs_plan(mdp_engine *eng)
 // plus the FP64 work per grid point of k_fwd_wide (every use a (nX+1)-term
 // dot product with a weight multiply per term, one FMA into the state
 // vector; the per-lane power tables; the final prior sum).
-int build_wide_plan(mdp_engine *eng, const mdp_problem *p)
+int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p)
 {
     int rc = build_direct_plan(eng, p);
     if (rc) return rc;
@@ -1021,7 +1021,7 @@ int build_wide_plan(mdp_engine *eng, const mdp_problem *p)
 // in the last quarter of a chunk.  With `gather`, each chunk stages only the
 // Q groups its uses read (at most kJitChunkQ doubles, a chunk-local layout of
 // even-aligned groups) instead of the whole Q row.
-int plan_chunks(mdp_engine *eng, uint32_t U, bool gather, size_t qlimit)
+int plan_chunks(MdpEnginePlan *eng, uint32_t U, bool gather, size_t qlimit)
 {
     const MdpJitPlan &base = eng->jit_plan;
     const std::vector<uint32_t> &np = eng->np;
@@ -1110,7 +1110,7 @@ int plan_chunks(mdp_engine *eng, uint32_t U, bool gather, size_t qlimit)
 // coefficients P_i / i (zero for a row without small columns: exp(0) = 1).
 constexpr double kZTau = 0x1p-7;
 
-void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
+void z_split(const MdpEnginePlan *eng, uint32_t js, double cmax, std::vector<double> &large, double *coef,
              std::vector<uint32_t> *cols)
 {
     const uint32_t n = eng->n;
@@ -1138,7 +1138,7 @@ void z_split(const mdp_engine *eng, uint32_t js, double cmax, std::vector<double
         for (int i = 0; i < kZTerms; ++i) coef[i] = pw[i] / (double)(i + 1);
 }
 
-void mdp_plan_item_tables(const mdp_engine *eng, std::vector<double> &sv, std::vector<uint2> &items)
+void mdp_plan_item_tables(const MdpEnginePlan *eng, std::vector<double> &sv, std::vector<uint2> &items)
 {
     sv.assign((size_t)eng->nj * eng->nvar + 1, 0.0);
     for (uint32_t js = 0; js < eng->nj; ++js)
@@ -1157,13 +1157,13 @@ namespace {
 
 // no fused kernel on the wide path, for a chunked series, Q rows built in HBM
 // or state vectors in LDS
-bool fused_path(const mdp_engine *eng)
+bool fused_path(const MdpEnginePlan *eng)
 {
     return eng->jit && !eng->wide && !eng->qglobal && eng->chunks.empty() && !eng->jit_plan.vlds;
 }
 
 // The c tables for the bound cmax.
-void plan_ctables(const mdp_engine *eng, double cmax, MdpCTables &t)
+void plan_ctables(const MdpEnginePlan *eng, double cmax, MdpCTables &t)
 {
     const uint32_t nj = eng->nj;
     std::vector<std::vector<double>> rows(nj);
@@ -1244,12 +1244,12 @@ uint32_t wide_cb(size_t most, size_t fit, int forced)
 
 }  // namespace
 
-bool mdp_plan_fused_capable(const mdp_engine *eng)
+bool mdp_plan_fused_capable(const MdpEnginePlan *eng)
 {
     return fused_path(eng) && fused_lds(eng, eng->jit_plan.ct_max) <= kFusedLdsMax;
 }
 
-int mdp_plan_grid(const mdp_engine *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
+int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uint32_t ne, const double *c, uint32_t nc,
                   uint32_t ncu, MdpGridPlan &g)
 {
     // c < 0 is refused: the item factors are folded as |n_b - pC_b| (k_qrows
@@ -1360,7 +1360,7 @@ int mdp_plan_grid(const mdp_engine *eng, MdpCTables &ct, const double *e, uint32
     return MDP_OK;
 }
 
-void mdp_plan_fwd_launch(const mdp_engine *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g)
+void mdp_plan_fwd_launch(const MdpEnginePlan *eng, const MdpCTables &ct, uint32_t ne, uint32_t nc, MdpGridPlan &g)
 {
     // threads per e block: kb (x spl with the split state-vector kernel)
     const uint32_t kb = g.fused ? eng->jit_kblock_fused : g.tall ? (uint32_t)kJitKblockTall : eng->jit_kblock;
@@ -1380,7 +1380,7 @@ void mdp_plan_fwd_launch(const mdp_engine *eng, const MdpCTables &ct, uint32_t n
     g.fwd_lds = g.fused ? (ct.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
 }
 
-bool mdp_plan_slot_active(const mdp_engine *eng, const MdpGridPlan &g, int k)
+bool mdp_plan_slot_active(const MdpEnginePlan *eng, const MdpGridPlan &g, int k)
 {
     if (eng->wide || (eng->jit && eng->qglobal)) return k == 2 || eng->nitems;
     // the direct path computes its Z rows inside k_qrows (slot 0 idle); the
@@ -1389,7 +1389,7 @@ bool mdp_plan_slot_active(const mdp_engine *eng, const MdpGridPlan &g, int k)
     return k != 1 || eng->nuses;
 }
 
-std::vector<std::string> mdp_plan_grid_kernels(const mdp_engine *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc)
+std::vector<std::string> mdp_plan_grid_kernels(const MdpEnginePlan *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc)
 {
     std::set<std::string> names;
     auto note = [&](const char *fmt, auto... a) {
@@ -1434,7 +1434,7 @@ std::vector<std::string> mdp_plan_grid_kernels(const mdp_engine *eng, const MdpG
 // reading at kJitKblockTall threads (a column of a tall grid in half the
 // blocks: its Q row staged half as often).  Sets the engine's launch shape of
 // the variant.
-std::string jit_source(mdp_engine *eng, int variant)
+std::string jit_source(MdpEnginePlan *eng, int variant)
 {
     const bool fused = variant == 1;
     MdpJitPlan plan = eng->jit_plan;
@@ -1483,7 +1483,7 @@ std::string jit_source(mdp_engine *eng, int variant)
 }
 
 // Compile (hipRTC, cached) that kernel.
-int jit_build(mdp_engine *eng, int variant)
+int jit_build(MdpEnginePlan *eng, int variant)
 {
     if (!eng->jit_code[variant].empty()) return MDP_OK;
     const std::string src = jit_source(eng, variant);
@@ -1496,7 +1496,7 @@ int jit_build(mdp_engine *eng, int variant)
 
 // Compile every chunk kernel of a long series (threads: hipRTC programs are
 // independent).
-int jit_build_chunks(mdp_engine *eng)
+int jit_build_chunks(MdpEnginePlan *eng)
 {
     const size_t nch = eng->chunks.size();
     if (eng->chunk_code.size() == nch) return MDP_OK;
@@ -1547,7 +1547,7 @@ int jit_build_chunks(mdp_engine *eng)
 // The planning half of mdp_engine_create_opts (declared in spom_engine.h).  On
 // an error, and after an offline check (MDP_ENODEV with the counts in the
 // message), the caller deletes the engine.
-int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t)
+int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t)
 {
     const bool offline_check = mode == MdpPlanMode::OfflineCheck;
     auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1726,24 +1726,22 @@ int mdp_plan_engine(mdp_engine *eng, const mdp_problem *p, size_t lds_max, MdpPl
     return MDP_OK;
 }
 
-extern "C" {
-
-int mdp_engine_get_info(const mdp_engine *eng, mdp_engine_info *info)
+// The arithmetic of mdp_engine_get_info, mdp_engine_work and
+// mdp_engine_work_fact (the ABI wrappers, spom_engine.hip, pass what they
+// take from the device contexts).
+void mdp_plan_info(const MdpEnginePlan *eng, int n_devices, mdp_engine_info *info)
 {
-    if (!eng || !info) return mdp_set_error(MDP_EINVAL, "null argument");
-    info->n_devices = (int)eng->devs.size();
+    info->n_devices = n_devices;
     info->npairs = eng->npairs;
     info->nuses = eng->nuses;
     info->ncoef = eng->ncoef;
     info->npmax = eng->npmax;
     info->variant = eng->variant + (eng->jit ? 10000u : 0u);
-    return MDP_OK;
 }
 
-int mdp_engine_work(const mdp_engine *eng, uint64_t ne, uint64_t nc, double *flop_impl,
-                    double *flop_survey, double *bytes_min)
+void mdp_plan_work(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double *flop_impl, double *flop_survey,
+                   double *bytes_min)
 {
-    if (!eng) return mdp_set_error(MDP_EINVAL, "null engine");
     const double pts = (double)ne * (double)nc;
     // k_forward per point: every use is a (D+1)-term dot product (2(D+1)
     // flops) and one multiply-add into the state vector (2), plus the
@@ -1764,17 +1762,16 @@ int mdp_engine_work(const mdp_engine *eng, uint64_t ne, uint64_t nc, double *flo
     // e values, the output
     if (bytes_min)
         *bytes_min = 8.0 * ((double)nc * (eng->jit || eng->wide ? eng->ldQ : ldR_of(eng)) + (double)ne + pts);
-    return MDP_OK;
 }
 
-
-int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_work *w)
+// cmax: the bound the device's c tables hold for (< 0: none yet); ns of nall:
+// the current grid's e rows on the s-form, over the devices
+void mdp_plan_work_fact(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double cmax, double ns, double nall,
+                        mdp_work *w)
 {
-    if (!eng || !w) return mdp_set_error(MDP_EINVAL, "null argument");
     *w = mdp_work{};
     // per c value (the direct plan's tables; zero on the generic path, which
     // has none): Z rows, var-column pressures, item factors, Q sums
-    double cmax = eng->devs.empty() ? 1.0 : eng->devs[0].ct.cmax;
     if (!(cmax >= 0.0)) cmax = 1.0;  // no grid yet: the default [0, 1]
     std::vector<double> large;
     double coef[kZTerms];
@@ -1823,18 +1820,10 @@ int mdp_engine_work_fact(const mdp_engine *eng, uint64_t ne, uint64_t nc, mdp_wo
     pl.np = eng->np;
     pl.udesc = ud;
     const MdpRatioWork rw = mdp_jit_ratio_work(pl);
-    double ns = 0.0, nall = 0.0;
-    for (const DevCtx &d : eng->devs) {
-        ns += d.plan.ne_sform;
-        nall += d.ne;
-    }
     const double fs = nall > 0.0 ? ns / nall : 0.5;
     w->setup_pt = fs * rw.setup_s + (1.0 - fs) * rw.setup_t;
     w->use_pt_ratio = fs * rw.use_s + (1.0 - fs) * rw.use_t;
     w->final_pt_ratio = rw.final_pt;
     w->pt_min = w->setup_pt + w->use_pt_ratio + w->final_pt_ratio;
     w->flop_min = (double)nc * per_c + (double)ne * (double)nc * w->pt_min;
-    return MDP_OK;
 }
-
-}  // extern "C"

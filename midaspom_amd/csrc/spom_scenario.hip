@@ -693,17 +693,15 @@ ScnKernel scn_kernel(uint32_t n)
 
 // The host side: every decision is the planner's (spom_scenario_plan.cpp);
 // this unit owns the device copies of its tables and launches what it lists.
-struct mdp_scenario {
+// (DevQueue: the device, stream and events, released after the buffers below)
+struct mdp_scenario : DevQueue {
     ScnPlan plan;
     ScnGrid grid;  // set by mdp_scenario_set_grid
-    int device = 0;
-    double *dS = nullptr, *dw = nullptr;
-    uint32_t *dboff = nullptr, *djsched = nullptr, *djord = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevBuf<double> dS, dw;
+    DevBuf<uint32_t> dboff, djsched, djord;
     // grow-only buffers of the grid: the axes, the source rows, v, k_scn_big's state scratch
-    double *de = nullptr, *dc = nullptr, *dK = nullptr, *dsr = nullptr, *dV = nullptr, *dY = nullptr;
-    size_t e_cap = 0, c_cap = 0, K_cap = 0, sr_cap = 0, V_cap = 0, Y_cap = 0;
+    DevBuf<double> de, dc, dK, dsr, dV, dY;
+    ~mdp_scenario() { drain(); }
 };
 
 namespace {
@@ -716,17 +714,19 @@ int scn_launch(mdp_scenario *sc, double *dout, hipStream_t st, int which)
     for (int mode = 0; mode < 2; ++mode) {
         if (!(which & (1 << mode))) continue;
         ScnArgs a{p.n, p.ns, g.ne, g.nc, g.nK, g.nd, mode ? g.ts : g.tdis, p.kind, mode, p.nsched, p.btot};
-        const double *y0 = mode ? sc->dV : sc->dw;
-        double *o = mode ? dout : sc->dV;
+        const double *S = sc->dS.get(), *y0 = mode ? sc->dV.get() : sc->dw.get();
+        const double *de = sc->de.get(), *dc = sc->dc.get(), *dK = sc->dK.get(), *dsr = sc->dsr.get();
+        const uint32_t *boff = sc->dboff.get(), *jsched = sc->djsched.get();
+        double *o = mode ? dout : sc->dV.get();
         for (const ScnLaunch &l : g.launches[mode]) {
             if (p.path == kScnRow) {  // one workgroup per point
-                hipLaunchKernelGGL(k_scn_row, dim3(l.nwg), dim3(kRowBlock), p.lds, st, a, sc->dS, y0, sc->de, sc->dc,
-                                   sc->dK, sc->dsr, sc->djord, (size_t)l.p0, o);
+                hipLaunchKernelGGL(k_scn_row, dim3(l.nwg), dim3(kRowBlock), p.lds, st, a, S, y0, de, dc, dK, dsr,
+                                   sc->djord.get(), (size_t)l.p0, o);
             } else if (p.path == kScnBig) {
-                hipLaunchKernelGGL(k_scn_big, dim3(l.nwg), dim3(kBigBlock), 0, st, a, sc->dS, y0, sc->de, sc->dc,
-                                   sc->dK, sc->dsr, (size_t)l.p0, (uint32_t)l.pts, sc->dY, o);
+                hipLaunchKernelGGL(k_scn_big, dim3(l.nwg), dim3(kBigBlock), 0, st, a, S, y0, de, dc, dK, dsr,
+                                   (size_t)l.p0, (uint32_t)l.pts, sc->dY.get(), o);
             } else {
-                void *args[] = {&a, &sc->dS, &y0, &sc->de, &sc->dc, &sc->dK, &sc->dsr, &sc->dboff, &sc->djsched, &o};
+                void *args[] = {&a, &S, &y0, &de, &dc, &dK, &dsr, &boff, &jsched, &o};
                 HIP_TRY(hipLaunchKernel((const void *)scn_kernel(p.n), dim3(l.nwg), dim3(kScnBlock), args, p.lds, st));
             }
         }
@@ -753,16 +753,7 @@ int mdp_scenario_create(const int32_t *row, uint32_t n, double m, float p, doubl
 
 void mdp_scenario_destroy(mdp_scenario *sc)
 {
-    if (!sc) return;
-    (void)hipSetDevice(sc->device);
-    if (sc->stream) (void)hipStreamSynchronize(sc->stream);
-    for (void *p : {(void *)sc->dS, (void *)sc->dw, (void *)sc->dboff, (void *)sc->djsched, (void *)sc->djord,
-                    (void *)sc->de, (void *)sc->dc, (void *)sc->dK, (void *)sc->dsr, (void *)sc->dV, (void *)sc->dY})
-        if (p) (void)hipFree(p);
-    if (sc->ev0) (void)hipEventDestroy(sc->ev0);
-    if (sc->ev1) (void)hipEventDestroy(sc->ev1);
-    if (sc->stream) (void)hipStreamDestroy(sc->stream);
-    delete sc;
+    delete sc;  // (its destructor releases the device side)
 }
 
 // options (ABI 7): "MDP_SCN_BIG=1" / "MDP_SCN_ROW=1" force the HBM-state or
@@ -783,17 +774,14 @@ int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
     if (device < 0 || device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", device);
     HIP_TRY(hipSetDevice(device));
-    struct Del {
-        void operator()(mdp_scenario *s) const { mdp_scenario_destroy(s); }
-    };
-    std::unique_ptr<mdp_scenario, Del> sc(new (std::nothrow) mdp_scenario());
+    std::unique_ptr<mdp_scenario> sc(new (std::nothrow) mdp_scenario());
     if (!sc) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     sc->device = device;
     sc->plan = std::move(plan);
     const ScnPlan &pl = sc->plan;
     int rc;
-    if ((rc = dev_upload(sc->dS, pl.S)) || (rc = dev_upload(sc->dw, pl.w)) || (rc = dev_upload(sc->dboff, pl.boff)) ||
-        (rc = dev_upload(sc->djsched, pl.jsched)) || (rc = dev_upload(sc->djord, pl.jord)))
+    if ((rc = sc->dS.assign(pl.S)) || (rc = sc->dw.assign(pl.w)) || (rc = sc->dboff.assign(pl.boff)) ||
+        (rc = sc->djsched.assign(pl.jsched)) || (rc = sc->djord.assign(pl.jord)))
         return rc;
     HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
     if (pl.lds > 64 * 1024)
@@ -814,15 +802,9 @@ int mdp_scenario_set_grid(mdp_scenario *sc, int ts, int tdis, const double *e, u
     sc->grid = ScnGrid();  // no grid until this one is whole
     sc->grid.ts = ts, sc->grid.tdis = tdis;
     if (!g.ne) return MDP_OK;
-    auto put = [](double *&p, size_t &cap, const double *h, size_t count) -> int {
-        if (int rc = dev_grow(p, cap, count)) return rc;
-        if (count) HIP_TRY(hipMemcpy(p, h, count * sizeof(double), hipMemcpyHostToDevice));
-        return MDP_OK;
-    };
     int rc;
-    if ((rc = put(sc->de, sc->e_cap, e, g.ne)) || (rc = put(sc->dc, sc->c_cap, c, g.nc)) ||
-        (rc = put(sc->dK, sc->K_cap, K, g.nK)) || (rc = put(sc->dsr, sc->sr_cap, g.src.data(), g.src.size())) ||
-        (rc = dev_grow(sc->dV, sc->V_cap, g.nV)) || (g.nY && (rc = dev_grow(sc->dY, sc->Y_cap, g.nY))))
+    if ((rc = sc->de.assign(e, g.ne)) || (rc = sc->dc.assign(c, g.nc)) || (rc = sc->dK.assign(K, g.nK)) ||
+        (rc = sc->dsr.assign(g.src)) || (rc = sc->dV.grow(g.nV)) || (g.nY && (rc = sc->dY.grow(g.nY))))
         return rc;
     sc->grid = std::move(g);
     return MDP_OK;
@@ -868,14 +850,12 @@ int mdp_scenario_lik(mdp_scenario *sc, int ts, int tdis, const double *e, uint32
     if (rc || !sc->grid.ne) return rc;
     const ScnGrid &g = sc->grid;
     const size_t npts = (size_t)g.ne * g.nc * g.nK * g.nd;
-    double *dout = nullptr;
-    if (hipMalloc((void **)&dout, npts * sizeof(double)) != hipSuccess)
-        return mdp_set_error(MDP_ENOMEM, "device allocation failed");
-    rc = scn_launch(sc, dout, sc->stream, 3);
-    if (!rc && (hipMemcpyAsync(out, dout, npts * sizeof(double), hipMemcpyDeviceToHost, sc->stream) != hipSuccess ||
+    DevBuf<double> dout;
+    if ((rc = dout.grow(npts))) return rc;
+    rc = scn_launch(sc, dout.get(), sc->stream, 3);
+    if (!rc && (hipMemcpyAsync(out, dout.get(), npts * sizeof(double), hipMemcpyDeviceToHost, sc->stream) != hipSuccess ||
                 hipStreamSynchronize(sc->stream) != hipSuccess))
         rc = mdp_set_error(MDP_EHIP, "scenario run failed");
-    (void)hipFree(dout);
     return rc;
 }
 

@@ -212,18 +212,19 @@ __global__ __launch_bounds__(kSimBlock) void k_scnsim(SimArgs a, const double *_
 
 }  // namespace
 
-struct mdp_scenario_sim {
+// (DevQueue: the device, stream and events, released after the buffers below)
+struct mdp_scenario_sim : DevQueue {
     SimPlan plan;
-    int device = 0;
     bool ready = false;  // the device side exists (set up by the first call that needs it)
     bool touched = false;  // a device call was made for this engine
     char kname[32] = "";
-    double *dM = nullptr, *dgrid = nullptr;
-    uint32_t *dmiss = nullptr;
-    unsigned long long *dhist = nullptr, *dmatch = nullptr;
-    size_t grid_cap = 0, hist_cap = 0, match_cap = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevBuf<double> dM, dgrid;
+    DevBuf<uint32_t> dmiss;
+    DevBuf<unsigned long long> dhist, dmatch;
+    ~mdp_scenario_sim()
+    {
+        if (touched) drain();  // (else nothing below exists: no HIP call)
+    }
 };
 
 namespace {
@@ -253,10 +254,10 @@ int sim_device(mdp_scenario_sim *s)
     if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
     HIP_TRY(hipSetDevice(s->device));
     s->touched = true;
-    if (!s->dM)
-        if (int rc = dev_upload(s->dM, s->plan.M)) return rc;
-    if (!s->dmiss)
-        if (int rc = dev_upload(s->dmiss, s->plan.miss)) return rc;
+    if (s->dM.empty())
+        if (int rc = s->dM.assign(s->plan.M)) return rc;
+    if (s->dmiss.empty())
+        if (int rc = s->dmiss.assign(s->plan.miss)) return rc;
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
     if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
@@ -283,9 +284,7 @@ int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
     h.insert(h.end(), gr.K, gr.K + gr.nK);
     h.insert(h.end(), src.begin(), src.end());
     HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = dev_grow(s->dgrid, s->grid_cap, h.size())) return rc;
-    HIP_TRY(hipMemcpy(s->dgrid, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    return MDP_OK;
+    return s->dgrid.assign(h);
 }
 
 // every launch of a call on st; the tables accumulate
@@ -293,7 +292,7 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
                uint64_t nrep, unsigned long long *d_hist, unsigned long long *d_match, hipStream_t st)
 {
     const SimPlan &p = s->plan;
-    const double *de = s->dgrid, *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = dK + gr.nK;
+    const double *de = s->dgrid.get(), *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = dK + gr.nK;
     const size_t lds = p.nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0;
     for (const SimLaunch &l : call.launches) {
         SimArgs a{};
@@ -316,8 +315,8 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
         a.fixed = p.fixed;
         a.missmask = p.missmask;
         if (int rc = sim_for_nm(p.nm, [&](auto NM) {
-                hipLaunchKernelGGL(k_scnsim<decltype(NM)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a, s->dM, dsrc,
-                                   de, dc, dK, s->dmiss, d_hist, d_match);
+                hipLaunchKernelGGL(k_scnsim<decltype(NM)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a, s->dM.get(), dsrc,
+                                   de, dc, dK, s->dmiss.get(), d_hist, d_match);
                 return MDP_OK;
             }))
             return rc;
@@ -350,20 +349,7 @@ int mdp_scenario_sim_create(const int32_t *row, uint32_t n, double m, float p, d
 
 void mdp_scenario_sim_destroy(mdp_scenario_sim *s)
 {
-    if (!s) return;
-    if (s->touched) {
-        (void)hipSetDevice(s->device);
-        if (s->stream) (void)hipStreamSynchronize(s->stream);
-        (void)hipFree(s->dM);
-        (void)hipFree(s->dgrid);
-        (void)hipFree(s->dmiss);
-        (void)hipFree(s->dhist);
-        (void)hipFree(s->dmatch);
-        if (s->ev0) (void)hipEventDestroy(s->ev0);
-        if (s->ev1) (void)hipEventDestroy(s->ev1);
-        if (s->stream) (void)hipStreamDestroy(s->stream);
-    }
-    delete s;
+    delete s;  // (its destructor releases the device side)
 }
 
 const char *mdp_scenario_sim_kernel(const mdp_scenario_sim *s) { return s ? s->kname : ""; }
@@ -399,18 +385,18 @@ int mdp_scenario_sim_tables(mdp_scenario_sim *s, int ts, int tdis, const double 
     if (nrep == 0) return MDP_OK;
     if (int rc = sim_device(s)) return rc;
     if (hist)
-        if (int rc = dev_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+        if (int rc = s->dhist.grow((size_t)call.hist_cells)) return rc;
     if (match)
-        if (int rc = dev_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+        if (int rc = s->dmatch.grow((size_t)call.match_cells)) return rc;
     int rc = mdp_scenario_sim_tables_device(s, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, seed, rep0, nrep,
-                                            hist ? (uint64_t *)s->dhist : nullptr,
-                                            match ? (uint64_t *)s->dmatch : nullptr, s->stream);
+                                            hist ? (uint64_t *)s->dhist.get() : nullptr,
+                                            match ? (uint64_t *)s->dmatch.get() : nullptr, s->stream);
     if (rc) return rc;
     std::vector<uint64_t> hh(hist ? (size_t)call.hist_cells : 0), hm(match ? (size_t)call.match_cells : 0);
     if (hist)
-        HIP_TRY(hipMemcpyAsync(hh.data(), s->dhist, hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(hh.data(), s->dhist.get(), hh.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     if (match)
-        HIP_TRY(hipMemcpyAsync(hm.data(), s->dmatch, hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(hm.data(), s->dmatch.get(), hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     for (size_t i = 0; i < hh.size(); ++i) hist[i] += hh[i];
     for (size_t i = 0; i < hm.size(); ++i) match[i] += hm[i];
@@ -433,15 +419,15 @@ int mdp_scenario_sim_time_kernel(mdp_scenario_sim *s, int ts, int tdis, const do
     if (int rc = sim_call(s->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, nrep, true, want_match, &call)) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     if (int rc = sim_device(s)) return rc;
-    if (int rc = dev_grow(s->dhist, s->hist_cap, (size_t)call.hist_cells)) return rc;
+    if (int rc = s->dhist.grow((size_t)call.hist_cells)) return rc;
     if (want_match)
-        if (int rc = dev_grow(s->dmatch, s->match_cap, (size_t)call.match_cells)) return rc;
+        if (int rc = s->dmatch.grow((size_t)call.match_cells)) return rc;
     const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
     if (int rc = sim_upload(s, gr, s->stream)) return rc;
-    HIP_TRY(hipMemsetAsync(s->dhist, 0, call.hist_cells * sizeof(uint64_t), s->stream));
-    if (want_match) HIP_TRY(hipMemsetAsync(s->dmatch, 0, call.match_cells * sizeof(uint64_t), s->stream));
+    HIP_TRY(hipMemsetAsync(s->dhist.get(), 0, call.hist_cells * sizeof(uint64_t), s->stream));
+    if (want_match) HIP_TRY(hipMemsetAsync(s->dmatch.get(), 0, call.match_cells * sizeof(uint64_t), s->stream));
     auto launch = [&]() {
-        return sim_launch(s, call, gr, seed, 0, nrep, s->dhist, want_match ? s->dmatch : nullptr, s->stream);
+        return sim_launch(s, call, gr, seed, 0, nrep, s->dhist.get(), want_match ? s->dmatch.get() : nullptr, s->stream);
     };
     if (int rc = launch()) return rc;  // warm-up
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
