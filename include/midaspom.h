@@ -428,7 +428,7 @@ int mdp_scenario_run(mdp_scenario *scenario, double *d_out, void *stream);
 int mdp_scenario_time_kernels(mdp_scenario *scenario, double *d_out, void *stream, int reps, double *ms);
 
 /* ------------------------------------------------------------------ */
-/* Simulated scenario likelihoods for rows of up to 64 patches          */
+/* Simulated scenario likelihoods for rows of up to 1024 patches        */
 /* (Rscript/simuls_traj.R, simtrajH1 / simtrajH2)                       */
 /* ------------------------------------------------------------------ */
 
@@ -440,28 +440,53 @@ int mdp_scenario_time_kernels(mdp_scenario *scenario, double *d_out, void *strea
  * and tdis baseline years (E = e, pC = c s1), and its final state is tallied:
  *   L = 2^n E[prior(final) 1{final compatible with the row}]
  * exactly in expectation.  Draws are Philox4x32-10 keyed by `seed`, addressed
- * by (replicate, year, patch pair) as in the future engine, the initial state
- * at counter {rep_lo, rep_hi, 0xffffffff, 1}; the grid point is not in the
+ * by (replicate, year, patch pair) as in the future engine.  The initial
+ * state: patch k is occupied iff bit k & 31 of word (k >> 5) & 3 of
+ * philox(seed; rep_lo, rep_hi, 0xffffffff, 1 + (k >> 7)) is set -- one
+ * counter per 128 patches, {.., 0xffffffff, 1} for the first (for k < 64 the
+ * definition the lane kernel has always had).  Counter word 3 >= 1 under word
+ * 2 = 0xffffffff meets neither a year's draws (word 2 = t <= 12287) nor the
+ * future engine's {.., 0xffffffff, 0}.  The grid point is not in the
  * counter, so every point sees the same replicates (common random numbers)
- * and no result depends on how replicates or points are split.
+ * and no result depends on how replicates or points are split, nor on the
+ * kernel that runs them.
  *
- * create: row, n, m, p, d, kind as mdp_scenario_create; 1 <= n <= 64.  No
- * device call is made before the first computing call, and every refusal of
- * every call comes before its first device call.  Options (test hooks):
+ * create: row, n, m, p, d, kind as mdp_scenario_create; 1 <= n <= 64, or
+ * <= 1024 under MDP_SIM_WAVE.  No device call is made before the first
+ * computing call, and every refusal of every call comes before its first
+ * device call.  Options:
+ *   MDP_SIM_WAVE=0|auto|1   the kernel family.  0 (default): the lane kernel
+ *                           k_scnsim<NM>, one replicate per lane, n <= 64.
+ *                           auto: k_scnsim<NM> for n <= 64, the patch-parallel
+ *                           k_scnsim_wave<NP> (one replicate per wave, NP =
+ *                           1, 2, 4, 8 patch pairs per lane for n <= 128,
+ *                           256, 512, 1024) beyond.  1: k_scnsim_wave<NP> for
+ *                           every n <= 1024.  Same tables where both run.
+ * and the test hooks
  *   MDP_SIM_NM=8|16|32|64   the instantiation k_scnsim<NM>, at least the one
- *                           n needs (the smallest NM >= n); smaller: MDP_EINVAL
+ *                           n needs (the smallest NM >= n); smaller, or with
+ *                           a wave kernel selected: MDP_EINVAL
+ *   MDP_SIM_NP=1|2|4|8      the instantiation k_scnsim_wave<NP>, at least the
+ *                           one n needs; smaller, or with a lane kernel
+ *                           selected: MDP_EINVAL
  *   MDP_SIM_LAUNCH_PTS=N    at most N grid points per launch (0: no cap)
  * Refusals: MDP_EINVAL for n = 0, a row value outside {-1, 0, 1}, both
  * tables NULL, ts < 0 or tdis < 0, a negative or non-finite e, c or dsrc, a K
  * that is not finite and > 0, an unknown option name or value;
- * MDP_EUNSUPPORTED for n > 64, `match` with more than 10 missing patches,
- * ts + tdis > 12288, more than 2^20 grid points or 2^24 cells in a table,
- * nrep > 2^31 per call. */
+ * MDP_EUNSUPPORTED for n > 64 (n > 1024 under MDP_SIM_WAVE=auto or 1), `match`
+ * with more than 10 missing patches, ts + tdis > 12288, more than 2^20 grid
+ * points or 2^24 cells in a table, nrep > 2^31 per call.
+ *
+ * Past 64 patches `match` is a weak statistic under a uniform start: a
+ * replicate matches n observed patches with probability near 2^-n, so the
+ * table is empty for any feasible nrep unless the scenario itself drives the
+ * state to the row.  `hist` (read through the share of replicates ending at
+ * the observed count, Rscript/simuls_traj.R) stays informative. */
 typedef struct mdp_scenario_sim mdp_scenario_sim;
 int mdp_scenario_sim_create(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
                             const char *options, mdp_scenario_sim **out);
 void mdp_scenario_sim_destroy(mdp_scenario_sim *sim);
-/* "k_scnsim<32>" (owned by the engine) */
+/* "k_scnsim<32>" or "k_scnsim_wave<2>" (owned by the engine) */
 const char *mdp_scenario_sim_kernel(const mdp_scenario_sim *sim);
 /* Over replicates [rep0, rep0 + nrep) and the grid points g = ((ie*nc + ic)*nK
  * + iK)*nd + id (the layout of mdp_scenario_lik; nd = 1 and dsrc ignored for
@@ -482,7 +507,10 @@ int mdp_scenario_sim_tables_device(mdp_scenario_sim *sim, int ts, int tdis, cons
                                    uint32_t nd, uint64_t seed, uint64_t rep0, uint64_t nrep, uint64_t *d_hist,
                                    uint64_t *d_match, void *stream);
 /* out[g] = (sum_j (double)prior_j * (double)match[g][j], j ascending) * 2^n
- * / nrep, prior_j the float prior of completion j (dieoff.c:230).  Host. */
+ * / nrep, prior_j the float prior of completion j (dieoff.c:230).  For
+ * n > 64 the mean is scaled, ldexp(sum / nrep, n): 0 for a zero sum and never
+ * NaN (2^1024 is not a double), the same value wherever the first form is
+ * finite.  Host. */
 int mdp_scenario_sim_lik(const mdp_scenario_sim *sim, const uint64_t *match, size_t npoints, uint64_t nrep,
                          double *out);
 /* Mean duration (ms) of `reps` runs of the call's launches over replicates

@@ -418,14 +418,24 @@ class Scenario:
 class ScenarioSim:
     """The two scenario hypotheses by simulation (``mdp_scenario_sim``,
     Rscript/simuls_traj.R simtrajH1 / simtrajH2), for first survey rows of up
-    to 64 patches: every replicate draws a uniform initial state, runs ``ts``
-    scenario years and ``tdis`` baseline years, and its final state is tallied
-    per grid point.  All grid points see the same replicates.
+    to 64 patches, or up to 1024 with ``MDP_SIM_WAVE``: every replicate draws
+    a uniform initial state, runs ``ts`` scenario years and ``tdis`` baseline
+    years, and its final state is tallied per grid point.  All grid points see
+    the same replicates.
 
-    ``options`` (a dict or "NAME=VALUE;..." string; test hooks): ``MDP_SIM_NM``
-    = 8 | 16 | 32 | 64 picks the kernel instantiation, ``MDP_SIM_LAUNCH_PTS``
-    = N caps the grid points per launch.  Creating the object makes no device
-    call; the first computing call does."""
+    ``options`` (a dict or "NAME=VALUE;..." string): ``MDP_SIM_WAVE`` = 0 |
+    auto | 1 selects the kernel family -- 0 (the default) the lane kernel
+    ``k_scnsim<NM>`` alone (65 patches are refused), ``auto`` the
+    patch-parallel ``k_scnsim_wave<NP>`` for 65 to 1024 patches, 1 that kernel
+    for every row; both give the same tables where both run.  Past 64 patches
+    ``match`` is almost always empty under a uniform start (a replicate
+    matches a row of n observed patches with probability near 2**-n): ``hist``
+    and ``count_likelihood`` are the statistic there.  Test hooks:
+    ``MDP_SIM_NM`` = 8 | 16 | 32 | 64 and ``MDP_SIM_NP`` = 1 | 2 | 4 | 8 pick
+    the instantiation of the selected family (at least what the row needs;
+    the other family's hook is refused), ``MDP_SIM_LAUNCH_PTS`` = N caps the
+    grid points per launch.  Creating the object makes no device call; the
+    first computing call does."""
 
     def __init__(self, row, kind: str = "dieoff", m: float = 400.0, p: float = 0.5, d: float = 200.0,
                  device: int = 0, options=None):
@@ -443,7 +453,7 @@ class ScenarioSim:
 
     @property
     def kernel(self) -> str:
-        """Name of the simulation kernel, e.g. ``k_scnsim<32>``."""
+        """Name of the simulation kernel, e.g. ``k_scnsim<32>`` or ``k_scnsim_wave<2>``."""
         return lib().mdp_scenario_sim_kernel(self._h).decode()
 
     def close(self):

@@ -245,7 +245,7 @@ ENGINE_OPTION_NAMES = (
     "MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")
 SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW", "MDP_SCN_LAUNCH_PTS")
 FUTURE_OPTION_NAMES = ("MDP_FUT_WIDE",)
-SCENARIO_SIM_OPTION_NAMES = ("MDP_SIM_NM", "MDP_SIM_LAUNCH_PTS")
+SCENARIO_SIM_OPTION_NAMES = ("MDP_SIM_NM", "MDP_SIM_LAUNCH_PTS", "MDP_SIM_WAVE", "MDP_SIM_NP")
 
 
 DIAG_OPTION_NAMES = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")

@@ -19,7 +19,7 @@
  *
  * Extension: -R <nrep> evaluates the same likelihood by simulation
  * (mdp_scenario_sim, Rscript/simuls_traj.R) with nrep replicates per grid
- * point -- the path for first rows of 17 to 64 patches, which the exact
+ * point -- the path for first rows of 17 to 1024 patches, which the exact
  * engine refuses; -r <seed> (default 0) keys the draws, -H <file> writes the
  * final occupied-patch counts, one line per grid point in output order, n+1
  * "%llu\t" values.  All grid points share their replicates, so the files do
@@ -63,7 +63,8 @@ static void *run_slab(void *arg)
         unsigned nm = 0;
         for (unsigned j = 0; j < sl->n; ++j) nm += sl->row[j] == -1;
         uint64_t *match = NULL;
-        sl->rc = mdp_scenario_sim_create(sl->row, sl->n, sl->mdisp, sl->prioroc, sl->d, SCN_KIND, sl->dev, NULL, &sim);
+        sl->rc = mdp_scenario_sim_create(sl->row, sl->n, sl->mdisp, sl->prioroc, sl->d, SCN_KIND, sl->dev,
+                                         "MDP_SIM_WAVE=auto", &sim);
         if (sl->rc == MDP_OK && sl->nK) {
             match = calloc(G << nm, sizeof(uint64_t)); /* nm <= 10, checked in main */
             if (!match) {
@@ -179,6 +180,10 @@ int main(int argc, char **argv)
     /* observed states and priors for the log lines (dieoff.c:205-232) */
     unsigned nm = 0;
     for (unsigned j = 0; j < n; ++j) nm += row[j] == -1;
+    if (nrep && n > 1024) { /* the simulator's patch-parallel kernel holds 1024 patches */
+        fprintf(stderr, "midaspom: %u patches in the first row: -R takes at most 1024\n", n);
+        return 1;
+    }
     if (nrep && nm > 10) { /* the simulator's match table holds 2^10 completions */
         fprintf(stderr, "midaspom: %u missing patches in the first row: -R takes at most 10\n", nm);
         return 1;
@@ -192,10 +197,10 @@ int main(int argc, char **argv)
         if (row[j] == -1) s1++;
         for (unsigned k = 0; k < np; ++k) {
             if (row[j] > -1) {
-                ps[k] += (unsigned long long)row[j] << (n - j - 1);
+                if (n <= 64) ps[k] += (unsigned long long)row[j] << (n - j - 1);
             } else {
                 const unsigned st1 = np >> s1, b = k / st1 % 2;
-                ps[k] += (unsigned long long)b << (n - j - 1);
+                if (n <= 64) ps[k] += (unsigned long long)b << (n - j - 1);
                 pr[k] *= b * prioroc + (1 - b) * (1 - prioroc);
             }
         }
@@ -216,7 +221,15 @@ int main(int argc, char **argv)
 #if SCN_KIND == 1
         printf("\t");
 #endif
-        for (unsigned j = 0; j < n; ++j) printf("%u ", (unsigned)((ps[k] >> (n - 1 - j)) & 1u));
+        if (n <= 64) {
+            for (unsigned j = 0; j < n; ++j) printf("%u ", (unsigned)((ps[k] >> (n - 1 - j)) & 1u));
+        } else { /* -R only: the state number passes 64 bits, the same digits patch by patch */
+            unsigned q = 0;
+            for (unsigned j = 0; j < n; ++j) {
+                if (row[j] == -1) q++;
+                printf("%u ", row[j] > -1 ? (unsigned)row[j] & 1u : k / (np >> q) % 2);
+            }
+        }
         printf("; pr=%lf\n", pr[k]);
     }
     double *K = malloc(nstep * sizeof(double)), *dv = malloc(nstepd * sizeof(double));

@@ -7,12 +7,19 @@
 // the missing-patch list, the dispersal table, the float priors and the source
 // row at distance DSRC, and the launches of a call over NK grid points (one
 // e, one c, one distance) and NREP replicates with both tables requested.
+// With k_scnsim_wave<NP> selected (MDP_SIM_WAVE) the row's per-lane words and
+// (lane, bit) list are printed in full, the digests are of the distance image,
+// the priors and the source row, and every 16-byte slot the kernel can address
+// -- every survivor l < n, every lane, every j < NP -- is checked to lie
+// inside the image and to hold M's bits.
 // Exit 0, or mdp_last_error() on stderr and exit 1.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "spom_future_plan.h"  // fut_wide_slot0
 #include "spom_scnsim_plan.h"
 
 namespace {
@@ -48,16 +55,58 @@ int main(int argc, char **argv)
     if (sim_parse_opts(argv[6], &opts)) return fail();
     SimPlan pl;
     if (sim_plan(row.data(), n, m, p, d, kind, opts, &pl)) return fail();
-    printf("kernel k_scnsim<%u>\n", pl.nm);
-    printf("row n %u nmiss %u live %llx fixed %llx missing %llx\n", pl.n, pl.nmiss, (unsigned long long)pl.live,
-           (unsigned long long)pl.fixed, (unsigned long long)pl.missmask);
     std::vector<double> src;
     sim_src(pl, &ds, 1, &src);
-    printf("miss %016llx M %016llx prior %016llx src %016llx\n",
-           (unsigned long long)fnv(pl.miss.data(), pl.miss.size() * sizeof(uint32_t)),
-           (unsigned long long)fnv(pl.M.data(), pl.M.size() * sizeof(double)),
-           (unsigned long long)fnv(pl.prior.data(), pl.prior.size() * sizeof(float)),
-           (unsigned long long)fnv(src.data(), src.size() * sizeof(double)));
+    if (pl.np) {
+        printf("kernel k_scnsim_wave<%u>\n", pl.np);
+        printf("row n %u nmiss %u len %u\n", pl.n, pl.nmiss, pl.wlen);
+        printf("fixed");
+        for (uint32_t v : pl.wfixed) printf(" %x", v);
+        printf("\nmissing");
+        for (uint32_t v : pl.wmissmask) printf(" %x", v);
+        printf("\nmiss");
+        for (uint32_t v : pl.wmiss) printf(" %x", v);
+        printf("\nimage %016llx prior %016llx src %016llx\n",
+               (unsigned long long)fnv(pl.image.data(), pl.image.size() * sizeof(double)),
+               (unsigned long long)fnv(pl.prior.data(), pl.prior.size() * sizeof(float)),
+               (unsigned long long)fnv(src.data(), src.size() * sizeof(double)));
+        if (src.size() != (size_t)128 * pl.np || pl.image.size() != (size_t)2 * pl.wlen || (pl.wlen & 1u)) {
+            fprintf(stderr, "scnsim_plan_check: table sizes\n");
+            return 1;
+        }
+        // every slot a lane reads for every survivor l: inside the image, and
+        // the bits of the lane kernels' table entry exp(-(1/m)|l-k|d)
+        const double a = 1.0 / m;
+        for (uint32_t l = 0; l < n; ++l) {
+            const uint32_t s0 = fut_wide_slot0(n, pl.wlen, l);
+            for (uint32_t pair = 0; pair < 64 * pl.np; ++pair) {
+                const size_t at = 2 * ((size_t)pair + s0);
+                if (at + 1 >= pl.image.size()) {
+                    fprintf(stderr, "scnsim_plan_check: slot of pair %u, survivor %u outside the image\n", pair, l);
+                    return 1;
+                }
+                for (uint32_t q = 0; q < 2; ++q) {
+                    const uint32_t k = 2 * pair + q;
+                    if (k >= n) continue;  // a padded patch: never live, its sum is not used
+                    const double want = k == l ? 0.0 : exp(-a * (double)(k > l ? k - l : l - k) * d);
+                    if (memcmp(&want, &pl.image[at + q], sizeof want)) {
+                        fprintf(stderr, "scnsim_plan_check: image entry of M[%u][%u] differs\n", l, k);
+                        return 1;
+                    }
+                }
+            }
+        }
+        printf("slots %u x %u inside the image\n", n, 64 * pl.np);
+    } else {
+        printf("kernel k_scnsim<%u>\n", pl.nm);
+        printf("row n %u nmiss %u live %llx fixed %llx missing %llx\n", pl.n, pl.nmiss, (unsigned long long)pl.live,
+               (unsigned long long)pl.fixed, (unsigned long long)pl.missmask);
+        printf("miss %016llx M %016llx prior %016llx src %016llx\n",
+               (unsigned long long)fnv(pl.miss.data(), pl.miss.size() * sizeof(uint32_t)),
+               (unsigned long long)fnv(pl.M.data(), pl.M.size() * sizeof(double)),
+               (unsigned long long)fnv(pl.prior.data(), pl.prior.size() * sizeof(float)),
+               (unsigned long long)fnv(src.data(), src.size() * sizeof(double)));
+    }
     const double e = 0.5, c = 0.5;
     std::vector<double> K(nK, 1.0);
     SimCall call;

@@ -1,7 +1,8 @@
 // midaspom_amd/csrc/spom_scnsim.hip -- the die-off and habitat-loss
 // hypotheses by simulation, for first survey rows the exact scenario engine
-// (spom_scenario.hip, 2^n states, n <= 16) cannot hold: 17..64 patches, and
-// any smaller row.  The reference's authors do the same in R
+// (spom_scenario.hip, 2^n states, n <= 16) cannot hold: 17..64 patches with
+// k_scnsim<NM>, 65..1024 with k_scnsim_wave<NP> further down, and any
+// smaller row.  The reference's authors do the same in R
 // (Rscript/simuls_traj.R, simtrajH1 / simtrajH2): draw an initial state, run
 // ts years under the scenario and tdis baseline years, tally the final state.
 //
@@ -12,8 +13,9 @@
 //
 // One replicate rg = rep0 + r, the same for every grid point but for its
 // rates (common random numbers: the counter holds no grid point):
-//   initial state  w = philox(seed; rg_lo, rg_hi, 0xffffffff, 1): patch k
-//                  occupied iff bit k & 31 of word k >> 5 (fair bits);
+//   initial state  w = philox(seed; rg_lo, rg_hi, 0xffffffff, 1 + (k >> 7)):
+//                  patch k occupied iff bit k & 31 of word (k >> 5) & 3 (fair
+//                  bits; one counter per 128 patches, {.., 1} for k < 64);
 //   year t         the future engine's addressing (spom_future.hip): pair
 //                  m = k >> 1, w = philox(seed; rg_lo, rg_hi, t, m), word
 //                  2(k&1) the extinction draw, 2(k&1)+1 the colonisation draw;
@@ -24,7 +26,7 @@
 //                  baseline years: E = min(1, e), pC = min(1, c s1).
 // Contraction is off: every product is rounded before the next operation.
 //
-// GPU design: one lane per (grid point, replicate), the 64 lanes of a wave on
+// GPU design of k_scnsim<NM>: one lane per (grid point, replicate), the 64 lanes of a wave on
 // one grid point, so K, e, c, E and the source row are wave-uniform (scalar
 // operands).  A work tile is (point, 256 replicates); workgroups of 256
 // threads walk the tiles grid-stride.  Occupancy is one 64-bit mask; the
@@ -42,6 +44,7 @@
 #include <vector>
 
 #include "spom_dev.h"
+#include "spom_future_plan.h"  // fut_wide_slot0: the addressing of the distance image
 #include "spom_scnsim_plan.h"
 
 #pragma clang fp contract(off)
@@ -210,6 +213,185 @@ __global__ __launch_bounds__(kSimBlock) void k_scnsim(SimArgs a, const double *_
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_scnsim_wave<NP>: rows of 65..1024 patches (and any smaller row).  One
+// wave per (grid point, replicate), the shape of k_future_wide<NP>
+// (spom_future.hip): lane lambda owns the patch pairs m = lambda + 64*j,
+// j < NP, and holds patch 2m + p in bit 2j + p of its occupancy word.  The
+// survivors of a year are 2*NP wave ballots, walked in ascending patch order
+// (j, then lane, then parity); every step adds one row of the unscaled
+// Toeplitz table, a window of the two-sided distance image in LDS
+// (spom_scnsim_plan.h), to the lane's 2*NP running sums.  Same stream, same
+// sums in the same order, K applied after the sum by sim_year's expression:
+// on n <= 64 patches the tables of k_scnsim<NM>, bit for bit.  A work tile is
+// (point, 4 replicates), one per wave of the workgroup.
+// ---------------------------------------------------------------------------
+struct SimWaveArgs {
+    uint32_t n, nmiss, ts, tdis;
+    uint32_t nc, nK, nd, kind;
+    uint64_t p0;       // first grid point of the launch
+    uint64_t tiles;    // work tiles of the launch: points x tpp
+    uint64_t tpp;      // tiles per point: ceil(nrep / 4)
+    uint64_t rep0, nrep;
+    uint32_t key0, key1;
+    uint32_t len, pad;  // len: doubles per copy of the distance image
+};
+
+// one year of the wave's replicate rg: the lane's occupancy word after year
+// t + 1.  (ks, km) as sim_year: pC = (c (s1 + src_k ks)) km.
+template <int NP>
+__device__ __forceinline__ uint32_t sim_wave_year(const SimWaveArgs &a, const double2 *G2,
+                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
+                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
+                                                  double E, double c, double ks, double km)
+{
+    uint64_t bal[NP][2];
+    uint32_t colw[2 * NP];
+    uint32_t surv = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t m = lane + 64u * j;
+        bool s0 = false, s1 = false;
+        colw[2 * j] = colw[2 * j + 1] = 0;
+        if (m < npairs) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
+            colw[2 * j] = w.y >> 1;
+            colw[2 * j + 1] = w.w >> 1;
+            // extinction: an occupied patch survives if u > E (dieoff.c:56-64)
+            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
+            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
+        }
+        bal[j][0] = __ballot(s0);
+        bal[j][1] = __ballot(s1);
+        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
+    }
+    // colonisation sums, ascending l for every k (dieoff.c:72-77): patch
+    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
+    double s[2 * NP];
+#pragma unroll
+    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        uint64_t both = bal[j][0] | bal[j][1];
+        while (both) {
+            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
+            both &= both - 1;
+#pragma unroll
+            for (uint32_t p = 0; p < 2; ++p) {
+                if (!((bal[j][p] >> lam) & 1u)) continue;
+                const uint32_t l = 2 * (lam + 64u * j) + p;
+                const double2 *row = G2 + fut_wide_slot0(a.n, a.len, l) + lane;
+#pragma unroll
+                for (int jj = 0; jj < NP; ++jj) {
+                    const double2 v = row[64 * jj];
+                    s[2 * jj] += v.x;
+                    s[2 * jj + 1] += v.y;
+                }
+            }
+        }
+    }
+    uint32_t nw = surv;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint32_t bit = 1u << (2 * j + p);
+            if ((live & bit) && !(surv & bit)) {
+                const double sk = (p ? sv.y : sv.x) * ks;    // loss.c:95-98: the product is rounded before the add
+                double pc = (c * (s[2 * j + p] + sk)) * km;  // dieoff.c:78 (c s1) K
+                if (pc > 1) pc = 1;
+                if (u_lt(colw[2 * j + p], pc)) nw |= bit;
+            }
+        }
+    }
+    return nw;
+}
+
+template <int NP>
+__global__ __launch_bounds__(kSimBlock) void k_scnsim_wave(SimWaveArgs a, const double *__restrict__ image,
+                                                           const double *__restrict__ srcv,
+                                                           const double *__restrict__ ev, const double *__restrict__ cv,
+                                                           const double *__restrict__ Kv,
+                                                           const uint32_t *__restrict__ rowbits,  // fixed[64] | missmask[64]
+                                                           const uint32_t *__restrict__ miss,
+                                                           unsigned long long *__restrict__ hist,
+                                                           unsigned long long *__restrict__ match)
+{
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    // both copies of the distance image: 2*len doubles
+    double2 *G2 = reinterpret_cast<double2 *>(dyn);
+    for (uint32_t i = threadIdx.x; i < a.len; i += kSimBlock) G2[i] = reinterpret_cast<const double2 *>(image)[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t npairs = (a.n + 1) >> 1;
+    const uint32_t years = a.ts + a.tdis;
+    const uint32_t fixed = rowbits[lane], missmask = rowbits[64 + lane];
+    // bit 2j+p set where patch 2*(lane + 64*j) + p exists
+    uint32_t live = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const uint32_t k0 = 2 * (lane + 64u * j);
+        if (k0 < a.n) live |= 1u << (2 * j);
+        if (k0 + 1 < a.n) live |= 2u << (2 * j);
+    }
+    for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        // workgroup-uniform: the tile's grid point; wave-uniform: its replicate
+        const uint64_t pl = tile / a.tpp;
+        const uint64_t g = a.p0 + pl;
+        const uint64_t r = (tile - pl * a.tpp) * kSimWaveReps + wave;
+        if (r >= a.nrep) continue;  // a wave past the last replicate
+        const uint64_t rg = a.rep0 + r;
+        const uint32_t id = (uint32_t)(g % a.nd), iK = (uint32_t)((g / a.nd) % a.nK);
+        const uint32_t ic = (uint32_t)((g / ((uint64_t)a.nd * a.nK)) % a.nc);
+        const uint32_t ie = (uint32_t)(g / ((uint64_t)a.nd * a.nK * a.nc));
+        const double e = ev[ie], c = cv[ic], K = Kv[iK];
+        double Eb = e;  // baseline and loss: E = e (loss.c:57)
+        if (Eb > 1) Eb = 1;
+        double Es = a.kind ? e : e / K;  // dieoff.c:56-57
+        if (Es > 1) Es = 1;
+        const double Ks = a.kind ? K : 0.0, Km = a.kind ? 1.0 : K;
+        const double *src = srcv + (size_t)id * (128 * NP);
+        // ---- initial state: patch k = 2*(lane + 64*j) + p from bit k & 31 of
+        // word (k >> 5) & 3 of counter (rg, 0xffffffff, 1 + (k >> 7)); k >> 7 = j
+        uint32_t occ = 0;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), 0xffffffffu, 1u + j});
+            const uint32_t q = (lane >> 4) & 3u;
+            const uint32_t word = q == 0 ? w.x : q == 1 ? w.y : q == 2 ? w.z : w.w;
+            occ |= ((word >> (2 * (lane & 15u))) & 3u) << (2 * j);
+        }
+        occ &= live;
+        // ---- ts scenario years, then tdis baseline years
+        for (uint32_t t = 0; t < years; ++t) {
+            const bool scen = t < a.ts;
+            // the replicate is extinct and no source in this or any later
+            // year: every sum is 0, pC = c*0, and no draw is below 0
+            if (!(a.kind && scen) && __ballot(occ != 0) == 0) break;
+            occ = sim_wave_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, scen ? Es : Eb, c, scen ? Ks : 0.0,
+                                    scen ? Km : 1.0);
+        }
+        // ---- tallies of the final state: one integer atomic per table
+        if (hist) {
+            uint32_t m = 0;
+#pragma unroll
+            for (int b = 0; b < 2 * NP; ++b) m += (uint32_t)__popcll(__ballot((occ >> b) & 1u));
+            if (lane == 0) atomicAdd(&hist[g * (a.n + 1) + m], 1ull);
+        }
+        if (match) {  // compatible with the row: its completion, the first missing patch the MSB
+            const bool ok = ((occ ^ fixed) & ~missmask & live) == 0;
+            uint32_t j = 0;
+            for (uint32_t q = 0; q < a.nmiss; ++q) {
+                const uint32_t mq = miss[q];
+                j = (j << 1) | (uint32_t)(__ballot(lane == (mq >> 8) && ((occ >> (mq & 0xffu)) & 1u)) != 0);
+            }
+            if (__ballot(!ok) == 0 && lane == 0) atomicAdd(&match[(g << a.nmiss) + j], 1ull);
+        }
+    }
+}
+
 }  // namespace
 
 // (DevQueue: the device, stream and events, released after the buffers below)
@@ -218,7 +400,8 @@ struct mdp_scenario_sim : DevQueue {
     bool ready = false;  // the device side exists (set up by the first call that needs it)
     bool touched = false;  // a device call was made for this engine
     char kname[32] = "";
-    DevBuf<double> dM, dgrid;
+    DevBuf<double> dM, dgrid;  // dM: the lane kernel's table, or the wave kernel's image
+    DevBuf<uint32_t> drow;     // the wave kernel's fixed[64] | missmask[64]
     DevBuf<uint32_t> dmiss;
     DevBuf<unsigned long long> dhist, dmatch;
     ~mdp_scenario_sim()
@@ -242,6 +425,19 @@ int sim_for_nm(uint32_t nm, F &&fn)
     }
 }
 
+// and over the patch pairs per lane of k_scnsim_wave
+template <typename F>
+int sim_for_np(uint32_t np, F &&fn)
+{
+    switch (np) {
+    case 1: return fn(std::integral_constant<int, 1>());
+    case 2: return fn(std::integral_constant<int, 2>());
+    case 4: return fn(std::integral_constant<int, 4>());
+    case 8: return fn(std::integral_constant<int, 8>());
+    default: return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", np);
+    }
+}
+
 // the first device calls of an engine: the device, the tables, stream and events
 int sim_device(mdp_scenario_sim *s)
 {
@@ -254,10 +450,16 @@ int sim_device(mdp_scenario_sim *s)
     if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
     HIP_TRY(hipSetDevice(s->device));
     s->touched = true;
+    const SimPlan &p = s->plan;
     if (s->dM.empty())
-        if (int rc = s->dM.assign(s->plan.M)) return rc;
+        if (int rc = s->dM.assign(p.np ? p.image : p.M)) return rc;
     if (s->dmiss.empty())
-        if (int rc = s->dmiss.assign(s->plan.miss)) return rc;
+        if (int rc = s->dmiss.assign(p.np ? p.wmiss : p.miss)) return rc;
+    if (p.np && s->drow.empty()) {
+        std::vector<uint32_t> rowbits(p.wfixed);
+        rowbits.insert(rowbits.end(), p.wmissmask.begin(), p.wmissmask.end());
+        if (int rc = s->drow.assign(rowbits)) return rc;
+    }
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
     if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
@@ -271,17 +473,22 @@ struct SimGrid {
     uint32_t ne, nc, nK, nd;
 };
 
-// the axes and the source rows into s->dgrid: [e | c | K | src[nd][nm]].
+// doubles of s->dgrid before the source rows: the three axes, rounded up to
+// an even count (k_scnsim_wave reads the rows as double2)
+size_t sim_src_at(const SimGrid &gr) { return ((size_t)gr.ne + gr.nc + gr.nK + 1) & ~(size_t)1; }
+
+// the axes and the source rows into s->dgrid: [e | c | K | (pad) | src[nd][ld]].
 // `st` is drained first, so that no launch still reads the buffer.
 int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
 {
     std::vector<double> src;
     sim_src(s->plan, gr.dsrc, gr.nd, &src);
     std::vector<double> h;
-    h.reserve((size_t)gr.ne + gr.nc + gr.nK + src.size());
+    h.reserve(sim_src_at(gr) + src.size());
     h.insert(h.end(), gr.e, gr.e + gr.ne);
     h.insert(h.end(), gr.c, gr.c + gr.nc);
     h.insert(h.end(), gr.K, gr.K + gr.nK);
+    h.resize(sim_src_at(gr), 0.0);
     h.insert(h.end(), src.begin(), src.end());
     HIP_TRY(hipStreamSynchronize(st));
     return s->dgrid.assign(h);
@@ -292,7 +499,37 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
                uint64_t nrep, unsigned long long *d_hist, unsigned long long *d_match, hipStream_t st)
 {
     const SimPlan &p = s->plan;
-    const double *de = s->dgrid.get(), *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = dK + gr.nK;
+    const double *de = s->dgrid.get(), *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = de + sim_src_at(gr);
+    if (p.np) {
+        const size_t lds = (size_t)2 * p.wlen * sizeof(double);  // both copies of the image: <= 32 KB
+        for (const SimLaunch &l : call.launches) {
+            SimWaveArgs a{};
+            a.n = p.n;
+            a.nmiss = p.nmiss;
+            a.ts = (uint32_t)gr.ts;
+            a.tdis = (uint32_t)gr.tdis;
+            a.nc = gr.nc;
+            a.nK = gr.nK;
+            a.nd = gr.nd;
+            a.kind = (uint32_t)p.kind;
+            a.p0 = l.p0;
+            a.tiles = l.tiles;
+            a.tpp = call.tiles_per_point;
+            a.rep0 = rep0;
+            a.nrep = nrep;
+            a.key0 = (uint32_t)seed;
+            a.key1 = (uint32_t)(seed >> 32);
+            a.len = p.wlen;
+            if (int rc = sim_for_np(p.np, [&](auto NP) {
+                    hipLaunchKernelGGL(k_scnsim_wave<decltype(NP)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a,
+                                       s->dM.get(), dsrc, de, dc, dK, s->drow.get(), s->dmiss.get(), d_hist, d_match);
+                    return MDP_OK;
+                }))
+                return rc;
+            HIP_TRY(hipGetLastError());
+        }
+        return MDP_OK;
+    }
     const size_t lds = p.nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0;
     for (const SimLaunch &l : call.launches) {
         SimArgs a{};
@@ -342,7 +579,8 @@ int mdp_scenario_sim_create(const int32_t *row, uint32_t n, double m, float p, d
     if (!s) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     if (int rc = sim_plan(row, n, m, p, d, kind, opts, &s->plan)) return rc;
     s->device = device;
-    snprintf(s->kname, sizeof s->kname, "k_scnsim<%u>", s->plan.nm);
+    if (s->plan.np) snprintf(s->kname, sizeof s->kname, "k_scnsim_wave<%u>", s->plan.np);
+    else snprintf(s->kname, sizeof s->kname, "k_scnsim<%u>", s->plan.nm);
     *out = s.release();
     return MDP_OK;
 }

@@ -15,7 +15,7 @@ start / end :320, :397, send / gather :401-418).  Rank 0 writes the file.
 
 `-R nrep` evaluates the likelihood by simulation (midaspom_amd.ScenarioSim,
 Rscript/simuls_traj.R) with nrep replicates per grid point: the path for first
-rows of 17 to 64 patches.  `-r seed` (default 0) keys the draws; `-H file`
+rows of 17 to 1024 patches.  `-r seed` (default 0) keys the draws; `-H file`
 writes the final occupied-patch counts, one line per grid point (single
 process only).  Same bytes as the compiled drop-ins, for every -g and rank
 count: all grid points share their replicates.
@@ -96,7 +96,7 @@ def _slab(mdp, row, kind, a, K, dv, nd, device):
     the exact engine, or with -R the simulator."""
     d = dv if kind == "loss" else None
     if a.R:
-        with mdp.ScenarioSim(row, kind, m=a.m, p=a.p, d=a.d, device=device) as sim:
+        with mdp.ScenarioSim(row, kind, m=a.m, p=a.p, d=a.d, device=device, options="MDP_SIM_WAVE=auto") as sim:
             hist, match = sim.tables(a.e, a.c, K, d, ts=a.b, tdis=a.a, nrep=a.R, seed=a.r, hist=bool(a.H))
             lik = sim.lik(match, a.R)[0, 0].reshape(K.size, nd)
         return lik, None if hist is None else hist[0, 0].reshape(K.size, nd, row.size + 1)
@@ -177,6 +177,9 @@ def main(argv=None) -> int:
     n = row.size
     if a.R and a.H and mpi:
         sys.stderr.write("midaspom: -H is not available under torchrun (the counts are not gathered)\n")
+        return 1
+    if a.R and n > 1024:
+        sys.stderr.write(f"midaspom: {n} patches in the first row: -R takes at most 1024\n")
         return 1
     if a.R and int((row == -1).sum()) > 10:
         sys.stderr.write(f"midaspom: {int((row == -1).sum())} missing patches in the first row: -R takes at most 10\n")

@@ -14,6 +14,20 @@ mdp_future_time_kernel of k_future<NM> over the same number of replicate-years
 e = 0.02..0.04, c = 0.03..0.08).  One JSON line per case: ms,
 replicate-years/s, and for the simulator the ratio to k_future's rate
 (yardstick: at least 0.5).
+
+    python scripts/scnsim_timing.py --wave [--reps 3]
+                                    [--out profiles/r13/scnsim_wave/timing.jsonl]
+
+The patch-parallel k_scnsim_wave<NP> (MDP_SIM_WAVE=auto) at n = 128, 256 and
+1024, die-off and loss, on the same 151 K values x 46 years, beside
+k_future_wide<NP> (Future(options="MDP_FUT_WIDE=auto").time_kernel) in the
+same process on the same n and the same replicate-years.  Replicates per
+point, chosen so that each case runs well under a second: 1000 at n = 128,
+400 at 256, 40 at 1024 (WAVE_NREP).  The yardstick is k_future_wide's rate,
+not the code under test; the bar is the same half.  The simulator's record
+also holds the mean final occupancy at the first and the last K, the future
+engine's that after the first and the last year (the two run in different
+occupancy regimes: a uniform start against the last survey row).
 """
 from __future__ import annotations
 
@@ -41,14 +55,53 @@ def problem(n):
     return row, post * (100.0 / float((np.outer(w, w) * post).sum()))
 
 
+WAVE_NREP = {128: 1000, 256: 400, 1024: 40}  # replicates per grid point
+
+
+def wave_cases(reps):
+    """One record per kernel and case of the --wave mode."""
+    ts, tdis, nK = 20, 26, 151
+    K = mdp.kgrid(nK, 0.1, 100.0)
+    for n, nrep in WAVE_NREP.items():
+        row, post = problem(n)
+        years = nK * nrep * (ts + tdis)
+        with mdp.Future(row, post, m=400.0, d=200.0, KD=1.0, KS=0.0, options="MDP_FUT_WIDE=auto") as f:
+            ms = f.time_kernel(nK * nrep, ts + tdis, seed=1, reps=reps)
+            fh, _ = f.summary(nK * nrep, ts + tdis, seed=1, occ=False)
+            fut = {"n": n, "kernel": f.kernel, "nrep": nK * nrep, "tfut": ts + tdis, "reps": reps, "ms": ms,
+                   "replicate_years_per_s": years / (ms * 1e-3),
+                   "mean_occupied_first_last_year": [float(mdp.mean_occupied(fh)[i]) for i in (0, -1)]}
+        yield fut
+        for kind in ("dieoff", "loss"):
+            dv = np.array([200.0])
+            with mdp.ScenarioSim(row, kind, m=400.0, d=200.0, options="MDP_SIM_WAVE=auto") as sim:
+                ms = sim.time_kernel(0.03, 0.05, K, dv, ts=ts, tdis=tdis, nrep=nrep, seed=1, reps=reps)
+                hist, _ = sim.tables(0.03, 0.05, K, dv, ts=ts, tdis=tdis, nrep=nrep, seed=1, match=False)
+                rate = years / (ms * 1e-3)
+                yield {"n": n, "kernel": sim.kernel, "kind": kind, "points": nK, "nrep": nrep, "ts": ts, "tdis": tdis,
+                       "reps": reps, "ms": ms, "replicate_years_per_s": rate,
+                       "rate_over_k_future_wide": rate / fut["replicate_years_per_s"],
+                       "mean_occupied_first_last_K": [float(mdp.mean_occupied(hist.reshape(-1, n + 1))[i])
+                                                      for i in (0, -1)]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nrep", type=int, default=10_000)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r11" / "scnsim" / "timing.jsonl"))
+    ap.add_argument("--wave", action="store_true", help="time k_scnsim_wave<NP> beside k_future_wide<NP>")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = Path(a.out)
+    sub = ("r13", "scnsim_wave") if a.wave else ("r11", "scnsim")
+    out = Path(a.out or ROOT / "profiles" / sub[0] / sub[1] / "timing.jsonl")
     out.parent.mkdir(parents=True, exist_ok=True)
+    if a.wave:
+        lines = []
+        for rec in wave_cases(a.reps):
+            lines.append(rec)
+            print(json.dumps(rec), flush=True)
+        out.write_text("".join(json.dumps(r) + "\n" for r in lines))
+        return
     ts, tdis, nK = 20, 26, 151
     K = mdp.kgrid(nK, 0.1, 100.0)
     lines = []
