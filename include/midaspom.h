@@ -15,6 +15,22 @@
  *    code; the reason is in mdp_last_error() (thread-local).  Nothing aborts
  *    or exits across the ABI;
  *  - an engine is not re-entrant; one host thread drives all its devices;
+ *  - Streams.  The device forms (mdp_engine_run, mdp_scenario_run,
+ *    mdp_future_simulate_device / _summary_device with mdp_future_check,
+ *    mdp_scenario_sim_tables_device, the two *_time_kernels) launch on the
+ *    caller's stream and return; what the caller queues on that stream
+ *    afterwards is ordered after them.  A call on a handle gives the result
+ *    it would give alone, whatever earlier device-form calls on that handle
+ *    are still pending on any stream.  Only the caller's output buffers are
+ *    the caller's to order.  A call that rewrites or reuses device state a
+ *    pending launch may read -- a new grid (mdp_engine_set_grid,
+ *    mdp_scenario_set_grid, every mdp_scenario_sim_tables* call), a host form,
+ *    a device form on a stream other than the pending one -- first waits for
+ *    the device; a device form behind another on the same stream does not
+ *    wait and makes no extra HIP call.  A stream need not outlive the work it
+ *    was given, but a device form on a stream that reuses the handle value of
+ *    one destroyed with work pending counts as "the same stream": synchronise
+ *    a stream before destroying it if that can happen;
  *  - results are deterministic (no floating-point atomics in any reduction;
  *    the future engine's integer counts -- the per-year extinct counts and
  *    the summary tables hist / occ of mdp_future_summary -- use LDS and
@@ -501,7 +517,9 @@ int mdp_scenario_sim_tables(mdp_scenario_sim *sim, int ts, int tdis, const doubl
                             uint64_t rep0, uint64_t nrep, uint64_t *hist, uint64_t *match);
 /* Same into caller-owned device memory (overwritten, not accumulated); the
  * launches are asynchronous on `stream` (NULL = HIP's null stream), after the
- * stream's earlier work has been waited for and the grid uploaded. */
+ * grid has been uploaded -- which waits for the device when an earlier
+ * device-form call of this simulator is still pending (Conventions, Streams),
+ * and for nothing otherwise. */
 int mdp_scenario_sim_tables_device(mdp_scenario_sim *sim, int ts, int tdis, const double *e, uint32_t ne,
                                    const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
                                    uint32_t nd, uint64_t seed, uint64_t rep0, uint64_t nrep, uint64_t *d_hist,

@@ -77,20 +77,58 @@ private:
     size_t cap_ = 0;
 };
 
+// The stream rule of a handle (include/midaspom.h, "Streams"): a call gives the
+// result it would give alone, whatever earlier device-form calls on the handle
+// are still pending on any stream.  A device form launches on the caller's
+// stream and returns; its kernels read -- and write -- device state the handle
+// owns (the grid's axes and tables, scratch, the look-back flag) until that
+// stream gets to them.  So:
+//   * a device form ends with launched_on(st): a flag and the stream's handle,
+//     no HIP call (no event per launch);
+//   * a device form starts with settle_unless(st): work pending on the same
+//     stream is ordered before it by the stream itself, on another stream it
+//     is waited for;
+//   * everything else that rewrites or reuses that state -- a new grid, the
+//     host forms, the timing calls on the handle's own stream -- starts with
+//     settle().
+// settle() waits for the device, not for the noted stream: the caller may have
+// destroyed that stream since, and a handle value may have been given out
+// again.  The handle's device must be current.
+struct DevPending {
+    bool pending = false;
+    hipStream_t pending_on = nullptr;
+    void launched_on(hipStream_t st) { pending = true, pending_on = st; }
+    // the host has waited for st: nothing noted there is pending any more
+    void waited_for(hipStream_t st)
+    {
+        if (pending && pending_on == st) pending = false;
+    }
+    int settle()
+    {
+        if (!pending) return MDP_OK;
+        HIP_TRY(hipDeviceSynchronize());
+        pending = false;
+        return MDP_OK;
+    }
+    int settle_unless(hipStream_t st) { return pending && pending_on != st ? settle() : MDP_OK; }
+};
+
 // The device, stream and timing events of a handle, as the BASE of the struct
 // that holds its DevBufs.  The release order is by declaration: the handle's
-// destructor body calls drain() (the device current, the stream drained), then
-// its members go (the buffers), then this base (the events, the stream).
-struct DevQueue {
+// destructor body calls drain() (the device current, pending device forms and
+// the stream waited for), then its members go (the buffers), then this base
+// (the events, the stream).
+struct DevQueue : DevPending {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevQueue() = default;
     DevQueue(const DevQueue &) = delete;
     DevQueue &operator=(const DevQueue &) = delete;
-    void drain() const
+    void drain()
     {
         (void)hipSetDevice(device);
+        (void)settle();
         if (stream) (void)hipStreamSynchronize(stream);
     }
     ~DevQueue()

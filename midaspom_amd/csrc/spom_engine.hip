@@ -62,8 +62,9 @@ struct LaunchNote {
 // The handles of a device context, as the BASE of DevCtx, which holds the
 // buffers.  The release order is by declaration: ~DevCtx's body makes the
 // device current, then DevCtx's members go (the buffers), then this base: the
-// events, the modules, the stream.
-struct DevHandles {
+// events, the modules, the stream.  (DevPending: the device forms still
+// pending on a caller's stream, spom_dev.h.)
+struct DevHandles : DevPending {
     int device = 0;
     hipStream_t stream = nullptr;
     // problem-specialised forward kernel [variant]: 0 reading, 1 fused, 2
@@ -131,7 +132,11 @@ struct DevCtx : DevHandles {
     DevBuf<uint4> hs_wplan, hs_pass;  // (hs_*: k_fwd_hs tables)
     std::vector<uint8_t> ev_mask;  // per profiled run: slots whose kernel was launched
     size_t ev_used = 0;          // event sets recorded since the last collect
-    ~DevCtx() { (void)hipSetDevice(device); }
+    ~DevCtx()
+    {
+        (void)hipSetDevice(device);
+        (void)settle();
+    }
 };
 
 struct mdp_engine : MdpEnginePlan {
@@ -2535,11 +2540,16 @@ int qrows_attrs(const mdp_engine *eng, DevCtx &d)
 
 // A new grid: plan it on the host (mdp_plan_grid: the refusals, the kernel
 // variant, the point list, the chunk widths, every buffer size), then grow
-// and upload what the plan says and load the forward kernel it names.
+// and upload what the plan says and load the forward kernel it names.  The
+// uploads are synchronous copies and a memset on the null stream, which
+// nothing orders against a caller's non-blocking stream: a mdp_engine_run
+// still pending there is waited for first (settle), or it would read this
+// grid's axes, point list and tables.
 int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const double *c,
                  uint32_t nc)
 {
     HIP_TRY(hipSetDevice(d.device));
+    if (int prc = d.settle()) return prc;
     if (!d.ncu && eng->jit && !eng->wide) {
         int v = 0;
         d.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && v > 0
@@ -2895,6 +2905,22 @@ int time_kernels(mdp_engine *eng, DevCtx &d, double *out, OutStrides os, hipStre
     return rc;
 }
 
+// A device form on the caller's stream st (spom_dev.h, the stream rule): a run
+// still pending on another stream shares this one's scratch (Q rows, Z, the
+// wide path's state vectors) and is waited for; on the same stream the stream
+// orders them.  Whatever `launch` queued is noted as pending, after an error
+// too.  No HIP call when nothing is pending elsewhere.
+template <typename F>
+int run_pending(DevCtx &d, hipStream_t st, F launch)
+{
+    if (d.pending && d.pending_on != st) {
+        HIP_TRY(hipSetDevice(d.device));
+        if (int rc = d.settle()) return rc;
+    }
+    d.launched_on(st);
+    return launch();
+}
+
 // Mean kernel durations over every profiled run since the last collect.
 int collect_times(mdp_engine *eng, DevCtx &d)
 {
@@ -3033,7 +3059,9 @@ int mdp_engine_run(mdp_engine *eng, double *d_out, uint32_t ld_out, void *stream
                              eng->layout == MDP_LAYOUT_CE ? d.ne : d.nc);
     // the caller's stream as given: NULL is HIP's null stream (torch's default
     // stream), never the engine's private non-blocking stream
-    return run_dev(eng, d, d_out, layout_strides(eng->layout, ld_out), (hipStream_t)stream);
+    return run_pending(d, (hipStream_t)stream, [&]() {
+        return run_dev(eng, d, d_out, layout_strides(eng->layout, ld_out), (hipStream_t)stream);
+    });
 }
 
 int mdp_loglik_grid(mdp_engine *eng, const double *e, uint32_t ne, const double *c, uint32_t nc,
@@ -3196,7 +3224,9 @@ int mdp_engine_time_kernels(mdp_engine *eng, double *d_out, uint32_t ld_out, voi
     double t[3];
     const int saved = eng->profiling;
     eng->profiling = 0;
-    int rc = time_kernels(eng, d, d_out, layout_strides(eng->layout, ld_out), (hipStream_t)stream, reps, t);
+    int rc = run_pending(d, (hipStream_t)stream, [&]() {
+        return time_kernels(eng, d, d_out, layout_strides(eng->layout, ld_out), (hipStream_t)stream, reps, t);
+    });
     eng->profiling = saved;
     if (rc) return rc;
     const int k = std::min(max_k, 3);

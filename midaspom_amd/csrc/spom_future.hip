@@ -702,6 +702,12 @@ __global__ __launch_bounds__(256) void k_future_split(const unsigned long long *
 
 }  // namespace
 // (DevQueue: the device, stream and events, released after the buffers below)
+// The stream rule (spom_dev.h): no grid is uploaded here, but the partial
+// counts, the summary table, the replicate records and the device forms'
+// look-back flag (dpartial, dtab, drec_*, derr[0]) are one set per engine,
+// shared by every call.  A device form notes the caller's stream and waits for
+// one pending on another stream; the host forms and the timing calls, which
+// run on the engine's own stream, wait for whatever is pending.
 struct mdp_future : DevQueue {
     uint32_t n = 0, nm = 0, nmiss = 0, necstep = 0, lvalid = 0;
     uint64_t occ0 = 0;
@@ -1081,6 +1087,7 @@ int mdp_future_states(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep
     if (!words) return mdp_set_error(MDP_EINVAL, "null states");
     HIP_TRY(hipSetDevice(f->device));
     int rc;
+    if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if ((rc = f->dstates.grow((size_t)nrep * 64))) return rc;
     HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
@@ -1109,7 +1116,9 @@ int mdp_future_simulate_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint
     if (!d_counts) return mdp_set_error(MDP_EINVAL, "null device counts");
     HIP_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
+    if ((rc = f->settle_unless(st))) return rc;
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
+    f->launched_on(st);
     // the look-back overflow flag is sticky: mdp_future_check reads and
     // clears it, so one check covers every launch since the previous check
     return fut_launch(f, seed, rep0, nrep, tfut, (unsigned long long *)d_counts, st, true, f->derr.get());
@@ -1120,10 +1129,14 @@ int mdp_future_check(mdp_future *f, void *stream)
     if (!f) return mdp_set_error(MDP_EINVAL, "null future engine");
     HIP_TRY(hipSetDevice(f->device));
     hipStream_t st = (hipStream_t)stream;
+    // (the launches it covers are those on st; one pending elsewhere is waited
+    // for, so that its flag is read too rather than cleared under it)
+    if (int rc = f->settle_unless(st)) return rc;
     uint32_t err = 0;
     HIP_TRY(hipMemcpyAsync(&err, f->derr.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemsetAsync(f->derr.get(), 0, sizeof(uint32_t), st));
     HIP_TRY(hipStreamSynchronize(st));
+    f->waited_for(st);
     return fut_lookback(err, true);
 }
 
@@ -1134,6 +1147,7 @@ int mdp_future_simulate(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nr
     if (rc) return rc;
     if (!counts) return mdp_set_error(MDP_EINVAL, "null counts");
     HIP_TRY(hipSetDevice(f->device));
+    if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     if (nrep == 0) return MDP_OK;
     HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
@@ -1154,6 +1168,7 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     HIP_TRY(hipSetDevice(f->device));
+    if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
     return fut_time(f, reps, ms, [&]() {
         return fut_launch(f, seed, 0, nrep, tfut, f->dcounts.get(), f->stream, false, f->derr.get() + 1);
@@ -1168,6 +1183,8 @@ int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint6
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
+    if ((rc = f->settle_unless(st))) return rc;
+    f->launched_on(st);
     // the sticky look-back flag of the device path (mdp_future_check)
     if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, st, f->derr.get()))) return rc;
     const uint32_t ncell = tfut * (2 * f->n + 1);
@@ -1185,6 +1202,7 @@ int mdp_future_summary(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nre
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (nrep == 0) return MDP_OK;
+    if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     HIP_TRY(hipMemsetAsync(f->derr.get() + 1, 0, sizeof(uint32_t), f->stream));
     if ((rc = fut_summary_run(f, p, seed, rep0, nrep, tfut, f->stream, f->derr.get() + 1))) return rc;
     const uint32_t n = f->n, cells = 2 * n + 1;
@@ -1208,6 +1226,7 @@ int mdp_future_time_summary(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_
     int rc = fut_summary_prepare(f, nrep, tfut, &p);
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
+    if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     return fut_time(f, reps, ms, [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr.get() + 1); });
 }
 

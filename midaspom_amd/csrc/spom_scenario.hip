@@ -798,7 +798,11 @@ int mdp_scenario_set_grid(mdp_scenario *sc, int ts, int tdis, const double *e, u
     ScnGrid g;
     if (int rc = scn_grid_plan(sc->plan, ts, tdis, e, ne, c, nc, K, nK, dsrc, nd, &g)) return rc;
     HIP_TRY(hipSetDevice(sc->device));
-    HIP_TRY(hipStreamSynchronize(sc->stream));  // no launch still reads the buffers
+    // The uploads below are synchronous copies on the null stream, which
+    // nothing orders against a caller's non-blocking stream: a
+    // mdp_scenario_run still pending there is waited for (spom_dev.h, the
+    // stream rule).  The host form leaves nothing behind on sc->stream.
+    if (int rc = sc->settle()) return rc;
     sc->grid = ScnGrid();  // no grid until this one is whole
     sc->grid.ts = ts, sc->grid.tdis = tdis;
     if (!g.ne) return MDP_OK;
@@ -816,6 +820,10 @@ int mdp_scenario_run(mdp_scenario *sc, double *d_out, void *stream)
     if (!sc->grid.ne) return MDP_OK;
     if (!d_out) return mdp_set_error(MDP_EINVAL, "null device output");
     HIP_TRY(hipSetDevice(sc->device));
+    // a run pending on another stream shares v (and k_scn_big's scratch): waited
+    // for; on this stream the stream orders them.  No HIP call otherwise.
+    if (int rc = sc->settle_unless((hipStream_t)stream)) return rc;
+    sc->launched_on((hipStream_t)stream);
     return scn_launch(sc, d_out, (hipStream_t)stream, 3);
 }
 
@@ -825,6 +833,8 @@ int mdp_scenario_time_kernels(mdp_scenario *sc, double *d_out, void *stream, int
     if (!sc->grid.ne) return mdp_set_error(MDP_EINVAL, "no grid set");
     HIP_TRY(hipSetDevice(sc->device));
     hipStream_t st = (hipStream_t)stream;
+    if (int rc = sc->settle_unless(st)) return rc;
+    sc->launched_on(st);
     if (!sc->ev0) HIP_TRY(hipEventCreate(&sc->ev0));
     if (!sc->ev1) HIP_TRY(hipEventCreate(&sc->ev1));
     int rc = scn_launch(sc, d_out, st, 3);
@@ -839,6 +849,7 @@ int mdp_scenario_time_kernels(mdp_scenario *sc, double *d_out, void *stream, int
         HIP_TRY(hipEventElapsedTime(&t, sc->ev0, sc->ev1));
         ms[which - 1] = (double)t / reps;
     }
+    sc->waited_for(st);  // (the last event: everything queued on st is done)
     return MDP_OK;
 }
 

@@ -478,8 +478,12 @@ struct SimGrid {
 size_t sim_src_at(const SimGrid &gr) { return ((size_t)gr.ne + gr.nc + gr.nK + 1) & ~(size_t)1; }
 
 // the axes and the source rows into s->dgrid: [e | c | K | (pad) | src[nd][ld]].
-// `st` is drained first, so that no launch still reads the buffer.
-int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
+// The copy is synchronous on the null stream, which nothing orders against a
+// caller's non-blocking stream: a device form still pending -- on the stream of
+// this call or on any other -- reads the buffer and is waited for first
+// (spom_dev.h, the stream rule).  The host forms leave nothing behind on
+// s->stream.
+int sim_upload(mdp_scenario_sim *s, const SimGrid &gr)
 {
     std::vector<double> src;
     sim_src(s->plan, gr.dsrc, gr.nd, &src);
@@ -490,7 +494,7 @@ int sim_upload(mdp_scenario_sim *s, const SimGrid &gr, hipStream_t st)
     h.insert(h.end(), gr.K, gr.K + gr.nK);
     h.resize(sim_src_at(gr), 0.0);
     h.insert(h.end(), src.begin(), src.end());
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = s->settle()) return rc;
     return s->dgrid.assign(h);
 }
 
@@ -605,7 +609,8 @@ int mdp_scenario_sim_tables_device(mdp_scenario_sim *s, int ts, int tdis, const 
     if (int rc = sim_device(s)) return rc;
     hipStream_t st = (hipStream_t)stream;  // as given: NULL is HIP's null stream
     const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
-    if (int rc = sim_upload(s, gr, st)) return rc;
+    if (int rc = sim_upload(s, gr)) return rc;
+    s->launched_on(st);
     if (d_hist) HIP_TRY(hipMemsetAsync(d_hist, 0, call.hist_cells * sizeof(uint64_t), st));
     if (d_match) HIP_TRY(hipMemsetAsync(d_match, 0, call.match_cells * sizeof(uint64_t), st));
     return sim_launch(s, call, gr, seed, rep0, nrep, (unsigned long long *)d_hist, (unsigned long long *)d_match, st);
@@ -636,6 +641,7 @@ int mdp_scenario_sim_tables(mdp_scenario_sim *s, int ts, int tdis, const double 
     if (match)
         HIP_TRY(hipMemcpyAsync(hm.data(), s->dmatch.get(), hm.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    s->waited_for(s->stream);
     for (size_t i = 0; i < hh.size(); ++i) hist[i] += hh[i];
     for (size_t i = 0; i < hm.size(); ++i) match[i] += hm[i];
     return MDP_OK;
@@ -661,7 +667,7 @@ int mdp_scenario_sim_time_kernel(mdp_scenario_sim *s, int ts, int tdis, const do
     if (want_match)
         if (int rc = s->dmatch.grow((size_t)call.match_cells)) return rc;
     const SimGrid gr{ts, tdis, e, c, K, dsrc, ne, nc, nK, nd};
-    if (int rc = sim_upload(s, gr, s->stream)) return rc;
+    if (int rc = sim_upload(s, gr)) return rc;
     HIP_TRY(hipMemsetAsync(s->dhist.get(), 0, call.hist_cells * sizeof(uint64_t), s->stream));
     if (want_match) HIP_TRY(hipMemsetAsync(s->dmatch.get(), 0, call.match_cells * sizeof(uint64_t), s->stream));
     auto launch = [&]() {
