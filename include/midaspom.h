@@ -17,14 +17,15 @@
  *  - an engine is not re-entrant; one host thread drives all its devices;
  *  - Streams.  The device forms (mdp_engine_run, mdp_scenario_run,
  *    mdp_future_simulate_device / _summary_device with mdp_future_check,
- *    mdp_scenario_sim_tables_device, the two *_time_kernels) launch on the
- *    caller's stream and return; what the caller queues on that stream
- *    afterwards is ordered after them.  A call on a handle gives the result
+ *    mdp_scenario_sim_tables_device, mdp_scenario_chain_lik_device, the two
+ *    *_time_kernels) launch on the caller's stream and return; what the
+ *    caller queues on that stream afterwards is ordered after them.  A call on a handle gives the result
  *    it would give alone, whatever earlier device-form calls on that handle
  *    are still pending on any stream.  Only the caller's output buffers are
  *    the caller's to order.  A call that rewrites or reuses device state a
  *    pending launch may read -- a new grid (mdp_engine_set_grid,
- *    mdp_scenario_set_grid, every mdp_scenario_sim_tables* call), a host form,
+ *    mdp_scenario_set_grid, every mdp_scenario_sim_tables* and
+ *    mdp_scenario_chain_* computing call), a host form,
  *    a device form on a stream other than the pending one -- first waits for
  *    the device; a device form behind another on the same stream does not
  *    wait and makes no extra HIP call.  A stream need not outlive the work it
@@ -536,6 +537,113 @@ int mdp_scenario_sim_lik(const mdp_scenario_sim *sim, const uint64_t *match, siz
 int mdp_scenario_sim_time_kernel(mdp_scenario_sim *sim, int ts, int tdis, const double *e, uint32_t ne,
                                  const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
                                  uint32_t nd, uint64_t seed, uint64_t nrep, int reps, double *ms);
+
+/* ------------------------------------------------------------------ */
+/* Count-class chain likelihoods for rows of up to 64 patches           */
+/* (Rscript/simuls_traj.R, simtrajH11 / simtrajH21)                     */
+/* ------------------------------------------------------------------ */
+
+/* Also added after ABI 9 without a version bump.  The estimator behind the
+ * reference's 26-segment figures: instead of whole trajectories, ONE simulated
+ * year from a random start with exactly k occupied patches, for every class
+ * k = 0..n, tallied into the (n+1) x (n+1) matrix of transitions between
+ * occupied-count classes -- A for a scenario year, B for a baseline year --
+ * and the likelihood read off the matrix powers,
+ *   out[g] = sum_k start[k] [A_g^ts B^tdis target]_k,
+ * which carry probabilities far below 1/nrep.  Lumping the 2^n states into
+ * n+1 classes is exact when the patches are exchangeable (d = 0, and for loss
+ * a source at distance 0) and an approximation otherwise.  Unlike
+ * the R script, class 0 is simulated like every other class: under habitat
+ * loss the source recolonises an empty row.
+ *
+ * The replicate model, per table (scenario: points g = ((ie*nc + ic)*nK +
+ * iK)*nd + id; baseline: g = ie*nc + ic), class k and replicate rg = rep0 + r:
+ *   start state  exactly k patches by selection sampling: need = k; for
+ *                j = 0..n-1 ascending, u_j = word j & 3 of philox(seed;
+ *                rg_lo, rg_hi, 0xfffffffe, 16*k + (j >> 2)); patch j is
+ *                occupied iff ((uint64)u_j * (n - j)) >> 32 < need, and then
+ *                need -= 1.  Counter word 2 = 0xfffffffe meets neither a
+ *                year's draws (word 2 = t <= 12287) nor the initial states of
+ *                the simulator and the future engine (0xffffffff).
+ *   one year     the simulator's year with year word t = k: pair m =
+ *                patch >> 1 draws philox(seed; rg_lo, rg_hi, k, m), words
+ *                2(p&1) and 2(p&1)+1 the extinction and colonisation draws.
+ *                The classes use disjoint draws; the grid point is not in
+ *                the counter, so every point shares its replicates.
+ *   rates        scenario table: mdp_scenario_sim's scenario year (die-off
+ *                E = min(1, e/K), pC = (c s1) K; loss E = min(1, e), pC =
+ *                c (s1 + src K)); baseline table: E = min(1, e), pC = c s1.
+ *   tally        cnt[(g*(n+1) + k)*(n+1) + l] += 1, l the number of occupied
+ *                patches after the year.
+ * No count depends on how replicates, classes or points are split over calls,
+ * launches, workgroups or GPUs, nor on the kernel instantiation.
+ *
+ * The evaluation, with a[k][l] = (double)cnt_scn / (double)nrep and b[k][l] =
+ * (double)cnt_base / (double)nbase: v = target; tdis times v'[k] = sum_l
+ * b[k][l] v[l]; ts times v'[k] = sum_l a[k][l] v[l]; by_class[g][k] = v[k];
+ * out[g] = sum_k start[k] v[k].  Every sum ascending from 0.0, each product
+ * rounded before its add.  Defaults (NULL): start[k] = 1/(n+1), the script's
+ * mean(Pf[, m+1]); target[n1 + j] = (C(nmiss, j) p^j) (1-p)^(nmiss-j) with p
+ * = (double)(float)p, n1 the observed 1s and nmiss the -1s of the row.
+ * start[k] = C(n, k) is the weighting under which exchangeable patches
+ * reproduce sum over the rows with the target's count of mdp_scenario_lik.
+ *
+ * create: row, n, m, p, d, kind, device as mdp_scenario_sim_create; 1 <= n <=
+ * 64.  No device call is made before the first computing call, and every
+ * refusal of every call comes before its first device call.  Options (test
+ * hooks; no result depends on them):
+ *   MDP_CHAIN_NM=8|16|32|64   the instantiation k_scnchain<NM>, at least the
+ *                             one n needs; smaller: MDP_EINVAL
+ *   MDP_CHAIN_LAUNCH_PTS=N    grid points per launch (0: the planner's cut,
+ *                             a device count table of at most 256 MiB)
+ *   MDP_CHAIN_PARTS=N         workgroups that share a grid point, each
+ *                             flushing its own tally (0: the planner's choice)
+ * Refusals: MDP_EINVAL for n = 0, a row value outside {-1, 0, 1}, an unknown
+ * option name or value, ts < 0 or tdis < 0, a negative or non-finite e, c or
+ * dsrc, a K that is not finite and > 0, a negative or non-finite weight,
+ * nrep = 0 or nbase = 0 in eval / lik; MDP_EUNSUPPORTED for n > 64, ts + tdis >
+ * 12288, more than 2^20 grid points, nrep or nbase > 2^31, and for counts a
+ * table of more than 2^24 cells. */
+typedef struct mdp_scenario_chain mdp_scenario_chain;
+int mdp_scenario_chain_create(const int32_t *row, uint32_t n, double m, float p, double d, int kind, int device,
+                              const char *options, mdp_scenario_chain **out);
+void mdp_scenario_chain_destroy(mdp_scenario_chain *chain);
+/* "k_scnchain<32>" (owned by the engine) */
+const char *mdp_scenario_chain_kernel(const mdp_scenario_chain *chain);
+/* the default target[n+1] */
+int mdp_scenario_chain_target(const mdp_scenario_chain *chain, double *target);
+/* cnt += the counts of replicates [rep0, rep0 + nrep) per class: the scenario
+ * table [ne*nc*nK*nd][n+1][n+1], or (baseline != 0; K, nK, dsrc and nd are
+ * ignored) the baseline table [ne*nc][n+1][n+1].  Host memory, 64-bit counts. */
+int mdp_scenario_chain_counts(mdp_scenario_chain *chain, int baseline, const double *e, uint32_t ne, const double *c,
+                              uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd, uint64_t seed,
+                              uint64_t rep0, uint64_t nrep, uint64_t *cnt);
+/* The evaluation on host tables of nrep and nbase replicates per class:
+ * out[ne*nc*nK*nd], by_class[ne*nc*nK*nd][n+1] (may be NULL).  Host
+ * arithmetic: no device call. */
+int mdp_scenario_chain_eval(const mdp_scenario_chain *chain, int ts, int tdis, uint32_t ne, uint32_t nc, uint32_t nK,
+                            uint32_t nd, const uint64_t *cnt_scn, uint64_t nrep, const uint64_t *cnt_base,
+                            uint64_t nbase, const double *start, const double *target, double *out, double *by_class);
+/* Counts (rep0 = 0) and evaluation on the device, the result in host memory:
+ * the bits mdp_scenario_chain_eval returns on mdp_scenario_chain_counts'
+ * tables.  The count tables stay on the device, cut into launches. */
+int mdp_scenario_chain_lik(mdp_scenario_chain *chain, int ts, int tdis, const double *e, uint32_t ne, const double *c,
+                           uint32_t nc, const double *K, uint32_t nK, const double *dsrc, uint32_t nd, uint64_t seed,
+                           uint64_t nrep, uint64_t nbase, const double *start, const double *target, double *out,
+                           double *by_class);
+/* Same into caller-owned device memory d_out[ne*nc*nK*nd] (overwritten); the
+ * launches are asynchronous on `stream` (NULL = HIP's null stream), after the
+ * grid has been uploaded -- which waits for the device when an earlier
+ * device-form call of this engine is still pending (Conventions, Streams). */
+int mdp_scenario_chain_lik_device(mdp_scenario_chain *chain, int ts, int tdis, const double *e, uint32_t ne,
+                                  const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
+                                  uint32_t nd, uint64_t seed, uint64_t nrep, uint64_t nbase, const double *start,
+                                  const double *target, double *d_out, void *stream);
+/* Mean durations (ms) over `reps` runs: ms[0] the baseline counts, ms[1] the
+ * scenario counts (each with its table's reset), ms[2] both evaluations. */
+int mdp_scenario_chain_time_kernels(mdp_scenario_chain *chain, int ts, int tdis, const double *e, uint32_t ne,
+                                    const double *c, uint32_t nc, const double *K, uint32_t nK, const double *dsrc,
+                                    uint32_t nd, uint64_t seed, uint64_t nrep, uint64_t nbase, int reps, double *ms);
 
 /* Thread-local description of the last error. */
 const char *mdp_last_error(void);

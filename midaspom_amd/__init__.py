@@ -28,7 +28,7 @@ __all__ = [
     "Model", "Engine", "grid", "log_total", "write_posterior", "posterior",
     "run_file", "MidaspomError", "Scenario", "kgrid", "dgrid", "first_row",
     "Future", "read_survey", "read_posterior", "device_count", "quasi_extinction", "mean_occupied",
-    "ScenarioSim", "count_likelihood",
+    "ScenarioSim", "count_likelihood", "ScenarioChain",
 ]
 
 
@@ -541,6 +541,163 @@ class ScenarioSim:
         ms = ctypes.c_double()
         check(lib().mdp_scenario_sim_time_kernel(self._h, ts, tdis, *args, seed, nrep, reps, ctypes.byref(ms)))
         return ms.value
+
+
+class ScenarioChain:
+    """The two scenario hypotheses through the chain of occupied-count classes
+    (``mdp_scenario_chain``, Rscript/simuls_traj.R simtrajH11 / simtrajH21),
+    for first survey rows of up to 64 patches: one simulated year from a
+    random start with exactly k occupied patches, for every k, tallied into
+    (n+1) x (n+1) transition counts -- a scenario table per grid point, a
+    baseline table per (e, c) -- and ``L = start . A^ts B^tdis target``.
+
+    ``options``: the test hooks ``MDP_CHAIN_NM`` = 8 | 16 | 32 | 64,
+    ``MDP_CHAIN_LAUNCH_PTS`` = N (grid points per launch) and
+    ``MDP_CHAIN_PARTS`` = N (workgroups per grid point); no result depends on
+    them.  Creating the object makes no device call."""
+
+    def __init__(self, row, kind: str = "dieoff", m: float = 400.0, p: float = 0.5, d: float = 200.0,
+                 device: int = 0, options=None):
+        if kind not in ("dieoff", "loss"):
+            raise ValueError("kind must be 'dieoff' or 'loss'")
+        self.kind = kind
+        row = np.ascontiguousarray(row, dtype=np.int32)
+        self.n = int(row.size)
+        h = ctypes.c_void_p()
+        opts = _lib.options_string(options, _lib.SCENARIO_CHAIN_OPTION_NAMES)
+        check(lib().mdp_scenario_chain_create(row.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), row.size, m, p, d,
+                                              1 if kind == "loss" else 0, device, opts, ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def kernel(self) -> str:
+        """Name of the counting kernel, e.g. ``k_scnchain<32>``."""
+        return lib().mdp_scenario_chain_kernel(self._h).decode()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mdp_scenario_chain_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    _grid = ScenarioSim._grid
+
+    def target(self) -> np.ndarray:
+        """The default target weights [n+1]: the distribution of the row's
+        occupied count, its missing patches independent with prior p."""
+        out = np.empty(self.n + 1)
+        check(lib().mdp_scenario_chain_target(self._h, _dptr(out)))
+        return out
+
+    def _weights(self, start, target):
+        """(start, target) as float64 arrays or None (the defaults)."""
+        if isinstance(start, str):
+            if start == "uniform":
+                start = None
+            elif start == "states":
+                import math
+                start = [float(math.comb(self.n, k)) for k in range(self.n + 1)]
+            else:
+                raise ValueError("start must be 'uniform', 'states' or n+1 weights")
+        out = []
+        for w in (start, target):
+            if w is not None:
+                w = np.ascontiguousarray(w, dtype=np.float64)
+                if w.shape != (self.n + 1,):
+                    raise ValueError(f"weights must have shape ({self.n + 1},)")
+            out.append(w)
+        return out
+
+    def counts(self, e, c, K=None, dsrc=None, nrep: int = 1000, seed: int = 0, rep0: int = 0, baseline: bool = False,
+               out=None) -> np.ndarray:
+        """uint64 transition counts of replicates [rep0, rep0 + nrep) per
+        class: grid + (n+1, n+1), grid = (ne, nc, nK[, nd]) for the scenario
+        table and (ne, nc) for the baseline table (K and dsrc ignored).  A
+        table passed as ``out`` is added to."""
+        if baseline:
+            K, dsrc = 1.0, (0.0 if self.kind == "loss" else None)
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        if baseline:
+            shape = shape[:2]
+        full = shape + (self.n + 1, self.n + 1)
+        if out is None:
+            out = np.zeros(full, dtype=np.uint64)
+        elif out.dtype != np.uint64 or out.shape != full or not out.flags.c_contiguous:
+            raise ValueError(f"table must be a C-contiguous uint64 array of shape {full}")
+        check(lib().mdp_scenario_chain_counts(self._h, int(bool(baseline)), *args, seed, rep0, nrep,
+                                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
+
+    def eval(self, cnt_scn, nrep: int, cnt_base, nbase: int, ts: int = 20, tdis: int = 10, start="uniform",
+             target=None, by_class: bool = False):
+        """The chain evaluation on host tables (no device call): ``lik`` of
+        shape cnt_scn.shape[:-2], or (lik, by_class[..., n+1])."""
+        cnt_scn = np.ascontiguousarray(cnt_scn, dtype=np.uint64)
+        cnt_base = np.ascontiguousarray(cnt_base, dtype=np.uint64)
+        shape = cnt_scn.shape[:-2]
+        if cnt_base.shape != shape[:2] + cnt_scn.shape[-2:] or cnt_scn.shape[-2:] != (self.n + 1, self.n + 1):
+            raise ValueError("count tables must have shapes grid + (n+1, n+1) and (ne, nc, n+1, n+1)")
+        dims = tuple(shape) + (1,) * (4 - len(shape))
+        ws, wt = self._weights(start, target)
+        out = np.empty(shape)
+        by = np.empty(shape + (self.n + 1,)) if by_class else None
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        check(lib().mdp_scenario_chain_eval(self._h, ts, tdis, *dims, cnt_scn.ctypes.data_as(u64p), nrep,
+                                            cnt_base.ctypes.data_as(u64p), nbase,
+                                            _dptr(ws) if ws is not None else None,
+                                            _dptr(wt) if wt is not None else None, _dptr(out),
+                                            _dptr(by) if by is not None else None))
+        return (out, by) if by_class else out
+
+    def lik(self, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10, nrep: int = 1000, nbase: int = 100000,
+            seed: int = 0, start="uniform", target=None, by_class: bool = False):
+        """Counts and evaluation on the device: ``lik`` of the grid's shape,
+        or (lik, by_class[..., n+1]).  ``start``: "uniform" (1/(n+1), the R
+        script's mean over start classes), "states" (C(n, k): every one of
+        the 2^n start states once, the exact engine's weighting) or n+1
+        weights; ``target``: n+1 weights (None: ``target()``)."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        ws, wt = self._weights(start, target)
+        out = np.empty(shape)
+        by = np.empty(shape + (self.n + 1,)) if by_class else None
+        check(lib().mdp_scenario_chain_lik(self._h, ts, tdis, *args, seed, nrep, nbase,
+                                           _dptr(ws) if ws is not None else None,
+                                           _dptr(wt) if wt is not None else None, _dptr(out),
+                                           _dptr(by) if by is not None else None))
+        return (out, by) if by_class else out
+
+    def lik_device(self, d_out: int, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10, nrep: int = 1000,
+                   nbase: int = 100000, seed: int = 0, start="uniform", target=None, stream: int = 0) -> tuple:
+        """Into device memory at ``d_out`` (float64, the grid's shape),
+        overwritten, the launches asynchronous on hipStream ``stream``.
+        Returns the grid shape."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        ws, wt = self._weights(start, target)
+        check(lib().mdp_scenario_chain_lik_device(self._h, ts, tdis, *args, seed, nrep, nbase,
+                                                  _dptr(ws) if ws is not None else None,
+                                                  _dptr(wt) if wt is not None else None, ctypes.c_void_p(d_out or None),
+                                                  ctypes.c_void_p(stream)))
+        return shape
+
+    def time_kernels(self, e, c, K, dsrc=None, ts: int = 20, tdis: int = 10, nrep: int = 1000, nbase: int = 100000,
+                     seed: int = 0, reps: int = 5) -> dict:
+        """Mean ms over ``reps`` runs of the baseline counts, the scenario
+        counts and the two evaluations."""
+        args, shape, keep = self._grid(e, c, K, dsrc)
+        ms = (ctypes.c_double * 3)()
+        check(lib().mdp_scenario_chain_time_kernels(self._h, ts, tdis, *args, seed, nrep, nbase, reps, ms))
+        return {"base_counts": ms[0], "scn_counts": ms[1], "eval": ms[2]}
 
 
 def count_likelihood(hist, m_obs: int) -> np.ndarray:

@@ -201,6 +201,25 @@ SIGNATURES = [
      [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_uint64, c_dbl_p]),
     ("mdp_scenario_sim_time_kernel", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
      [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, c_dbl_p]),
+    # the scenario chain (also after ABI 9 without a version bump)
+    ("mdp_scenario_chain_create", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int32), ctypes.c_uint32, ctypes.c_double, ctypes.c_float, ctypes.c_double,
+      ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]),
+    ("mdp_scenario_chain_destroy", None, [ctypes.c_void_p]),
+    ("mdp_scenario_chain_kernel", ctypes.c_char_p, [ctypes.c_void_p]),
+    ("mdp_scenario_chain_target", ctypes.c_int, [ctypes.c_void_p, c_dbl_p]),
+    ("mdp_scenario_chain_counts", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    ("mdp_scenario_chain_eval", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+      ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, c_dbl_p,
+      c_dbl_p, c_dbl_p, c_dbl_p]),
+    ("mdp_scenario_chain_lik", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    ("mdp_scenario_chain_lik_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, c_dbl_p, c_dbl_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("mdp_scenario_chain_time_kernels", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + _SIM_GRID +
+     [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, c_dbl_p]),
 ]
 
 _lib = None
@@ -246,6 +265,7 @@ ENGINE_OPTION_NAMES = (
 SCENARIO_OPTION_NAMES = ("MDP_SCN_BIG", "MDP_SCN_ROW", "MDP_SCN_LAUNCH_PTS")
 FUTURE_OPTION_NAMES = ("MDP_FUT_WIDE",)
 SCENARIO_SIM_OPTION_NAMES = ("MDP_SIM_NM", "MDP_SIM_LAUNCH_PTS", "MDP_SIM_WAVE", "MDP_SIM_NP")
+SCENARIO_CHAIN_OPTION_NAMES = ("MDP_CHAIN_NM", "MDP_CHAIN_LAUNCH_PTS", "MDP_CHAIN_PARTS")
 
 
 DIAG_OPTION_NAMES = ("MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE")

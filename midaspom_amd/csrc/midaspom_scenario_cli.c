@@ -24,6 +24,13 @@
  * final occupied-patch counts, one line per grid point in output order, n+1
  * "%llu\t" values.  All grid points share their replicates, so the files do
  * not depend on -g.  Without -R nothing changes.
+ *
+ * Extension: -C <nbase> with -R <nrep> writes the count-class chain likelihood
+ * instead (mdp_scenario_chain, Rscript/simuls_traj.R simtrajH11 / simtrajH21):
+ * one simulated year per replicate and start class, nrep replicates per class
+ * for every grid point's scenario year, nbase for the baseline year, default
+ * start and target weights, -r the seed; rows of up to 64 patches, no -H.
+ * Same file layout, the same bytes for every -g.  Without -C nothing changes.
  */
 #include <ctype.h>
 #include <math.h>
@@ -49,6 +56,7 @@ struct slab {
     const double *K, *dv;
     double *L;
     unsigned long long nrep, seed; /* -R, -r: nrep > 0 selects the simulator */
+    unsigned long long nbase;      /* -C: nbase > 0 selects the chain instead */
     uint64_t *H;                   /* -H: [nK*nd][n+1] or NULL */
     int rc;
     char err[256];
@@ -57,6 +65,16 @@ struct slab {
 static void *run_slab(void *arg)
 {
     struct slab *sl = arg;
+    if (sl->nbase) {
+        mdp_scenario_chain *ch = NULL;
+        sl->rc = mdp_scenario_chain_create(sl->row, sl->n, sl->mdisp, sl->prioroc, sl->d, SCN_KIND, sl->dev, NULL, &ch);
+        if (sl->rc == MDP_OK && sl->nK)
+            sl->rc = mdp_scenario_chain_lik(ch, sl->ts, sl->tdis, &sl->eB, 1, &sl->cB, 1, sl->K, sl->nK, sl->dv, sl->nd,
+                                            sl->seed, sl->nrep, sl->nbase, NULL, NULL, sl->L, NULL);
+        if (sl->rc != MDP_OK) snprintf(sl->err, sizeof sl->err, "%s", mdp_last_error());
+        mdp_scenario_chain_destroy(ch);
+        return NULL;
+    }
     if (sl->nrep) {
         mdp_scenario_sim *sim = NULL;
         const size_t G = (size_t)sl->nK * sl->nd;
@@ -96,12 +114,12 @@ int main(int argc, char **argv)
 #if SCN_KIND == 0
     printf("------ MIDASPOM, in situ die-off hypothesis, beta version -------\n-> N. Alcala, E. M. Cole, N. A. "
            "Rosenberg <-\n");
-    const char *opts = "b:a:e:c:m:p:d:i:o:s:l:u:g:R:r:H:";
+    const char *opts = "b:a:e:c:m:p:d:i:o:s:l:u:g:R:r:H:C:";
     const char *fout = "lh_dieoff.txt";
 #else
     printf("------ MIDASPOM, habitat loss hypothesis, beta version -------\n-> N. Alcala, E. M. Cole, N. A. "
            "Rosenberg  <-\n");
-    const char *opts = "b:a:e:c:m:p:d:i:o:s:v:l:u:L:U:g:R:r:H:";
+    const char *opts = "b:a:e:c:m:p:d:i:o:s:v:l:u:L:U:g:R:r:H:C:";
     const char *fout = "lh_loss.txt";
 #endif
     int ts = 20, tdis = 0, have_a = 0, have_e = 0, have_c = 0, ngpu = 1;
@@ -110,7 +128,7 @@ int main(int argc, char **argv)
     double eB = 0, cB = 0, Kmin = 0.1, Kmax = 100.0, mdisp = 400.0, d = 200, dmin = 200, dmax = 4000;
     float prioroc = 0.5f;
     const char *fname = "input.txt", *fhist = NULL;
-    unsigned long long nrep = 0, seed = 0;
+    unsigned long long nrep = 0, seed = 0, nbase = 0;
     int c;
     opterr = 0;
     while ((c = getopt(argc, argv, opts)) != -1) {
@@ -134,6 +152,7 @@ int main(int argc, char **argv)
         case 'R': nrep = strtoull(optarg, NULL, 10); break;
         case 'r': seed = strtoull(optarg, NULL, 10); break;
         case 'H': fhist = optarg; break;
+        case 'C': nbase = strtoull(optarg, NULL, 10); break;
         case '?':
             if (optopt == 'c')
                 fprintf(stderr, "Option -%c requires an argument.\n", optopt);
@@ -148,6 +167,14 @@ int main(int argc, char **argv)
     }
     if (!have_a || !have_e || !have_c) {
         fprintf(stderr, "Options -a (years after the event), -e and -c are required.\n");
+        return 1;
+    }
+    if (nbase && !nrep) {
+        fprintf(stderr, "midaspom: -C (baseline replicates of the chain likelihood) needs -R (replicates per class)\n");
+        return 1;
+    }
+    if (nbase && fhist) {
+        fprintf(stderr, "midaspom: -H is not available with -C (the chain has no final-count table)\n");
         return 1;
     }
 #if SCN_KIND == 0
@@ -180,6 +207,10 @@ int main(int argc, char **argv)
     /* observed states and priors for the log lines (dieoff.c:205-232) */
     unsigned nm = 0;
     for (unsigned j = 0; j < n; ++j) nm += row[j] == -1;
+    if (nbase && n > 64) { /* the chain holds one 64-bit occupancy mask per replicate */
+        fprintf(stderr, "midaspom: %u patches in the first row: -C takes at most 64\n", n);
+        return 1;
+    }
     if (nrep && n > 1024) { /* the simulator's patch-parallel kernel holds 1024 patches */
         fprintf(stderr, "midaspom: %u patches in the first row: -R takes at most 1024\n", n);
         return 1;
@@ -238,7 +269,9 @@ int main(int argc, char **argv)
     time_t start, end;
     time(&start);
     printf("Starting likelihood computation\n");
-    if (nrep) printf("Simulated likelihood: %llu replicates per grid point, seed %llu\n", nrep, seed);
+    if (nbase)
+        printf("Chain likelihood: %llu replicates per class, %llu baseline replicates, seed %llu\n", nrep, nbase, seed);
+    else if (nrep) printf("Simulated likelihood: %llu replicates per grid point, seed %llu\n", nrep, seed);
     const unsigned nd = SCN_KIND == 1 ? nstepd : 1u;
     double *L = malloc((size_t)nstep * nd * sizeof(double));
     uint64_t *H = nrep && fhist ? calloc((size_t)nstep * nd * (n + 1), sizeof(uint64_t)) : NULL;
@@ -250,7 +283,7 @@ int main(int argc, char **argv)
     for (int r = 0; r < ngpu; ++r) {
         const unsigned k0 = r == 0 ? 0 : (unsigned)r * avg + rem, k1 = (unsigned)(r + 1) * avg + rem;
         sl[r] = (struct slab){row, n, k1 - k0, nd, mdisp, d, eB, cB, prioroc, ts, tdis, r, K + k0, dv,
-                              L + (size_t)k0 * nd, nrep, seed, H ? H + (size_t)k0 * nd * (n + 1) : NULL, 0, ""};
+                              L + (size_t)k0 * nd, nrep, seed, nbase, H ? H + (size_t)k0 * nd * (n + 1) : NULL, 0, ""};
     }
     {   /* slabs dealt round-robin over the visible devices */
         const int ndev = mdp_device_count() > 0 ? mdp_device_count() : 1;

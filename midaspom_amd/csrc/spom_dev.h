@@ -1,4 +1,4 @@
-// midaspom_amd/csrc/spom_dev.h -- what the four HIP units share of their host
+// midaspom_amd/csrc/spom_dev.h -- what the five HIP units share of their host
 // side: the check of a HIP call and the owning device buffer.
 #ifndef SPOM_DEV_H
 #define SPOM_DEV_H

@@ -19,6 +19,12 @@ rows of 17 to 1024 patches.  `-r seed` (default 0) keys the draws; `-H file`
 writes the final occupied-patch counts, one line per grid point (single
 process only).  Same bytes as the compiled drop-ins, for every -g and rank
 count: all grid points share their replicates.
+
+`-C nbase` with `-R nrep` writes the count-class chain likelihood instead
+(midaspom_amd.ScenarioChain, Rscript/simuls_traj.R simtrajH11 / simtrajH21):
+nrep replicates per start class of every grid point's scenario year, nbase of
+the baseline year, default start and target weights, `-r` the seed; rows of up
+to 64 patches, no `-H`.  Same layout and bytes as the compiled drop-ins.
 """
 from __future__ import annotations
 
@@ -65,6 +71,8 @@ def parse_args(kind, argv):
     ap.add_argument("-R", type=int, default=0, help="simulate: replicates per grid point (0: the exact engine)")
     ap.add_argument("-r", type=int, default=0, help="seed of the simulated likelihood")
     ap.add_argument("-H", default=None, help="with -R: file of final occupied-patch counts per grid point")
+    ap.add_argument("-C", type=int, default=0,
+                    help="with -R: the chain likelihood, this many baseline replicates per class")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl)")
     return ap.parse_args(argv)
 
@@ -95,6 +103,10 @@ def _slab(mdp, row, kind, a, K, dv, nd, device):
     """(lik[nK, nd], hist[nK, nd, n+1] or None) of one K slab on one device:
     the exact engine, or with -R the simulator."""
     d = dv if kind == "loss" else None
+    if a.C:
+        with mdp.ScenarioChain(row, kind, m=a.m, p=a.p, d=a.d, device=device) as ch:
+            lik = ch.lik(a.e, a.c, K, d, ts=a.b, tdis=a.a, nrep=a.R, nbase=a.C, seed=a.r)
+        return lik[0, 0].reshape(K.size, nd), None
     if a.R:
         with mdp.ScenarioSim(row, kind, m=a.m, p=a.p, d=a.d, device=device, options="MDP_SIM_WAVE=auto") as sim:
             hist, match = sim.tables(a.e, a.c, K, d, ts=a.b, tdis=a.a, nrep=a.R, seed=a.r, hist=bool(a.H))
@@ -164,6 +176,12 @@ def main(argv=None) -> int:
     except SystemExit:
         sys.stderr.write("Options -a (years after the event), -e and -c are required.\n")
         return 1
+    if a.C and not a.R:
+        sys.stderr.write("midaspom: -C (baseline replicates of the chain likelihood) needs -R (replicates per class)\n")
+        return 1
+    if a.C and a.H:
+        sys.stderr.write("midaspom: -H is not available with -C (the chain has no final-count table)\n")
+        return 1
     if kind == "dieoff":
         out(f"{a.b} years before increased die-off, {a.a} years after increased die-off\n")
     else:
@@ -177,6 +195,9 @@ def main(argv=None) -> int:
     n = row.size
     if a.R and a.H and mpi:
         sys.stderr.write("midaspom: -H is not available under torchrun (the counts are not gathered)\n")
+        return 1
+    if a.C and n > 64:
+        sys.stderr.write(f"midaspom: {n} patches in the first row: -C takes at most 64\n")
         return 1
     if a.R and n > 1024:
         sys.stderr.write(f"midaspom: {n} patches in the first row: -R takes at most 1024\n")
@@ -204,6 +225,8 @@ def main(argv=None) -> int:
     start = int(time.time())
     hist = None
     sim_line = f"Simulated likelihood: {a.R} replicates per grid point, seed {a.r}\n" if a.R else ""
+    if a.C:
+        sim_line = f"Chain likelihood: {a.R} replicates per class, {a.C} baseline replicates, seed {a.r}\n"
     if not mpi:
         out("Starting likelihood computation\n" + sim_line)
         lik, hist = _lik_slabs(mdp, mdist, row, kind, a, K, dv, nd)
