@@ -1,10 +1,13 @@
 // midaspom_amd/csrc/spom_dev.h -- what the five HIP units share of their host
-// side: the check of a HIP call and the owning device buffer.
+// side: the check of a HIP call, the owning device buffer, the switch over a
+// kernel template's width, and a handle's device, stream and timing events.
 #ifndef SPOM_DEV_H
 #define SPOM_DEV_H
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdint>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -113,20 +116,82 @@ struct DevPending {
     int settle_unless(hipStream_t st) { return pending && pending_on != st ? settle() : MDP_OK; }
 };
 
+// The one switch over a kernel template's width: fn(integral_constant<int, W>)
+// for the W that equals w, or the refusal `what` (a format of w) for any other.
+// (A left fold: the kernels fn names are then emitted in ascending W, the
+// order of a switch; a right fold reverses them in the code object.)
+template <int... W, typename F>
+int dev_for_width(uint32_t w, const char *what, F &&fn)
+{
+    int rc = MDP_OK;
+    if ((... || (w == (uint32_t)W && ((rc = fn(std::integral_constant<int, W>())), true)))) return rc;
+    return mdp_set_error(MDP_EINVAL, what, w);
+}
+// the lane kernels' padded patch count, and the patch pairs per lane of the
+// wave kernels
+template <typename F>
+int dev_for_padded(uint32_t nm, F &&fn)
+{
+    return dev_for_width<8, 16, 32, 64>(nm, "internal: padded patch count %u", fn);
+}
+template <typename F>
+int dev_for_pairs(uint32_t np, F &&fn)
+{
+    return dev_for_width<1, 2, 4, 8>(np, "internal: %u patch pairs per lane", fn);
+}
+
 // The device, stream and timing events of a handle, as the BASE of the struct
 // that holds its DevBufs.  The release order is by declaration: the handle's
 // destructor body calls drain() (the device current, pending device forms and
 // the stream waited for), then its members go (the buffers), then this base
-// (the events, the stream).
+// (the events, the stream).  A handle makes its first HIP call in open(); one
+// that never got there has nothing on the device, and drain() makes no HIP
+// call for it.
 struct DevQueue : DevPending {
     int device = 0;
+    bool opened = false;  // open() made the device current once: HIP calls were made for this handle
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevQueue() = default;
     DevQueue(const DevQueue &) = delete;
     DevQueue &operator=(const DevQueue &) = delete;
+    // Makes `device` current and creates what is missing of the non-blocking
+    // stream and (events) the two timing events.  The first call refuses a
+    // device that is not there (MDP_ENODEV); a call after a failed one takes
+    // up where that one stopped.
+    int open(bool events = true)
+    {
+        if (!opened) {
+            int ndev = 0;
+            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+                return mdp_set_error(MDP_ENODEV, "no HIP device available");
+            if (device < 0 || device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", device);
+        }
+        HIP_TRY(hipSetDevice(device));
+        opened = true;
+        if (!stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (events && !ev0) HIP_TRY(hipEventCreate(&ev0));
+        if (events && !ev1) HIP_TRY(hipEventCreate(&ev1));
+        return MDP_OK;
+    }
+    // the mean time in ms of `reps` runs of launch() on st, between the two
+    // events; the warm-up is the caller's
+    template <typename F>
+    int time(hipStream_t st, int reps, double *ms, F &&launch)
+    {
+        HIP_TRY(hipEventRecord(ev0, st));
+        for (int i = 0; i < reps; ++i)
+            if (int rc = launch()) return rc;
+        HIP_TRY(hipEventRecord(ev1, st));
+        HIP_TRY(hipEventSynchronize(ev1));
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, ev0, ev1));
+        *ms = (double)t / reps;
+        return MDP_OK;
+    }
     void drain()
     {
+        if (!opened) return;
         (void)hipSetDevice(device);
         (void)settle();
         if (stream) (void)hipStreamSynchronize(stream);

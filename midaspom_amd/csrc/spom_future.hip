@@ -26,8 +26,9 @@
 // The ensemble's summaries (mdp_future_summary: per-year histograms of the
 // number of occupied patches, per-patch occupancy counts) come from the
 // variants k_future_tab<NM> and k_future_wide_tab<NP>, one launch per window
-// of years.  The model's year is stated in the fut_* device functions, which
-// k_future_tab and both wide kernels call; k_future<NM> holds it inline.
+// of years.  The model's year is lane_year / wide_year of spom_sim_year.h,
+// shared with the scenario simulators, which k_future_tab and both wide
+// kernels call; k_future<NM> holds the lane year inline.
 //
 // Random numbers: the reference draws rand()/RAND_MAX from one sequential
 // stream per process (srand(time(NULL)), :345).  Here every draw is
@@ -59,6 +60,7 @@
 #pragma clang fp contract(off)
 
 #include "spom_rng.h"  // u32x4, philox, kRandMax, u_gt, u_lt (shared with spom_scnsim.hip)
+#include "spom_sim_year.h"  // kTabN, lane_year<NM>, wide_year<NP>
 
 namespace {
 
@@ -91,8 +93,8 @@ __device__ __forceinline__ uint32_t upper_bound(const double *__restrict__ pcum,
 
 // colonisation sums of every survivor set of n <= 8 patches:
 // T[surv][k] = (sum_{l in surv, l != k, ascending} M[l][k]*K_D) + M[n][k]*K_S,
-// the reference's s1 of simpij :89-95 (its added zeros change nothing)
-constexpr int kTabN = 8;
+// the reference's s1 of simpij :89-95 (its added zeros change nothing).  The
+// source term is in the table, so this is not sim_year_table.
 __global__ __launch_bounds__(256) void k_future_table(const double *__restrict__ MK, const double *__restrict__ src,
                                                       uint32_t n, double *__restrict__ T)
 {
@@ -107,10 +109,15 @@ __global__ __launch_bounds__(256) void k_future_table(const double *__restrict__
 
 // ---------------------------------------------------------------------------
 // The replicate model of the lane kernels as functions: fut_draw and
-// fut_rates (also the wide kernels'), fut_init and fut_year<NM>.
-// k_future_tab<NM> calls them; k_future<NM> below still holds the same text
-// inline, because with the calls k_future<64> measured 0.2-0.4 % slower than
-// its parent build.  A change to the model is made in both.
+// fut_rates (also the wide kernels'), fut_init, and fut_year<NM>, which is
+// lane_year<NM> of spom_sim_year.h with this engine's pC.  k_future_tab<NM>
+// calls them.  k_future<NM> below still holds the same text inline: with the
+// year alone replaced by the call its listing changes, and with the prologue
+// replaced as well k_future<64> measured 0.2-0.4 % slower than its parent
+// build.  So the model's year stands in three places --
+// lane_year, wide_year and k_future<NM> -- and a change to the lane year is
+// made in lane_year and here; the tests pin the two to each other
+// (hist[:, 0] of k_future_tab equals k_future's counts).
 // ---------------------------------------------------------------------------
 // (e, c) cell of replicate rg from the posterior, with the reference's
 // carry-over (:361-377): idx < lvalid is the cell, lvalid "never found";
@@ -162,58 +169,15 @@ __device__ __forceinline__ uint64_t fut_init(uint64_t occ0, uint32_t nmiss, cons
     return occ;
 }
 
-// one year of replicate rg (simpij :64-110): the occupancy after year t + 1
+// one year of replicate rg (simpij :64-110): the occupancy after year t + 1.
+// lane_year on the table scaled by K_D: the source term src_k = M[n][k] K_S
+// joins every sum behind the survivors' terms (in T for NM = 8), pC = c s1.
 template <int NM>
 __device__ __forceinline__ uint64_t fut_year(const FutArgs &a, const double *__restrict__ MK,
                                              const double *__restrict__ src, const double *Ts, uint64_t rg,
                                              uint32_t t, uint32_t npairs, uint64_t occ, double E, double c)
 {
-    uint64_t surv = 0;
-    uint32_t colw[NM];
-#pragma unroll
-    for (int m = 0; m < NM / 2; ++m) {
-        if ((uint32_t)m < npairs) {
-            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, (uint32_t)m});
-            const uint32_t k0 = 2 * m, k1 = 2 * m + 1;
-            colw[k0] = w.y >> 1;
-            colw[k1] = w.w >> 1;
-            // extinction: an occupied patch survives if u > E (:75-82)
-            if (((occ >> k0) & 1u) && u_gt(w.x >> 1, E)) surv |= 1ull << k0;
-            if (((occ >> k1) & 1u) && u_gt(w.z >> 1, E)) surv |= 1ull << k1;
-        } else {
-            colw[2 * m] = colw[2 * m + 1] = 0;
-        }
-    }
-    // colonisation sums, ascending l for every k (:89-95)
-    double s1[NM];
-    if constexpr (NM == kTabN) {
-        const double2 *row = reinterpret_cast<const double2 *>(Ts + (uint32_t)surv * kTabN);
-#pragma unroll
-        for (int k = 0; k < NM; k += 2) {
-            const double2 v = row[k / 2];
-            s1[k] = v.x, s1[k + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < NM; ++k) s1[k] = 0.0;
-        for (uint32_t l = 0; l < a.n; ++l) {
-            const bool on = (surv >> l) & 1u;
-#pragma unroll
-            for (int k = 0; k < NM; ++k) s1[k] += on ? MK[l * NM + k] : 0.0;
-        }
-#pragma unroll
-        for (int k = 0; k < NM; ++k) s1[k] += src[k];
-    }
-    uint64_t nw = surv;
-#pragma unroll
-    for (int k = 0; k < NM; ++k) {
-        if ((uint32_t)k < a.n && !((surv >> k) & 1u)) {
-            double pc = c * s1[k];  // :95-97
-            if (pc > 1) pc = 1;
-            if (u_lt(colw[k], pc)) nw |= 1ull << k;  // :98-101
-        }
-    }
-    return nw;
+    return lane_year<NM>(a, MK, Ts, rg, t, npairs, occ, E, src, [&](double s, int) { return c * s; });
 }
 
 template <int NM>
@@ -394,75 +358,6 @@ __device__ __forceinline__ uint32_t fut_wide_init(uint32_t occ_init, uint32_t nm
     return occ;
 }
 
-// one year of the wave's replicate rg: the lane's occupancy word after year t + 1
-template <int NP>
-__device__ __forceinline__ uint32_t fut_wide_year(const FutWideArgs &a, const double2 *G2,
-                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
-                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
-                                                  double E, double c)
-{
-    uint64_t bal[NP][2];
-    uint32_t colw[2 * NP];
-    uint32_t surv = 0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const uint32_t m = lane + 64u * j;
-        bool s0 = false, s1 = false;
-        colw[2 * j] = colw[2 * j + 1] = 0;
-        if (m < npairs) {
-            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
-            colw[2 * j] = w.y >> 1;
-            colw[2 * j + 1] = w.w >> 1;
-            // extinction: an occupied patch survives if u > E (:75-82)
-            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
-            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
-        }
-        bal[j][0] = __ballot(s0);
-        bal[j][1] = __ballot(s1);
-        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
-    }
-    // colonisation sums, ascending l for every k (:89-95): patch
-    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
-    double s[2 * NP];
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        uint64_t both = bal[j][0] | bal[j][1];
-        while (both) {
-            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
-            both &= both - 1;
-#pragma unroll
-            for (uint32_t p = 0; p < 2; ++p) {
-                if (!((bal[j][p] >> lam) & 1u)) continue;
-                const uint32_t l = 2 * (lam + 64u * j) + p;
-                const double2 *row = G2 + fut_wide_slot0(a.n, a.len, l) + lane;
-#pragma unroll
-                for (int jj = 0; jj < NP; ++jj) {
-                    const double2 v = row[64 * jj];
-                    s[2 * jj] += v.x;
-                    s[2 * jj + 1] += v.y;
-                }
-            }
-        }
-    }
-    uint32_t nw = surv;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t bit = 1u << (2 * j + p);
-            if ((live & bit) && !(surv & bit)) {
-                double pc = c * (s[2 * j + p] + (p ? sv.y : sv.x));  // :95-97
-                if (pc > 1) pc = 1;
-                if (u_lt(colw[2 * j + p], pc)) nw |= bit;  // :98-101
-            }
-        }
-    }
-    return nw;
-}
-
 template <int NP>
 __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const double *__restrict__ image,
                                                            const double *__restrict__ src,
@@ -495,7 +390,8 @@ __global__ __launch_bounds__(kFutBlock) void k_future_wide(FutWideArgs a, const 
         uint32_t occ = fut_wide_init(occ_init, a.nmiss, miss, init_w, lane);
         // ---- tfut years (:381-385)
         for (uint32_t t = 0; t < a.tfut; ++t) {
-            occ = fut_wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E, c);
+            occ = wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E,
+                                [&](double s, double sk) { return c * (s + sk); });
             if (__ballot(occ != 0) == 0) {
                 if (!a.ks0) {
                     if (lane == 0) atomicAdd(&cnt[t], 1u);
@@ -659,7 +555,8 @@ __global__ __launch_bounds__(kFutBlock) void k_future_wide_tab(FutWideArgs a, Fu
                 for (uint32_t tt = t + lane; tt < w.t1; tt += 64) atomicAdd(&win[(tt - w.t0) * w.cells], 1u);
                 break;
             }
-            occ = fut_wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E, c);
+            occ = wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, E,
+                                [&](double s, double sk) { return c * (s + sk); });
             uint32_t *row = win + (t - w.t0) * w.cells;
             uint32_t m = 0;
 #pragma unroll
@@ -732,32 +629,6 @@ struct mdp_future : DevQueue {
 };
 
 namespace {
-
-// the one switch over the lane kernels' padded patch count: fn(integral_constant<int, NM>)
-template <typename F>
-int fut_for_nm(uint32_t nm, F &&fn)
-{
-    switch (nm) {
-    case 8: return fn(std::integral_constant<int, 8>());
-    case 16: return fn(std::integral_constant<int, 16>());
-    case 32: return fn(std::integral_constant<int, 32>());
-    case 64: return fn(std::integral_constant<int, 64>());
-    default: return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", nm);
-    }
-}
-
-// and over the patch pairs per lane of k_future_wide
-template <typename F>
-int fut_for_np(uint32_t np, F &&fn)
-{
-    switch (np) {
-    case 1: return fn(std::integral_constant<int, 1>());
-    case 2: return fn(std::integral_constant<int, 2>());
-    case 4: return fn(std::integral_constant<int, 4>());
-    case 8: return fn(std::integral_constant<int, 8>());
-    default: return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", np);
-    }
-}
 
 // the refusal of a look-back overflow, from the flag a finished launch left;
 // device_path: the text of mdp_future_check
@@ -835,7 +706,7 @@ int fut_launch_wide(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, 
     const FutWideArgs a = fut_wide_args(f, seed, rep0, nrep, tfut);
     const int nwg = fut_grid(f, nrep);
     const size_t lds = fut_wide_lds(f, tfut);
-    if (int rc = fut_for_np(f->np, [&](auto NP) {
+    if (int rc = dev_for_pairs(f->np, [&](auto NP) {
             hipLaunchKernelGGL(k_future_wide<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dimage.get(),
                                f->dsrc.get(), f->dpcum.get(), f->docc0.get(), f->dwmiss.get(), f->dpartial.get(), d_states, derr);
             return MDP_OK;
@@ -855,7 +726,7 @@ int fut_launch(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint3
     } else {
         const FutArgs a = fut_args(f, seed, rep0, nrep, tfut);
         const size_t lds = (size_t)tfut * sizeof(uint32_t) + (f->nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0);
-        if (int rc = fut_for_nm(f->nm, [&](auto NM) {
+        if (int rc = dev_for_padded(f->nm, [&](auto NM) {
                 hipLaunchKernelGGL(k_future<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, f->dMK.get(),
                                    f->dsrc.get(), f->dpcum.get(), f->dmiss.get(), f->dT.get(), f->dpartial.get(), derr);
                 return MDP_OK;
@@ -901,7 +772,7 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
             int rc;
             if (f->np) {
                 const FutWideArgs a = fut_wide_args(f, seed, rep0 + done, cnt, tfut);
-                rc = fut_for_np(f->np, [&](auto NP) {
+                rc = dev_for_pairs(f->np, [&](auto NP) {
                     hipLaunchKernelGGL(k_future_wide_tab<decltype(NP)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a,
                                        w, f->dimage.get(), f->dsrc.get(), f->dpcum.get(), f->docc0.get(), f->dwmiss.get(),
                                        (uint32_t *)f->drec_occ.get(), f->drec_idx.get(), f->dtab.get(), derr);
@@ -909,7 +780,7 @@ int fut_summary_run(mdp_future *f, const FutSumPlan &p, uint64_t seed, uint64_t 
                 });
             } else {
                 const FutArgs a = fut_args(f, seed, rep0 + done, cnt, tfut);
-                rc = fut_for_nm(f->nm, [&](auto NM) {
+                rc = dev_for_padded(f->nm, [&](auto NM) {
                     hipLaunchKernelGGL(k_future_tab<decltype(NM)::value>, dim3(nwg), dim3(kFutBlock), lds, st, a, w,
                                        f->dMK.get(), f->dsrc.get(), f->dpcum.get(), f->dmiss.get(), f->dT.get(), (uint64_t *)f->drec_occ.get(),
                                        f->drec_idx.get(), f->dtab.get(), derr);
@@ -937,30 +808,13 @@ int fut_summary_prepare(mdp_future *f, uint64_t nrep, uint32_t tfut, FutSumPlan 
     return f->drec_idx.grow(recs);
 }
 
-// the mean time in ms of `reps` runs of launch() on f->stream, after one
-// warm-up run
-template <typename F>
-int fut_time(mdp_future *f, int reps, double *ms, F launch)
-{
-    int rc;
-    if ((rc = launch())) return rc;
-    HIP_TRY(hipEventRecord(f->ev0, f->stream));
-    for (int i = 0; i < reps; ++i)
-        if ((rc = launch())) return rc;
-    HIP_TRY(hipEventRecord(f->ev1, f->stream));
-    HIP_TRY(hipEventSynchronize(f->ev1));
-    float t = 0;
-    HIP_TRY(hipEventElapsedTime(&t, f->ev0, f->ev1));
-    *ms = (double)t / reps;
-    return MDP_OK;
-}
-
 // tables, colonisation table, look-back flags, stream and events of an engine
 // whose host fields are set
 int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp, const FutPostPlan &pp)
 {
     const int device = f->device;
     if (hipSetDevice(device) != hipSuccess) return mdp_set_error(MDP_EHIP, "hipSetDevice(%d) failed", device);
+    f->opened = true;  // (not DevQueue::open(): this engine's own results for a bad device)
     int rc;
     if ((rc = f->dpcum.assign(pp.pcum))) return rc;
     if (f->np) {
@@ -971,7 +825,7 @@ int fut_device_setup(mdp_future *f, const FutLanePlan &lp, const FutWidePlan &wp
         // summary kernel: the image and one window's table
         const size_t lds[2] = {fut_wide_lds(f, kFutMaxT), (size_t)2 * f->wlen * sizeof(double) + kFutSumTableBytes};
         const void *fn[2] = {nullptr, nullptr};
-        if ((rc = fut_for_np(f->np, [&](auto NP) {
+        if ((rc = dev_for_pairs(f->np, [&](auto NP) {
                  fn[0] = (const void *)k_future_wide<decltype(NP)::value>;
                  fn[1] = (const void *)k_future_wide_tab<decltype(NP)::value>;
                  return MDP_OK;
@@ -1170,9 +1024,11 @@ int mdp_future_time_kernel(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_t
     HIP_TRY(hipSetDevice(f->device));
     if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
     if ((rc = fut_reserve(f, fut_grid(f, nrep), tfut))) return rc;
-    return fut_time(f, reps, ms, [&]() {
+    auto launch = [&]() {
         return fut_launch(f, seed, 0, nrep, tfut, f->dcounts.get(), f->stream, false, f->derr.get() + 1);
-    });
+    };
+    if ((rc = launch())) return rc;  // warm-up
+    return f->time(f->stream, reps, ms, launch);
 }
 
 int mdp_future_summary_device(mdp_future *f, uint64_t seed, uint64_t rep0, uint64_t nrep, uint32_t tfut,
@@ -1227,7 +1083,9 @@ int mdp_future_time_summary(mdp_future *f, uint64_t seed, uint64_t nrep, uint32_
     if (rc) return rc;
     if (!ms || reps <= 0 || nrep == 0) return mdp_set_error(MDP_EINVAL, "bad timing request");
     if ((rc = f->settle())) return rc;  // (mdp_future: the stream rule)
-    return fut_time(f, reps, ms, [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr.get() + 1); });
+    auto launch = [&]() { return fut_summary_run(f, p, seed, 0, nrep, tfut, f->stream, f->derr.get() + 1); };
+    if ((rc = launch())) return rc;  // warm-up
+    return f->time(f->stream, reps, ms, launch);
 }
 
 int mdp_future_philox(uint64_t key, const uint32_t *ctr, uint32_t *out)

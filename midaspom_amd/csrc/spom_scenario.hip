@@ -770,20 +770,18 @@ int mdp_scenario_create_opts(const int32_t *row, uint32_t n, double m, float p, 
     if (int rc = scn_parse_opts(options, &opts)) return rc;
     ScnPlan plan;
     if (int rc = scn_plan(row, n, m, p, d, kind, opts, &plan)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
-    if (device < 0 || device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", device);
-    HIP_TRY(hipSetDevice(device));
     std::unique_ptr<mdp_scenario> sc(new (std::nothrow) mdp_scenario());
     if (!sc) return mdp_set_error(MDP_ENOMEM, "out of host memory");
     sc->device = device;
+    // the first HIP calls: the device (or its refusal) and the stream; the
+    // events are mdp_scenario_time_kernels'
+    if (int rc = sc->open(false)) return rc;
     sc->plan = std::move(plan);
     const ScnPlan &pl = sc->plan;
     int rc;
     if ((rc = sc->dS.assign(pl.S)) || (rc = sc->dw.assign(pl.w)) || (rc = sc->dboff.assign(pl.boff)) ||
         (rc = sc->djsched.assign(pl.jsched)) || (rc = sc->djord.assign(pl.jord)))
         return rc;
-    HIP_TRY(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
     if (pl.lds > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(pl.path == kScnRow ? (const void *)k_scn_row : (const void *)scn_kernel(n),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
@@ -839,16 +837,8 @@ int mdp_scenario_time_kernels(mdp_scenario *sc, double *d_out, void *stream, int
     if (!sc->ev1) HIP_TRY(hipEventCreate(&sc->ev1));
     int rc = scn_launch(sc, d_out, st, 3);
     if (rc) return rc;
-    for (int which = 1; which <= 2; ++which) {
-        HIP_TRY(hipEventRecord(sc->ev0, st));
-        for (int i = 0; i < reps; ++i)
-            if ((rc = scn_launch(sc, d_out, st, which))) return rc;
-        HIP_TRY(hipEventRecord(sc->ev1, st));
-        HIP_TRY(hipEventSynchronize(sc->ev1));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, sc->ev0, sc->ev1));
-        ms[which - 1] = (double)t / reps;
-    }
+    for (int which = 1; which <= 2; ++which)
+        if ((rc = sc->time(st, reps, &ms[which - 1], [&]() { return scn_launch(sc, d_out, st, which); }))) return rc;
     sc->waited_for(st);  // (the last event: everything queued on st is done)
     return MDP_OK;
 }

@@ -193,52 +193,22 @@ __global__ __launch_bounds__(kChainEvalBlock) void k_chain_eval(EvalArgs a, cons
 // (DevQueue: the device, stream and events, released after the buffers below)
 struct mdp_scenario_chain : DevQueue {
     ChainPlan plan;
-    bool ready = false;    // the device side exists (set up by the first call that needs it)
-    bool touched = false;  // a device call was made for this engine
     char kname[32] = "";
     DevBuf<double> dM, dgrid;  // dgrid: [e | c | K | src[nd][nm] | zero row[nm]]
     DevBuf<double> dw;         // [start | target]
     DevBuf<uint32_t> dtab;     // the count table of one launch
     DevBuf<double> dvbase, dbyclass, dout;
-    ~mdp_scenario_chain()
-    {
-        if (touched) drain();  // (else nothing below exists: no HIP call)
-    }
+    ~mdp_scenario_chain() { drain(); }  // (never opened: nothing below exists, no HIP call)
 };
 
 namespace {
 
-template <typename F>
-int chain_for_nm(uint32_t nm, F &&fn)
-{
-    switch (nm) {
-    case 8: return fn(std::integral_constant<int, 8>());
-    case 16: return fn(std::integral_constant<int, 16>());
-    case 32: return fn(std::integral_constant<int, 32>());
-    case 64: return fn(std::integral_constant<int, 64>());
-    default: return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", nm);
-    }
-}
-
-// the first device calls of an engine: the device, the table, stream and events
+// the device side of an engine, set up by the first call that needs it: the
+// device, stream and events, then the table, uploaded once
 int chain_device(mdp_scenario_chain *s)
 {
-    if (s->ready) {
-        HIP_TRY(hipSetDevice(s->device));
-        return MDP_OK;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
-    if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
-    HIP_TRY(hipSetDevice(s->device));
-    s->touched = true;
-    if (s->dM.empty())
-        if (int rc = s->dM.assign(s->plan.M)) return rc;
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
-    if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
-    s->ready = true;
-    return MDP_OK;
+    if (int rc = s->open()) return rc;
+    return s->dM.empty() ? s->dM.assign(s->plan.M) : MDP_OK;
 }
 
 struct ChainGrid {
@@ -304,7 +274,7 @@ int chain_count_launch(mdp_scenario_chain *s, const ChainCall &call, const Chain
     a.key1 = (uint32_t)(seed >> 32);
     HIP_TRY(hipMemsetAsync(s->dtab.get(), 0, l.npts * cells * sizeof(uint32_t), st));
     const size_t lds = chain_counts_lds(p);
-    if (int rc = chain_for_nm(p.nm, [&](auto NM) {
+    if (int rc = dev_for_padded(p.nm, [&](auto NM) {
             hipLaunchKernelGGL(k_scnchain<decltype(NM)::value>, dim3(l.nwg), dim3(kChainBlock), lds, st, a, s->dM.get(),
                                baseline ? dzero : dsrc, de, dc, dK, s->dtab.get());
             return MDP_OK;
@@ -540,14 +510,7 @@ int mdp_scenario_chain_time_kernels(mdp_scenario_chain *s, int ts, int tdis, con
     };
     for (int ph = 0; ph < 3; ++ph) {
         if (int rc = phase(ph)) return rc;  // warm-up
-        HIP_TRY(hipEventRecord(s->ev0, st));
-        for (int i = 0; i < reps; ++i)
-            if (int rc = phase(ph)) return rc;
-        HIP_TRY(hipEventRecord(s->ev1, st));
-        HIP_TRY(hipEventSynchronize(s->ev1));
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, s->ev0, s->ev1));
-        ms[ph] = (double)t / reps;
+        if (int rc = s->time(st, reps, &ms[ph], [&]() { return phase(ph); })) return rc;
     }
     return MDP_OK;
 }

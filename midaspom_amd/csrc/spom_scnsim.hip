@@ -30,9 +30,10 @@
 // one grid point, so K, e, c, E and the source row are wave-uniform (scalar
 // operands).  A work tile is (point, 256 replicates); workgroups of 256
 // threads walk the tiles grid-stride.  Occupancy is one 64-bit mask; the
-// year is k_future's (fut_year<NM>) on the unscaled M, K applied after the
-// sum.  The tallies happen once per trajectory: ballots per wave, then 64-bit
-// integer atomics into the global tables -- exact, the same for every split.
+// year is the future engine's (lane_year<NM>, spom_sim_year.h) on the unscaled
+// M, K applied after the sum.  The tallies happen once per trajectory: ballots
+// per wave, then 64-bit integer atomics into the global tables -- exact, the
+// same for every split.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,13 +45,12 @@
 #include <vector>
 
 #include "spom_dev.h"
-#include "spom_future_plan.h"  // fut_wide_slot0: the addressing of the distance image
 #include "spom_scnsim_plan.h"
 
 #pragma clang fp contract(off)
 
 #include "spom_rng.h"
-#include "spom_sim_year.h"  // kTabN, sim_year<NM>, sim_year_table
+#include "spom_sim_year.h"  // kTabN, sim_year_table, sim_year<NM>, wide_year<NP>: the model's year
 
 namespace {
 
@@ -154,8 +154,9 @@ __global__ __launch_bounds__(kSimBlock) void k_scnsim(SimArgs a, const double *_
 // survivors of a year are 2*NP wave ballots, walked in ascending patch order
 // (j, then lane, then parity); every step adds one row of the unscaled
 // Toeplitz table, a window of the two-sided distance image in LDS
-// (spom_scnsim_plan.h), to the lane's 2*NP running sums.  Same stream, same
-// sums in the same order, K applied after the sum by sim_year's expression:
+// (spom_scnsim_plan.h), to the lane's 2*NP running sums: wide_year<NP> of
+// spom_sim_year.h, the function k_future_wide calls, so the same stream and the
+// same sums in the same order, K applied after the sum by sim_year's expression:
 // on n <= 64 patches the tables of k_scnsim<NM>, bit for bit.  A work tile is
 // (point, 4 replicates), one per wave of the workgroup.
 // ---------------------------------------------------------------------------
@@ -169,77 +170,6 @@ struct SimWaveArgs {
     uint32_t key0, key1;
     uint32_t len, pad;  // len: doubles per copy of the distance image
 };
-
-// one year of the wave's replicate rg: the lane's occupancy word after year
-// t + 1.  (ks, km) as sim_year: pC = (c (s1 + src_k ks)) km.
-template <int NP>
-__device__ __forceinline__ uint32_t sim_wave_year(const SimWaveArgs &a, const double2 *G2,
-                                                  const double *__restrict__ src, uint64_t rg, uint32_t t,
-                                                  uint32_t lane, uint32_t npairs, uint32_t live, uint32_t occ,
-                                                  double E, double c, double ks, double km)
-{
-    uint64_t bal[NP][2];
-    uint32_t colw[2 * NP];
-    uint32_t surv = 0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const uint32_t m = lane + 64u * j;
-        bool s0 = false, s1 = false;
-        colw[2 * j] = colw[2 * j + 1] = 0;
-        if (m < npairs) {
-            const u32x4 w = philox(a.key0, a.key1, u32x4{(uint32_t)rg, (uint32_t)(rg >> 32), t, m});
-            colw[2 * j] = w.y >> 1;
-            colw[2 * j + 1] = w.w >> 1;
-            // extinction: an occupied patch survives if u > E (dieoff.c:56-64)
-            s0 = ((occ >> (2 * j)) & 1u) && u_gt(w.x >> 1, E);
-            s1 = ((occ >> (2 * j + 1)) & 1u) && u_gt(w.z >> 1, E);
-        }
-        bal[j][0] = __ballot(s0);
-        bal[j][1] = __ballot(s1);
-        surv |= ((uint32_t)s0 << (2 * j)) | ((uint32_t)s1 << (2 * j + 1));
-    }
-    // colonisation sums, ascending l for every k (dieoff.c:72-77): patch
-    // l = 2*(lam + 64*j) + p ascends with j, then lam, then p
-    double s[2 * NP];
-#pragma unroll
-    for (int k = 0; k < 2 * NP; ++k) s[k] = 0.0;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        uint64_t both = bal[j][0] | bal[j][1];
-        while (both) {
-            const uint32_t lam = (uint32_t)__builtin_ctzll(both);
-            both &= both - 1;
-#pragma unroll
-            for (uint32_t p = 0; p < 2; ++p) {
-                if (!((bal[j][p] >> lam) & 1u)) continue;
-                const uint32_t l = 2 * (lam + 64u * j) + p;
-                const double2 *row = G2 + fut_wide_slot0(a.n, a.len, l) + lane;
-#pragma unroll
-                for (int jj = 0; jj < NP; ++jj) {
-                    const double2 v = row[64 * jj];
-                    s[2 * jj] += v.x;
-                    s[2 * jj + 1] += v.y;
-                }
-            }
-        }
-    }
-    uint32_t nw = surv;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const double2 sv = reinterpret_cast<const double2 *>(src)[lane + 64 * j];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const uint32_t bit = 1u << (2 * j + p);
-            if ((live & bit) && !(surv & bit)) {
-                const double sk = (p ? sv.y : sv.x) * ks;    // loss.c:95-98: the product is rounded before the add
-                double pc = (c * (s[2 * j + p] + sk)) * km;  // dieoff.c:78 (c s1) K
-                if (pc > 1) pc = 1;
-                if (u_lt(colw[2 * j + p], pc)) nw |= bit;
-            }
-        }
-    }
-    return nw;
-}
 
 template <int NP>
 __global__ __launch_bounds__(kSimBlock) void k_scnsim_wave(SimWaveArgs a, const double *__restrict__ image,
@@ -303,8 +233,12 @@ __global__ __launch_bounds__(kSimBlock) void k_scnsim_wave(SimWaveArgs a, const 
             // the replicate is extinct and no source in this or any later
             // year: every sum is 0, pC = c*0, and no draw is below 0
             if (!(a.kind && scen) && __ballot(occ != 0) == 0) break;
-            occ = sim_wave_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, scen ? Es : Eb, c, scen ? Ks : 0.0,
-                                    scen ? Km : 1.0);
+            // (ks, km) as sim_year: pC = (c (s1 + src_k ks)) km
+            const double ks = scen ? Ks : 0.0, km = scen ? Km : 1.0;
+            occ = wide_year<NP>(a, G2, src, rg, t, lane, npairs, live, occ, scen ? Es : Eb, [&](double s, double sv) {
+                const double sk = sv * ks;   // loss.c:95-98: the product is rounded before the add
+                return (c * (s + sk)) * km;  // dieoff.c:78 (c s1) K
+            });
         }
         // ---- tallies of the final state: one integer atomic per table
         if (hist) {
@@ -330,59 +264,21 @@ __global__ __launch_bounds__(kSimBlock) void k_scnsim_wave(SimWaveArgs a, const 
 // (DevQueue: the device, stream and events, released after the buffers below)
 struct mdp_scenario_sim : DevQueue {
     SimPlan plan;
-    bool ready = false;  // the device side exists (set up by the first call that needs it)
-    bool touched = false;  // a device call was made for this engine
     char kname[32] = "";
     DevBuf<double> dM, dgrid;  // dM: the lane kernel's table, or the wave kernel's image
     DevBuf<uint32_t> drow;     // the wave kernel's fixed[64] | missmask[64]
     DevBuf<uint32_t> dmiss;
     DevBuf<unsigned long long> dhist, dmatch;
-    ~mdp_scenario_sim()
-    {
-        if (touched) drain();  // (else nothing below exists: no HIP call)
-    }
+    ~mdp_scenario_sim() { drain(); }  // (never opened: nothing below exists, no HIP call)
 };
 
 namespace {
 
-// the one switch over the padded patch count: fn(integral_constant<int, NM>)
-template <typename F>
-int sim_for_nm(uint32_t nm, F &&fn)
-{
-    switch (nm) {
-    case 8: return fn(std::integral_constant<int, 8>());
-    case 16: return fn(std::integral_constant<int, 16>());
-    case 32: return fn(std::integral_constant<int, 32>());
-    case 64: return fn(std::integral_constant<int, 64>());
-    default: return mdp_set_error(MDP_EINVAL, "internal: padded patch count %u", nm);
-    }
-}
-
-// and over the patch pairs per lane of k_scnsim_wave
-template <typename F>
-int sim_for_np(uint32_t np, F &&fn)
-{
-    switch (np) {
-    case 1: return fn(std::integral_constant<int, 1>());
-    case 2: return fn(std::integral_constant<int, 2>());
-    case 4: return fn(std::integral_constant<int, 4>());
-    case 8: return fn(std::integral_constant<int, 8>());
-    default: return mdp_set_error(MDP_EINVAL, "internal: %u patch pairs per lane", np);
-    }
-}
-
-// the first device calls of an engine: the device, the tables, stream and events
+// the device side of an engine, set up by the first call that needs it: the
+// device, stream and events, then the tables, uploaded once
 int sim_device(mdp_scenario_sim *s)
 {
-    if (s->ready) {
-        HIP_TRY(hipSetDevice(s->device));
-        return MDP_OK;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mdp_set_error(MDP_ENODEV, "no HIP device available");
-    if (s->device < 0 || s->device >= ndev) return mdp_set_error(MDP_ENODEV, "device %d not present", s->device);
-    HIP_TRY(hipSetDevice(s->device));
-    s->touched = true;
+    if (int rc = s->open()) return rc;
     const SimPlan &p = s->plan;
     if (s->dM.empty())
         if (int rc = s->dM.assign(p.np ? p.image : p.M)) return rc;
@@ -393,10 +289,6 @@ int sim_device(mdp_scenario_sim *s)
         rowbits.insert(rowbits.end(), p.wmissmask.begin(), p.wmissmask.end());
         if (int rc = s->drow.assign(rowbits)) return rc;
     }
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->ev0) HIP_TRY(hipEventCreate(&s->ev0));
-    if (!s->ev1) HIP_TRY(hipEventCreate(&s->ev1));
-    s->ready = true;
     return MDP_OK;
 }
 
@@ -437,39 +329,8 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
 {
     const SimPlan &p = s->plan;
     const double *de = s->dgrid.get(), *dc = de + gr.ne, *dK = dc + gr.nc, *dsrc = de + sim_src_at(gr);
-    if (p.np) {
-        const size_t lds = (size_t)2 * p.wlen * sizeof(double);  // both copies of the image: <= 32 KB
-        for (const SimLaunch &l : call.launches) {
-            SimWaveArgs a{};
-            a.n = p.n;
-            a.nmiss = p.nmiss;
-            a.ts = (uint32_t)gr.ts;
-            a.tdis = (uint32_t)gr.tdis;
-            a.nc = gr.nc;
-            a.nK = gr.nK;
-            a.nd = gr.nd;
-            a.kind = (uint32_t)p.kind;
-            a.p0 = l.p0;
-            a.tiles = l.tiles;
-            a.tpp = call.tiles_per_point;
-            a.rep0 = rep0;
-            a.nrep = nrep;
-            a.key0 = (uint32_t)seed;
-            a.key1 = (uint32_t)(seed >> 32);
-            a.len = p.wlen;
-            if (int rc = sim_for_np(p.np, [&](auto NP) {
-                    hipLaunchKernelGGL(k_scnsim_wave<decltype(NP)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a,
-                                       s->dM.get(), dsrc, de, dc, dK, s->drow.get(), s->dmiss.get(), d_hist, d_match);
-                    return MDP_OK;
-                }))
-                return rc;
-            HIP_TRY(hipGetLastError());
-        }
-        return MDP_OK;
-    }
-    const size_t lds = p.nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0;
-    for (const SimLaunch &l : call.launches) {
-        SimArgs a{};
+    // the fields SimArgs and SimWaveArgs share, of launch l
+    auto common = [&](auto &a, const SimLaunch &l) {
         a.n = p.n;
         a.nmiss = p.nmiss;
         a.ts = (uint32_t)gr.ts;
@@ -485,10 +346,31 @@ int sim_launch(mdp_scenario_sim *s, const SimCall &call, const SimGrid &gr, uint
         a.nrep = nrep;
         a.key0 = (uint32_t)seed;
         a.key1 = (uint32_t)(seed >> 32);
+    };
+    if (p.np) {
+        const size_t lds = (size_t)2 * p.wlen * sizeof(double);  // both copies of the image: <= 32 KB
+        for (const SimLaunch &l : call.launches) {
+            SimWaveArgs a{};
+            common(a, l);
+            a.len = p.wlen;
+            if (int rc = dev_for_pairs(p.np, [&](auto NP) {
+                    hipLaunchKernelGGL(k_scnsim_wave<decltype(NP)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a,
+                                       s->dM.get(), dsrc, de, dc, dK, s->drow.get(), s->dmiss.get(), d_hist, d_match);
+                    return MDP_OK;
+                }))
+                return rc;
+            HIP_TRY(hipGetLastError());
+        }
+        return MDP_OK;
+    }
+    const size_t lds = p.nm == kTabN ? sizeof(double) * (kTabN << kTabN) : 0;
+    for (const SimLaunch &l : call.launches) {
+        SimArgs a{};
+        common(a, l);
         a.live = p.live;
         a.fixed = p.fixed;
         a.missmask = p.missmask;
-        if (int rc = sim_for_nm(p.nm, [&](auto NM) {
+        if (int rc = dev_for_padded(p.nm, [&](auto NM) {
                 hipLaunchKernelGGL(k_scnsim<decltype(NM)::value>, dim3(l.nwg), dim3(kSimBlock), lds, st, a, s->dM.get(), dsrc,
                                    de, dc, dK, s->dmiss.get(), d_hist, d_match);
                 return MDP_OK;
@@ -607,15 +489,7 @@ int mdp_scenario_sim_time_kernel(mdp_scenario_sim *s, int ts, int tdis, const do
         return sim_launch(s, call, gr, seed, 0, nrep, s->dhist.get(), want_match ? s->dmatch.get() : nullptr, s->stream);
     };
     if (int rc = launch()) return rc;  // warm-up
-    HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    for (int i = 0; i < reps; ++i)
-        if (int rc = launch()) return rc;
-    HIP_TRY(hipEventRecord(s->ev1, s->stream));
-    HIP_TRY(hipEventSynchronize(s->ev1));
-    float t = 0;
-    HIP_TRY(hipEventElapsedTime(&t, s->ev0, s->ev1));
-    *ms = (double)t / reps;
-    return MDP_OK;
+    return s->time(s->stream, reps, ms, launch);
 }
 
 }  // extern "C"
