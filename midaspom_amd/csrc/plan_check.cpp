@@ -38,6 +38,16 @@ using MdpEnginePlan = mdp_engine;
 
 namespace {
 
+// does the plan run the specialised forward kernel (a direct path)?
+bool direct(const MdpEnginePlan *e)
+{
+#ifdef MDP_PLAN_PATH
+    return path_is_jit(e->path);
+#else  // a planner from before MdpPath (scripts/jit_sources.py --rev): its flags
+    return e->jit && !e->wide;
+#endif
+}
+
 uint64_t g_h = 0xcbf29ce484222325ull;  // FNV-1a, 64 bit
 
 void mix(const void *p, size_t n)
@@ -89,7 +99,7 @@ void digest(MdpEnginePlan *e)
             const std::string src = mdp_jit_forward_source(c);
             source(("chunk" + std::to_string(i++)).c_str(), src, c.flops_pt);
         }
-    } else if (e->jit) {
+    } else if (direct(e)) {
         for (int variant = 0; variant < 2; ++variant) {
             const std::string src = jit_source(e, variant);
             source(variant ? "fused" : "reading", src, e->jit_flops_pt);
@@ -120,6 +130,20 @@ int tall_source(MdpEnginePlan *e)
 std::string path_of(const MdpEnginePlan *e)
 {
     char b[64];
+#ifdef MDP_PLAN_PATH
+    switch (e->path) {
+    case MdpPath::Generic: return "generic";
+    case MdpPath::Direct:
+    case MdpPath::DirectQGlobal: break;
+    case MdpPath::WideHs: snprintf(b, sizeof b, "wide-hs<%u,%u,%u>", e->hs_rt, e->hs_nb, e->hs_nw); return b;
+    case MdpPath::WideMmt:
+        snprintf(b, sizeof b, "wide-mmt<%u,%u,%s>", e->mmt_rt, e->mmt_rows, mmt_shape(e).db ? "2buf" : "1buf");
+        return b;
+    case MdpPath::WideMma: snprintf(b, sizeof b, "wide-mma<%u>", e->mma_npm); return b;
+    case MdpPath::WidePlain: return "wide-plain";
+    }
+    const bool qglobal = e->path == MdpPath::DirectQGlobal;
+#else  // a planner from before MdpPath (scripts/jit_sources.py --rev): its flags
     if (e->wide) {
         if (e->hs) snprintf(b, sizeof b, "wide-hs<%u,%u,%u>", e->hs_rt, e->hs_nb, e->hs_nw);
         else if (e->mmt) snprintf(b, sizeof b, "wide-mmt<%u,%u,%s>", e->mmt_rt, e->mmt_rows, mmt_shape(e).db ? "2buf" : "1buf");
@@ -128,17 +152,19 @@ std::string path_of(const MdpEnginePlan *e)
         return b;
     }
     if (!e->jit) return "generic";
+    const bool qglobal = e->qglobal;
+#endif
     if (!e->chunks.empty()) {
         snprintf(b, sizeof b, "chunked<%zu%s>", e->chunks.size(), e->chunks[0].qidx.empty() ? "" : ",gathered");
-        return std::string(e->jit_plan.vlds ? "vlds " : "direct ") + b + (e->qglobal ? " qglobal" : "");
+        return std::string(e->jit_plan.vlds ? "vlds " : "direct ") + b + (qglobal ? " qglobal" : "");
     }
     if (e->jit_plan.vlds) return "vlds";
 #ifdef MDP_PLAN_GRID
     const bool fused = mdp_plan_fused_capable(e);
 #else  // a planner from before mdp_plan_grid (scripts/jit_sources.py --rev)
-    const bool fused = !e->qglobal && fused_lds(e, e->jit_plan.ct_max) <= kFusedLdsMax;
+    const bool fused = !qglobal && fused_lds(e, e->jit_plan.ct_max) <= kFusedLdsMax;
 #endif
-    return std::string("direct") + (fused ? " fused-capable" : "") + (e->qglobal ? " qglobal" : "");
+    return std::string("direct") + (fused ? " fused-capable" : "") + (qglobal ? " qglobal" : "");
 }
 
 template <typename T>
@@ -173,7 +199,7 @@ int grid_line(MdpEnginePlan *eng, const GridArgs &a)
     MdpCTables ct;
     MdpGridPlan g;
     if (mdp_plan_grid(eng, ct, e.data(), a.ne, c.data(), a.nc, a.ncu, g)) return 1;
-    const bool jit = eng->jit && !eng->wide;
+    const bool jit = direct(eng);
     if (jit) mdp_plan_fwd_launch(eng, ct, a.ne, a.nc, g);
     std::string kernels;
     for (const std::string &k : mdp_plan_grid_kernels(eng, g, a.ne, a.nc)) kernels += (kernels.empty() ? "" : ";") + k;
@@ -250,7 +276,7 @@ int main(int argc, char **argv)
     printf("path %s | nj %u nitems %u ldQ %zu nqi %u qmaxlen %u kzmax %u slots %u conflicts %u + %u | digest %016llx\n",
            path_of(eng.get()).c_str(), eng->nj, eng->nitems, eng->ldQ, pl.nqi, pl.qmaxlen, pl.kzmax, eng->npl_slots,
            eng->slot_conflicts, eng->slot_store_conflicts, (unsigned long long)g_h);
-    if (g_sources && eng->jit && !eng->wide && eng->chunks.empty() && !pl.vlds && tall_source(eng.get())) return 1;
+    if (g_sources && direct(eng.get()) && eng->chunks.empty() && !pl.vlds && tall_source(eng.get())) return 1;
     fputs(g_src_lines.c_str(), stdout);
     if (grid.on && grid_line(eng.get(), grid)) return fail();
     return 0;

@@ -1,7 +1,8 @@
 // midaspom_amd/csrc/spom_engine.h -- internal to the posterior engine (not
 // installed; the public ABI is include/midaspom.h).  Shared by
-//   spom_plan.cpp    host planning: options, plan tables, hipRTC sources, and
-//                    per grid the c tables and the grid plan (kernel variant,
+//   spom_plan.cpp    host planning: options, plan tables, the engine's path
+//                    (MdpPath), hipRTC sources, and per grid the c tables and
+//                    the grid plan (each slot's step, MdpStep, kernel variant,
 //                    point list, chunk widths, buffer sizes, launch shape)
 //   spom_engine.hip  the kernels; the engine (the plan plus its device contexts
 //                    and run-time state); device set-up, uploads and launches
@@ -74,6 +75,43 @@ constexpr size_t kWideVBytes = 1ull << 30;     // wide path: state-vector scratc
 // ---------------------------------------------------------------------------
 // types
 // ---------------------------------------------------------------------------
+// What an engine runs: one path, decided once (mdp_plan_engine's last
+// statement).  jit_plan.vlds and chunks are sub-modes of the direct paths.
+enum class MdpPath : uint8_t {
+    Generic,        // k_zpv -> k_coefs -> k_forward(_lds): MDP_JIT=0, or hipRTC failed
+    Direct,         // k_qrows -> the forward kernel specialised with hipRTC, or its fused variant alone
+    DirectQGlobal,  // its Q rows built in HBM instead (k_qrows' tables exceed the LDS, or MDP_QGLOBAL=1)
+    WideHs,         // years of more than 16 states, or MDP_WIDE=1: k_zrows -> k_witems -> k_fwd_hs
+    WideMmt,        // ... k_zrows -> k_witems + k_wq -> k_fwd_mmt
+    WideMma,        // ... -> k_fwd_mma
+    WidePlain       // ... -> k_fwd_wide
+};
+constexpr bool path_is_wide(MdpPath p) { return p >= MdpPath::WideHs; }
+constexpr bool path_is_jit(MdpPath p) { return p == MdpPath::Direct || p == MdpPath::DirectQGlobal; }
+// Q rows from k_zrows + k_witems + k_wq (k_fwd_hs reads the item factors themselves)
+constexpr bool path_q_global(MdpPath p) { return p >= MdpPath::DirectQGlobal; }
+
+// What one of a grid's three slots (0: Z rows / k_zpv, 1: Q rows / k_coefs,
+// 2: forward) runs: one case per launcher body (launch_slot).  mdp_plan_steps
+// is the only place that picks them.
+enum class MdpStep : uint8_t {
+    None,
+    Zpv,
+    Coefs,
+    FwdGeneric,
+    Zrows,
+    Qrows,
+    ItemsQ,        // k_witems + k_wq per chunk of c values
+    ItemsAll,      // k_fwd_hs's k_witems: every column's item factors, when they fit one Pg block (wide_cb_items
+                   // >= nc); else the slot stays, timed and named, with nothing in it, and FwdHs takes them
+    FwdJit,
+    FwdJitChunks,
+    FwdHs,         // with k_witems per chunk of columns when the factors do not fit one Pg block
+    FwdMmt,
+    FwdMma,
+    FwdPlain
+};
+
 // The tables that depend on the grid's |c| bound (mdp_plan_grid builds them;
 // z_split prunes the Z rows for the bound).  Cached by cmax: a grid under the
 // same bound neither rebuilds nor re-uploads them.
@@ -91,6 +129,7 @@ struct MdpCTables {
 // made on the host without a device.  set_grid_dev grows and uploads what it
 // says, the launchers read it.
 struct MdpGridPlan {
+    MdpStep step[3] = {MdpStep::None, MdpStep::None, MdpStep::None};  // what each slot runs (mdp_plan_steps)
     uint32_t ne_sform = 0;  // e rows on the s-form (x < y), for the work count
     bool tables_new = false;  // the c tables were rebuilt for this grid (upload them)
     // forward kernels with several points per lane: list positions -> e rows
@@ -147,9 +186,8 @@ struct MdpEnginePlan {
     bool lds_zpv = true;      // k_coefs stages Z/PV in LDS
     bool lds_part = true;     // k_coefs keeps subset partial sums in LDS
     bool diag = false;        // MDP_DIAG: record phase stamps
-    bool jit = false;         // forward kernel specialised with hipRTC (spom_jit.cpp)
-    bool wide = false;        // wide path (k_witems + k_wq + k_fwd_wide): npmax > 16 or MDP_WIDE=1
-    bool qrows_xcd = true;    // k_qrows deals c ranges XCD-aware (MDP_QROWS_XCD=0: blockIdx order)
+    MdpPath path = MdpPath::Generic;  // what the engine runs
+    bool qrows_xcd = true;   // k_qrows deals c ranges XCD-aware (MDP_QROWS_XCD=0: blockIdx order)
     double wide_flops_pt = 0; // its FP64 flops per grid point
     int jit_epl = 1;          // its grid points per lane (Q-row reading variant and chunks)
     uint32_t jit_kblock = kBlock;  // its threads per column
@@ -168,11 +206,10 @@ struct MdpEnginePlan {
     std::vector<std::string> chunk_src;
     std::vector<MdpJitPlan> chunks;               // > 1: the series runs as chunks of years
     std::vector<std::vector<char>> chunk_code;    // their code objects
-    bool qglobal = false;     // Q rows built by k_zrows + k_witems + k_wq (k_qrows' tables exceed the LDS)
     double cbound = 0.0;         // the per-c tables' |c| bound at least this (mdp_engine_set_cbound)
     int fused_mode = -1;            // MDP_FUSED: -1 auto, 0, 1
     MdpJitPlan jit_plan;
-    // direct path (jit): k_qrows computes Pc[j][b] for the needed (j, b)
+    // direct path: k_qrows computes Pc[j][b] for the needed (j, b)
     // items, the forward kernel assembles Q from them
     uint32_t nj = 0, nitems = 0, ncoef_d = 0;
     size_t ldP = 0;
@@ -187,7 +224,6 @@ struct MdpEnginePlan {
     // k_fwd_mma (wide years on the matrix cores): per year t its K entries
     // (k | |A_k| << 8 | m << 16 | valid << 31, padded to 4) from kbase[t],
     // and the Q-row slot of each (K entry, new state l) from gbase[t]
-    bool mma = false;
     uint32_t mma_npm = 0;
     std::vector<uint2> mma_kt;  // per year its K entries: LDS byte offsets of the W rows, m, k
     std::vector<uint2> mma_wplan;  // per (year, wave) its work item (chunk range, column tile, slice)
@@ -196,7 +232,6 @@ struct MdpEnginePlan {
     // k_fwd_mmt (round 6, the default matrix-core forward: years of up to
     // 1 024 states): RT point tiles a block, per (year, tile) K lists, per
     // (year, wave) work items (build_mmt_plan)
-    bool mmt = false;
     uint32_t mmt_rt = 0, mmt_rows = 0;
     std::vector<uint2> mmt_kt, mmt_ktile, mmt_wplan;
     std::vector<uint32_t> mmt_cidx;
@@ -205,7 +240,6 @@ struct MdpEnginePlan {
     // cube positions, RT point tiles; per (year, tile) K lists of hidden
     // states and their item offsets, per year butterfly passes, the new
     // states' cube positions in tile order and free 16-row park blocks
-    bool hs = false;
     uint32_t hs_rt = 0, hs_nb = 0, hs_nw = 16;
     uint32_t hs_probe = 0;  // MDP_HS_PROBE (timing probes only, wrong results): 1 skips v Pe, 2 U Pc
     std::vector<uint32_t> hs_kt, hs_cidx, hs_pbase, hs_dpos, hs_dbase, hs_pk;
@@ -402,8 +436,8 @@ int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build);
 enum class MdpPlanMode {
     Compile,       // compile the forward kernel the first grid most likely runs
     OfflineCheck,  // MDP_JIT_CHECK=1 without a device: compile every kernel, then MDP_ENODEV
-    // no hipRTC: the specialised kernel is taken to compile, so eng->jit is
-    // set with no code object behind it.  For plan_check, which plans a bare
+    // no hipRTC: the specialised kernel is taken to compile, so the path is
+    // a direct one with no code object behind it.  For plan_check, which plans a bare
     // MdpEnginePlan: a plan is not an engine, and nothing that uploads or
     // launches takes one.
     TablesOnly
@@ -416,6 +450,7 @@ int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, Md
 
 #define MDP_PLAN_GRID 1    // (plan_check.cpp also builds against planners without these: scripts/jit_sources.py --rev)
 #define MDP_ENGINE_PLAN 1  // the planner takes an MdpEnginePlan
+#define MDP_PLAN_PATH 1    // the plan names its path (MdpPath), the grid plan its steps
 // The grid plan of e[ne] x c[nc] on a device of ncu compute units: refuses a
 // c the engine does not take (MDP_EINVAL) and Z rows past k_zrows' LDS
 // (MDP_EUNSUPPORTED), rebuilds ct when the grid's |c| bound (at least
@@ -434,8 +469,10 @@ bool mdp_plan_fused_capable(const MdpEnginePlan *eng);
 // columns of j: pressure fmin(c inf, 1) = 1.0), and the packed items {B | row
 // << 24, j | (row >> 8) << 24}; one spare element each.
 void mdp_plan_item_tables(const MdpEnginePlan *eng, std::vector<double> &sv, std::vector<uint2> &items);
-// Does kernel slot k (0: Q rows / k_zpv, 1: k_coefs, 2: forward) run on this path?
-bool mdp_plan_slot_active(const MdpEnginePlan *eng, const MdpGridPlan &g, int k);
+// What each slot of a grid runs, from the engine's path and g.fused: the only
+// place that knows these rules (a slot with nothing to do is MdpStep::None).
+// On a default-constructed g: the steps the path alone implies.
+void mdp_plan_steps(const MdpEnginePlan *eng, MdpGridPlan &g);
 // The kernel instantiations one run of the grid notes for mdp_engine_launched,
 // sorted (the generic path's forward kernel is left to its launcher).
 std::vector<std::string> mdp_plan_grid_kernels(const MdpEnginePlan *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc);

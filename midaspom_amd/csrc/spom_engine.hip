@@ -18,7 +18,10 @@
 //   spom_jit.cpp     generator of the specialised forward kernel's source
 //   spom_jit_rtc.cpp its hipRTC compilation and code-object caches
 //
-// Paths (mdp_plan_engine picks one per engine; DESIGN.md sections 3-4):
+// Paths (mdp_plan_engine picks one per engine, MdpEnginePlan::path: Generic,
+// Direct or DirectQGlobal, WideHs / WideMmt / WideMma / WidePlain; per grid
+// mdp_plan_steps names what each of the three slots runs, MdpGridPlan::step,
+// and launch_slot switches on it; DESIGN.md sections 3-4):
 //   generic  any problem (MDP_JIT=0, or hipRTC failed): k_zpv -> k_coefs ->
 //            k_forward(_lds), transitions as degree-D polynomials in e;
 //            tables from build_plan.
@@ -2280,9 +2283,6 @@ __global__ __launch_bounds__(kBlock) void k_fwd_wide(
 // ---------------------------------------------------------------------------
 
 constexpr int kNumEv = 6;  // start/stop per kernel: k_zpv, k_coefs, k_forward
-const char *const kKernelNames[3][3] = {{"k_zpv", "k_coefs", "k_forward"},
-                                        {"k_zrows", "k_qrows", "k_forward"},
-                                        {"k_zrows", "k_witems+k_wq", "k_fwd_wide"}};
 
 // record a launched kernel instantiation ("k_qrows<16,0,2>", ...): the name
 // is formatted and looked up in the engine's set (fmt is a launch site's
@@ -2339,17 +2339,16 @@ int set_lds_limit(K *kernel, size_t bytes)
 // instantiation and k_fwd_wide
 int wide_lds_limits(const mdp_engine *eng)
 {
-    int rc;
-    if (eng->mma && (rc = for_mma(eng, [&](auto npm) { return set_lds_limit(k_fwd_mma<npm()>, mma_lds(eng)); }))) return rc;
-    if (eng->mmt && (rc = for_mmt(eng, [&](auto rt, auto rows, auto db) {
+    int rc = MDP_OK;
+    if (eng->path == MdpPath::WideMma)
+        rc = for_mma(eng, [&](auto npm) { return set_lds_limit(k_fwd_mma<npm()>, mma_lds(eng)); });
+    if (eng->path == MdpPath::WideMmt)
+        rc = for_mmt(eng, [&](auto rt, auto rows, auto db) {
             return set_lds_limit(k_fwd_mmt<rt(), rows(), db()>, mmt_lds(eng));
-        })))
-        return rc;
-    if (eng->hs && (rc = for_hs(eng, [&](auto rt, auto nb, auto nw) {
-            return set_lds_limit(k_fwd_hs<rt(), nb(), nw()>, hs_lds(eng));
-        })))
-        return rc;
-    return set_lds_limit(k_fwd_wide, wide_lds(eng));
+        });
+    if (eng->path == MdpPath::WideHs)
+        rc = for_hs(eng, [&](auto rt, auto nb, auto nw) { return set_lds_limit(k_fwd_hs<rt(), nb(), nw()>, hs_lds(eng)); });
+    return rc ? rc : set_lds_limit(k_fwd_wide, wide_lds(eng));
 }
 
 // the c tables of a grid plan onto the device
@@ -2478,48 +2477,51 @@ int init_device(mdp_engine *eng, DevCtx &d, const mdp_problem *p)
 {
     HIP_TRY(hipSetDevice(d.device));
     HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    int rc = MDP_OK;
+    mdp_plan_steps(eng, d.plan);  // until a grid is set: the steps the path alone implies (mdp_engine_kernel_name)
     // the generic path's tables (k_zpv / k_coefs / k_forward: colonisation
     // sums of every state, binomials, pair plans) only for an engine that
     // runs it: the direct and wide paths never touch them, so their set-up
     // does not load the library's precompiled kernels at all (CLI start-up)
-    if (!eng->jit && !eng->wide && (rc = init_generic(eng, d, p))) return rc;
-    if (eng->jit || eng->wide) {
-        std::vector<double> sv;
-        std::vector<uint2> items;
-        mdp_plan_item_tables(eng, sv, items);
-        std::vector<uint32_t> qitem = eng->qitem;
-        qitem.push_back(0u);
-        if ((rc = d.sv.assign(sv)) || (rc = d.items.assign(items)) ||
-            (rc = d.qstart.assign(eng->qstart)) || (rc = d.qitem.assign(qitem)) ||
-            (rc = d.qslot.assign(eng->qslot)) || (rc = d.qlane.assign(eng->qlane)) ||
-            (rc = d.islot.assign(eng->islot)))
+    if (eng->path == MdpPath::Generic) return init_generic(eng, d, p);
+    int rc = MDP_OK;
+    std::vector<double> sv;
+    std::vector<uint2> items;
+    mdp_plan_item_tables(eng, sv, items);
+    std::vector<uint32_t> qitem = eng->qitem;
+    qitem.push_back(0u);
+    if ((rc = d.sv.assign(sv)) || (rc = d.items.assign(items)) ||
+        (rc = d.qstart.assign(eng->qstart)) || (rc = d.qitem.assign(qitem)) ||
+        (rc = d.qslot.assign(eng->qslot)) || (rc = d.qlane.assign(eng->qlane)) ||
+        (rc = d.islot.assign(eng->islot)))
+        return rc;
+    // (k_qrows' LDS attribute is set before its first launch and the forward
+    // kernel loaded by set_grid_dev: nothing here loads a module)
+    if (!path_is_wide(eng->path)) return MDP_OK;
+    if ((rc = d.np_d.assign(eng->np)) || (rc = d.udesc_w.assign(eng->udesc_d))) return rc;
+    switch (eng->path) {
+    case MdpPath::WideMma:
+        if ((rc = d.mma_kt.assign(eng->mma_kt)) || (rc = d.mma_kbase.assign(eng->mma_kbase)) ||
+            (rc = d.mma_wplan.assign(eng->mma_wplan)) ||
+            (rc = d.mma_desc.assign(eng->mma_desc)) || (rc = d.mma_dbase.assign(eng->mma_dbase)))
             return rc;
-        if (eng->wide) {
-            if ((rc = d.np_d.assign(eng->np)) || (rc = d.udesc_w.assign(eng->udesc_d))) return rc;
-            if (eng->mma &&
-                ((rc = d.mma_kt.assign(eng->mma_kt)) || (rc = d.mma_kbase.assign(eng->mma_kbase)) ||
-                 (rc = d.mma_wplan.assign(eng->mma_wplan)) ||
-                 (rc = d.mma_desc.assign(eng->mma_desc)) || (rc = d.mma_dbase.assign(eng->mma_dbase))))
-                return rc;
-            if (eng->mmt &&
-                ((rc = d.mmt_kt.assign(eng->mmt_kt)) || (rc = d.mmt_ktile.assign(eng->mmt_ktile)) ||
-                 (rc = d.mmt_wplan.assign(eng->mmt_wplan)) || (rc = d.mmt_cidx.assign(eng->mmt_cidx))))
-                return rc;
-            if (eng->hs &&
-                ((rc = d.hs_kt.assign(eng->hs_kt)) || (rc = d.hs_cidx.assign(eng->hs_cidx)) ||
-                 (rc = d.hs_pbase.assign(eng->hs_pbase)) || (rc = d.hs_ppos.assign(eng->hs_ppos)) ||
-                 (rc = d.hs_dpos.assign(eng->hs_dpos)) || (rc = d.hs_dbase.assign(eng->hs_dbase)) ||
-                 (rc = d.hs_pk.assign(eng->hs_pk)) ||
-                 (rc = d.hs_wplan.assign(eng->hs_wplan)) || (rc = d.hs_pass.assign(eng->hs_pass)) ||
-                 (rc = d.hs_dpk.assign(eng->hs_dpk))))
-                return rc;
-            return wide_lds_limits(eng);
-        }
-        // (k_qrows' LDS attribute is set before its first launch and the
-        // forward kernel loaded by set_grid_dev: nothing here loads a module)
+        break;
+    case MdpPath::WideMmt:
+        if ((rc = d.mmt_kt.assign(eng->mmt_kt)) || (rc = d.mmt_ktile.assign(eng->mmt_ktile)) ||
+            (rc = d.mmt_wplan.assign(eng->mmt_wplan)) || (rc = d.mmt_cidx.assign(eng->mmt_cidx)))
+            return rc;
+        break;
+    case MdpPath::WideHs:
+        if ((rc = d.hs_kt.assign(eng->hs_kt)) || (rc = d.hs_cidx.assign(eng->hs_cidx)) ||
+            (rc = d.hs_pbase.assign(eng->hs_pbase)) || (rc = d.hs_ppos.assign(eng->hs_ppos)) ||
+            (rc = d.hs_dpos.assign(eng->hs_dpos)) || (rc = d.hs_dbase.assign(eng->hs_dbase)) ||
+            (rc = d.hs_pk.assign(eng->hs_pk)) ||
+            (rc = d.hs_wplan.assign(eng->hs_wplan)) || (rc = d.hs_pass.assign(eng->hs_pass)) ||
+            (rc = d.hs_dpk.assign(eng->hs_dpk)))
+            return rc;
+        break;
+    default: break;  // (k_fwd_wide reads the tables above)
     }
-    return MDP_OK;
+    return wide_lds_limits(eng);
 }
 
 // k_qrows may take more than 64 KB of dynamic LDS: raise its limit once per
@@ -2550,7 +2552,7 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
 {
     HIP_TRY(hipSetDevice(d.device));
     if (int prc = d.settle()) return prc;
-    if (!d.ncu && eng->jit && !eng->wide) {
+    if (!d.ncu && path_is_jit(eng->path)) {
         int v = 0;
         d.ncu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && v > 0
                     ? (uint32_t)v : 256u;
@@ -2573,7 +2575,7 @@ int set_grid_dev(mdp_engine *eng, DevCtx &d, const double *e, uint32_t ne, const
     if (g.pg_zero && g.n_pg) HIP_TRY(hipMemset(d.Pg.get(), 0, g.n_pg * sizeof(double)));
     if (g.zrows_lds > 64 * 1024 && (rc = set_lds_limit(k_zrows, g.zrows_lds))) return rc;
     if (!g.plist_identity && ((rc = d.plist.assign(g.plist)) || (rc = d.elist.assign(g.elist)))) return rc;
-    if (eng->jit && !eng->wide) {
+    if (path_is_jit(eng->path)) {
         if ((rc = jit_load(eng, d, g.variant))) return rc;
         mdp_plan_fwd_launch(eng, d.ct, ne, nc, g);  // (the variant's shape is settled once it is built)
     }
@@ -2626,58 +2628,63 @@ int launch_fwd_deg(const mdp_engine *eng, const DevCtx &d, double *out, OutStrid
     return MDP_OK;
 }
 
-int launch_forward(const mdp_engine *eng, const DevCtx &d, double *out, OutStrides os, hipStream_t s)
+// Slot 2 of the direct paths: the specialised forward kernel (a long series:
+// its chunk kernels)
+int launch_fwd_jit(const mdp_engine *eng, const DevCtx &d, double *out, OutStrides os, hipStream_t s)
 {
-    int rc;
-    if (eng->jit) {
-        // the launch as the grid plan shaped it (mdp_plan_fwd_launch)
-        const MdpGridPlan &g = d.plan;
-        if (g.fwd_threads > 0xffffffffull)
-            return mdp_set_error(MDP_EUNSUPPORTED, "grid %u x %u too large", d.ne, d.nc);
-        const uint32_t nthreads = (uint32_t)(g.fwd_threads * g.fwd_pro);
-        // mdp_fwd_jit's parameters (spom_jit.h declares them once, for the
-        // generated signature and for this struct)
-        MdpFwdJitArgs a;
-        a.tab = g.fused ? d.coltab.get() : d.Qrow.get();  // the table the variant stages first
-        a.cvals = d.c.get();
-        a.evals = g.fwd_listed ? d.elist.get() : d.e.get();  // a listed kernel reads e by list position
-        a.ct_len = d.ct.ct_len;
-        a.nlist = g.fwd_nlist;
-        a.ne = d.ne;
-        a.nc = d.nc;
-        a.plist = g.fwd_listed ? d.plist.get() : nullptr;
-        a.nblk = (uint32_t)g.fwd_nblk;
-        a.kmax = d.ct.kmax;
-        a.one = 1;
-        a.out = out;
-        a.ld_out = os.se;
-        a.out_cs = os.sc;
-        a.prior0 = eng->prior0;
-        a.vscr = d.vscr.get();
-        a.ldv = g.ldv;
-        a.stamps = d.stamps[2].get();
-        auto args = a.params();
-        static_assert(std::tuple_size<decltype(args)>::value == 19, "one kernelParams entry per parameter of mdp_fwd_jit");
-        if (!eng->chunks.empty()) {  // a long series: its chunks in order on the stream
-            const size_t nch = d.cfn.size();
-            if (nch != eng->chunks.size() || d.cqidx.size() != nch)
-                return mdp_set_error(MDP_EHIP, "forward chunks not loaded (%zu of %zu)", nch, eng->chunks.size());
-            for (size_t i = 0; i < nch; ++i) {
-                a.qidx = d.cqidx[i].get();  // the chunk's gather list (args points at the member)
-                HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], nthreads, 1, 1, g.fwd_block, 1, 1, 0, s,
-                                                 args.data(), nullptr, i == 0 ? t_kev.start : nullptr,
-                                                 i + 1 == nch ? t_kev.stop : nullptr, 0));
-            }
-            note_launch(eng, d, kFmtJitChunks, eng->maxA, nch,
-                        eng->chunks[0].qidx.empty() ? "" : ",gather");
-            return MDP_OK;
+    // the launch as the grid plan shaped it (mdp_plan_fwd_launch)
+    const MdpGridPlan &g = d.plan;
+    if (g.fwd_threads > 0xffffffffull)
+        return mdp_set_error(MDP_EUNSUPPORTED, "grid %u x %u too large", d.ne, d.nc);
+    const uint32_t nthreads = (uint32_t)(g.fwd_threads * g.fwd_pro);
+    // mdp_fwd_jit's parameters (spom_jit.h declares them once, for the
+    // generated signature and for this struct)
+    MdpFwdJitArgs a;
+    a.tab = g.fused ? d.coltab.get() : d.Qrow.get();  // the table the variant stages first
+    a.cvals = d.c.get();
+    a.evals = g.fwd_listed ? d.elist.get() : d.e.get();  // a listed kernel reads e by list position
+    a.ct_len = d.ct.ct_len;
+    a.nlist = g.fwd_nlist;
+    a.ne = d.ne;
+    a.nc = d.nc;
+    a.plist = g.fwd_listed ? d.plist.get() : nullptr;
+    a.nblk = (uint32_t)g.fwd_nblk;
+    a.kmax = d.ct.kmax;
+    a.one = 1;
+    a.out = out;
+    a.ld_out = os.se;
+    a.out_cs = os.sc;
+    a.prior0 = eng->prior0;
+    a.vscr = d.vscr.get();
+    a.ldv = g.ldv;
+    a.stamps = d.stamps[2].get();
+    auto args = a.params();
+    static_assert(std::tuple_size<decltype(args)>::value == 19, "one kernelParams entry per parameter of mdp_fwd_jit");
+    if (g.step[2] == MdpStep::FwdJitChunks) {  // a long series: its chunks in order on the stream
+        const size_t nch = d.cfn.size();
+        if (nch != eng->chunks.size() || d.cqidx.size() != nch)
+            return mdp_set_error(MDP_EHIP, "forward chunks not loaded (%zu of %zu)", nch, eng->chunks.size());
+        for (size_t i = 0; i < nch; ++i) {
+            a.qidx = d.cqidx[i].get();  // the chunk's gather list (args points at the member)
+            HIP_TRY(hipExtModuleLaunchKernel(d.cfn[i], nthreads, 1, 1, g.fwd_block, 1, 1, 0, s,
+                                             args.data(), nullptr, i == 0 ? t_kev.start : nullptr,
+                                             i + 1 == nch ? t_kev.stop : nullptr, 0));
         }
-        HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[g.variant], nthreads, 1, 1, g.fwd_block, 1, 1, g.fwd_lds, s, args.data(),
-                                         nullptr, t_kev.start, t_kev.stop, 0));
-        note_launch(eng, d, kFmtJit, g.fused ? "fused" : "reading", eng->maxA);
-        if (g.tall) note_launch(eng, d, kFmtJitTall, kJitKblockTall);
+        note_launch(eng, d, kFmtJitChunks, eng->maxA, nch,
+                    eng->chunks[0].qidx.empty() ? "" : ",gather");
         return MDP_OK;
     }
+    HIP_TRY(hipExtModuleLaunchKernel(d.jit_fn[g.variant], nthreads, 1, 1, g.fwd_block, 1, 1, g.fwd_lds, s, args.data(),
+                                     nullptr, t_kev.start, t_kev.stop, 0));
+    note_launch(eng, d, kFmtJit, g.fused ? "fused" : "reading", eng->maxA);
+    if (g.tall) note_launch(eng, d, kFmtJitTall, kJitKblockTall);
+    return MDP_OK;
+}
+
+// Slot 2 of the generic path
+int launch_fwd_generic(const mdp_engine *eng, const DevCtx &d, double *out, OutStrides os, hipStream_t s)
+{
+    int rc;
     switch (eng->variant / 100) {
     case 1: rc = launch_fwd_deg<1>(eng, d, out, os, s); break;
     case 2: rc = launch_fwd_deg<2>(eng, d, out, os, s); break;
@@ -2704,107 +2711,48 @@ int launch_coefs(const mdp_engine *eng, const DevCtx &d, hipStream_t s)
     return MDP_OK;
 }
 
-// Wide path, slot 1 (k_witems + k_wq per chunk of c values) or slot 2
-// (k_fwd_wide per chunk).  A profiled run times the slot as a whole: events
-// recorded around its launches.
-int launch_wide(const mdp_engine *eng, const DevCtx &d, int k, double *out, OutStrides os, hipStream_t s)
+// k_witems: the item factors of n c values from c0, in Pg rows of ldp
+void launch_witems(const mdp_engine *eng, const DevCtx &d, uint32_t c0, uint32_t n, uint32_t ldp, hipStream_t s)
+{
+    const dim3 gi((eng->nitems + kBlock - 1) / kBlock, n);
+    for_nv(eng, [&](auto nv) {
+        note_launch(eng, d, kFmtWitems, nv());
+        hipLaunchKernelGGL((k_witems<nv()>), gi, dim3(kBlock), 0, s, d.c.get(), d.nc, c0, eng->nvar, d.Zg.get(), d.sv.get(),
+                           eng->nitems, d.items.get(), d.Pg.get(), ldp);
+    });
+}
+
+// A slot of several launches (the Q-global paths' chunks of c values).  A
+// profiled run times the slot as a whole: events recorded around its launches.
+template <typename F>
+int launch_bracketed(hipStream_t s, F &&launches)
 {
     const KernelEvents ev = t_kev;
     t_kev = KernelEvents{};
     if (ev.start) HIP_TRY(hipEventRecord(ev.start, s));
-    auto witems = [&](uint32_t c0, uint32_t n, uint32_t ldp) {
-        const dim3 gi((eng->nitems + kBlock - 1) / kBlock, n);
-        for_nv(eng, [&](auto nv) {
-            note_launch(eng, d, kFmtWitems, nv());
-            hipLaunchKernelGGL((k_witems<nv()>), gi, dim3(kBlock), 0, s, d.c.get(), d.nc, c0, eng->nvar, d.Zg.get(), d.sv.get(),
-                               eng->nitems, d.items.get(), d.Pg.get(), ldp);
-        });
-    };
-    if (eng->hs) {
-        // slot 1: the item factors of every column when they fit one Pg
-        // block (kHsPgBytes), else nothing; slot 2: k_fwd_hs, or per column
-        // chunk k_witems then k_fwd_hs
-        const uint32_t cb = d.plan.wide_cb_items, ldp = eng->nitems + 1;
-        const bool one = cb >= d.nc;
-        if (k == 1) {
-            if (one && eng->nitems) witems(0, d.nc, ldp);
-        } else {
-            const uint32_t rt = eng->hs_rt, nb = eng->hs_nb, npb = (d.ne + mmt_pts(rt) - 1) / mmt_pts(rt);
-            for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
-                const uint32_t n = std::min(cb, d.nc - c0);
-                if (!one && eng->nitems) witems(c0, n, ldp);
-                const uint64_t nbk = (uint64_t)npb * n;
-                if (nbk > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_hs workgroups", (unsigned long long)nbk);
-                note_launch(eng, d, kFmtHs, rt, nb);
-                for_hs(eng, [&](auto RT, auto NB, auto NW) {
-                    hipLaunchKernelGGL((k_fwd_hs<RT(), NB(), NW()>), dim3((uint32_t)nbk), dim3(NW() * 64), hs_lds(eng), s,
-                                       d.Pg.get(), ldp, c0, d.np_d.get(), d.hs_kt.get(), d.hs_cidx.get(), d.hs_wplan.get(),
-                                       d.hs_pass.get(), d.hs_pbase.get(), d.hs_ppos.get(), d.hs_dpos.get(), d.hs_dbase.get(),
-                                       d.hs_dpk.get(), d.hs_pk.get(), eng->tmax, eng->prior0, d.e.get(),
-                                       d.ne, out, os.se, os.sc, eng->hs_probe);
-                });
-            }
-        }
-    } else if (k == 1) {
-        const uint32_t cb = d.plan.wide_cb_items;
-        for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
-            const uint32_t n = std::min(cb, d.nc - c0);
-            witems(c0, n, eng->nitems);
-            const dim3 gq((uint32_t)((eng->ldQ + kBlock - 1) / kBlock), n);
-            note_launch(eng, d, "k_wq");
-            hipLaunchKernelGGL(k_wq, gq, dim3(kBlock), 0, s, c0, eng->nitems, d.Pg.get(), eng->ncoef_d, d.qstart.get(), d.qitem.get(),
-                               d.Qrow.get(), (uint32_t)eng->ldQ);
-        }
-    } else if (eng->mmt) {  // the matrix-core forward: every c in one launch, blocks dealt XCD-aware
-        const uint32_t rt = eng->mmt_rt, rows = eng->mmt_rows, npb = (d.ne + mmt_pts(rt) - 1) / mmt_pts(rt);
-        const bool db = mmt_shape(eng).db;
-        const uint64_t nb = (uint64_t)npb * d.nc;
-        if (nb > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_mmt workgroups", (unsigned long long)nb);
-        note_launch(eng, d, kFmtMmt, rt, rows, db ? "2buf" : "1buf");
-        for_mmt(eng, [&](auto RT, auto ROWS, auto DB) {
-            hipLaunchKernelGGL((k_fwd_mmt<RT(), ROWS(), DB()>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s,
-                               d.Qrow.get(), (uint32_t)eng->ldQ, d.np_d.get(), d.mmt_kt.get(), d.mmt_cidx.get(), d.mmt_ktile.get(),
-                               d.mmt_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, eng->maxA, out, os.se, os.sc);
-        });
-    } else if (eng->mma) {  // round 5's matrix-core forward (MDP_WIDE_MMA=1; years of up to 256 states)
-        uint32_t se = os.se, sc = os.sc;
-        for (uint32_t c0 = 0; c0 < d.nc; c0 += 65535) {
-            const uint32_t n = std::min(65535u, d.nc - c0);
-            const uint32_t pts = mma_pts(eng->mma_npm);
-            const dim3 g((d.ne + pts - 1) / pts, n);
-            note_launch(eng, d, kFmtMma, eng->mma_npm);
-            for_mma(eng, [&](auto NPM) {
-                hipLaunchKernelGGL((k_fwd_mma<NPM()>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ,
-                                   d.np_d.get(), d.mma_kt.get(), d.mma_kbase.get(), d.mma_desc.get(), d.mma_dbase.get(),
-                                   d.mma_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, eng->mma_ktmax,
-                                   eng->ncoef_d, out, se, sc);
-            });
-        }
-    } else {
-        const uint32_t cb = d.plan.wide_cb_fwd;
-        uint32_t se = os.se, sc = os.sc;
-        for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
-            const uint32_t n = std::min(cb, d.nc - c0);
-            const dim3 g((d.ne + kBlock - 1) / kBlock, n);
-            note_launch(eng, d, "k_fwd_wide");
-            hipLaunchKernelGGL(k_fwd_wide, g, dim3(kBlock), wide_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ, d.udesc_w.get(),
-                               d.np_d.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, d.V.get(), eng->npmax, out, se,
-                               sc);
-        }
-    }
+    if (int rc = launches()) return rc;
     HIP_TRY(hipGetLastError());
     if (ev.stop) HIP_TRY(hipEventRecord(ev.stop, s));
     return MDP_OK;
 }
 
-bool slot_active(const mdp_engine *eng, const DevCtx &d, int k) { return mdp_plan_slot_active(eng, d.plan, k); }
-
+// What slot k of the grid runs (MdpGridPlan::step, mdp_plan_steps): one case
+// per step, none left to a default.
 int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, hipStream_t s)
 {
-    if (!slot_active(eng, d, k)) return MDP_OK;
-    if ((eng->wide && k > 0) || (eng->jit && eng->qglobal && k == 1)) return launch_wide(eng, d, k, out, os, s);
-    if (k == 2) return launch_forward(eng, d, out, os, s);
-    if ((eng->jit || eng->wide) && k == 0) {  // Z rows
+    switch (d.plan.step[k]) {
+    case MdpStep::None: return MDP_OK;
+    case MdpStep::Zpv: {
+        dim3 grid((eng->nstates + kZpvJ - 1) / kZpvJ, (d.nc + kZpvCT - 1) / kZpvCT);
+        note_launch(eng, d, "k_zpv");
+        MDP_LAUNCH(k_zpv, grid, dim3(kBlock), 0, s, d.S.get(), eng->nstates, eng->n - eng->nvar, eng->nvar, d.c.get(),
+                   d.nc, d.ZPV.get(), d.stamps[0].get());
+        HIP_TRY(hipGetLastError());
+        return MDP_OK;
+    }
+    case MdpStep::Coefs: return launch_coefs(eng, d, s);
+    case MdpStep::FwdGeneric: return launch_fwd_generic(eng, d, out, os, s);
+    case MdpStep::Zrows: {
         const uint32_t kmax = d.ct.kmax;
         const dim3 grid((d.nc + 64 * kZC - 1) / (64 * kZC), (eng->nj + kZRows - 1) / kZRows);
         note_launch(eng, d, "k_zrows");
@@ -2813,7 +2761,7 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
         HIP_TRY(hipGetLastError());
         return MDP_OK;
     }
-    if (eng->jit) {  // k == 1: Q rows
+    case MdpStep::Qrows: {
         if (int rc = qrows_attrs(eng, d)) return rc;
         const uint32_t cb = d.plan.qrows_cb;
         const dim3 grid((d.nc + cb - 1) / cb);
@@ -2829,15 +2777,94 @@ int launch_slot(mdp_engine *eng, DevCtx &d, int k, double *out, OutStrides os, h
         HIP_TRY(hipGetLastError());
         return MDP_OK;
     }
-    if (k == 0) {
-        dim3 grid((eng->nstates + kZpvJ - 1) / kZpvJ, (d.nc + kZpvCT - 1) / kZpvCT);
-        note_launch(eng, d, "k_zpv");
-        MDP_LAUNCH(k_zpv, grid, dim3(kBlock), 0, s, d.S.get(), eng->nstates, eng->n - eng->nvar, eng->nvar, d.c.get(),
-                   d.nc, d.ZPV.get(), d.stamps[0].get());
-        HIP_TRY(hipGetLastError());
-        return MDP_OK;
+    case MdpStep::ItemsQ:  // k_witems + k_wq per chunk of c values
+        return launch_bracketed(s, [&]() {
+            const uint32_t cb = d.plan.wide_cb_items;
+            for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
+                const uint32_t n = std::min(cb, d.nc - c0);
+                launch_witems(eng, d, c0, n, eng->nitems, s);
+                const dim3 gq((uint32_t)((eng->ldQ + kBlock - 1) / kBlock), n);
+                note_launch(eng, d, "k_wq");
+                hipLaunchKernelGGL(k_wq, gq, dim3(kBlock), 0, s, c0, eng->nitems, d.Pg.get(), eng->ncoef_d, d.qstart.get(),
+                                   d.qitem.get(), d.Qrow.get(), (uint32_t)eng->ldQ);
+            }
+            return MDP_OK;
+        });
+    case MdpStep::ItemsAll:  // k_fwd_hs: the item factors of every column when they fit one Pg block (kHsPgBytes), else nothing
+        return launch_bracketed(s, [&]() {
+            if (d.plan.wide_cb_items >= d.nc) launch_witems(eng, d, 0, d.nc, eng->nitems + 1, s);
+            return MDP_OK;
+        });
+    case MdpStep::FwdJit:
+    case MdpStep::FwdJitChunks: return launch_fwd_jit(eng, d, out, os, s);
+    case MdpStep::FwdHs:  // k_fwd_hs, or per column chunk k_witems then k_fwd_hs
+        return launch_bracketed(s, [&]() {
+            const uint32_t cb = d.plan.wide_cb_items, ldp = eng->nitems + 1;
+            const bool one = cb >= d.nc;
+            const uint32_t rt = eng->hs_rt, nb = eng->hs_nb, npb = (d.ne + mmt_pts(rt) - 1) / mmt_pts(rt);
+            for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
+                const uint32_t n = std::min(cb, d.nc - c0);
+                if (!one && eng->nitems) launch_witems(eng, d, c0, n, ldp, s);
+                const uint64_t nbk = (uint64_t)npb * n;
+                if (nbk > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_hs workgroups", (unsigned long long)nbk);
+                note_launch(eng, d, kFmtHs, rt, nb);
+                for_hs(eng, [&](auto RT, auto NB, auto NW) {
+                    hipLaunchKernelGGL((k_fwd_hs<RT(), NB(), NW()>), dim3((uint32_t)nbk), dim3(NW() * 64), hs_lds(eng), s,
+                                       d.Pg.get(), ldp, c0, d.np_d.get(), d.hs_kt.get(), d.hs_cidx.get(), d.hs_wplan.get(),
+                                       d.hs_pass.get(), d.hs_pbase.get(), d.hs_ppos.get(), d.hs_dpos.get(), d.hs_dbase.get(),
+                                       d.hs_dpk.get(), d.hs_pk.get(), eng->tmax, eng->prior0, d.e.get(),
+                                       d.ne, out, os.se, os.sc, eng->hs_probe);
+                });
+            }
+            return MDP_OK;
+        });
+    case MdpStep::FwdMmt:  // the matrix-core forward: every c in one launch, blocks dealt XCD-aware
+        return launch_bracketed(s, [&]() {
+            const uint32_t rt = eng->mmt_rt, rows = eng->mmt_rows, npb = (d.ne + mmt_pts(rt) - 1) / mmt_pts(rt);
+            const bool db = mmt_shape(eng).db;
+            const uint64_t nb = (uint64_t)npb * d.nc;
+            if (nb > 0x7fffffffull) return mdp_set_error(MDP_EUNSUPPORTED, "grid of %llu k_fwd_mmt workgroups", (unsigned long long)nb);
+            note_launch(eng, d, kFmtMmt, rt, rows, db ? "2buf" : "1buf");
+            for_mmt(eng, [&](auto RT, auto ROWS, auto DB) {
+                hipLaunchKernelGGL((k_fwd_mmt<RT(), ROWS(), DB()>), dim3((uint32_t)nb), dim3(kMmaThreads), mmt_lds(eng), s,
+                                   d.Qrow.get(), (uint32_t)eng->ldQ, d.np_d.get(), d.mmt_kt.get(), d.mmt_cidx.get(), d.mmt_ktile.get(),
+                                   d.mmt_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, eng->maxA, out, os.se, os.sc);
+            });
+            return MDP_OK;
+        });
+    case MdpStep::FwdMma:  // round 5's matrix-core forward (MDP_WIDE_MMA=1; years of up to 256 states)
+        return launch_bracketed(s, [&]() {
+            uint32_t se = os.se, sc = os.sc;
+            for (uint32_t c0 = 0; c0 < d.nc; c0 += 65535) {
+                const uint32_t n = std::min(65535u, d.nc - c0);
+                const uint32_t pts = mma_pts(eng->mma_npm);
+                const dim3 g((d.ne + pts - 1) / pts, n);
+                note_launch(eng, d, kFmtMma, eng->mma_npm);
+                for_mma(eng, [&](auto NPM) {
+                    hipLaunchKernelGGL((k_fwd_mma<NPM()>), g, dim3(kMmaThreads), mma_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ,
+                                       d.np_d.get(), d.mma_kt.get(), d.mma_kbase.get(), d.mma_desc.get(), d.mma_dbase.get(),
+                                       d.mma_wplan.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, eng->mma_ktmax,
+                                       eng->ncoef_d, out, se, sc);
+                });
+            }
+            return MDP_OK;
+        });
+    case MdpStep::FwdPlain:  // k_fwd_wide per chunk of c values
+        return launch_bracketed(s, [&]() {
+            const uint32_t cb = d.plan.wide_cb_fwd;
+            uint32_t se = os.se, sc = os.sc;
+            for (uint32_t c0 = 0; c0 < d.nc; c0 += cb) {
+                const uint32_t n = std::min(cb, d.nc - c0);
+                const dim3 g((d.ne + kBlock - 1) / kBlock, n);
+                note_launch(eng, d, "k_fwd_wide");
+                hipLaunchKernelGGL(k_fwd_wide, g, dim3(kBlock), wide_lds(eng), s, d.Qrow.get(), (uint32_t)eng->ldQ, d.udesc_w.get(),
+                                   d.np_d.get(), eng->tmax, eng->prior0, d.e.get(), d.ne, c0, eng->maxA, d.V.get(), eng->npmax, out, se,
+                                   sc);
+            }
+            return MDP_OK;
+        });
     }
-    return launch_coefs(eng, d, s);
+    return MDP_OK;  // (not reached: every step returns above)
 }
 
 int run_dev(mdp_engine *eng, DevCtx &d, double *out, OutStrides os, hipStream_t s)
@@ -2865,7 +2892,7 @@ int run_dev(mdp_engine *eng, DevCtx &d, double *out, OutStrides os, hipStream_t 
         ~Reset() { t_kev = KernelEvents{}; }
     } reset;
     for (int k = 0; k < 3; ++k) {
-        if (!slot_active(eng, d, k)) continue;
+        if (d.plan.step[k] == MdpStep::None) continue;
         // only launched kernels carry events (no marker packets between kernels)
         t_kev = prof ? KernelEvents{ev[2 * k], ev[2 * k + 1]} : KernelEvents{};
         if (prof) d.ev_mask.back() |= (uint8_t)(1u << k);
@@ -2887,7 +2914,7 @@ int time_kernels(mdp_engine *eng, DevCtx &d, double *out, OutStrides os, hipStre
     HIP_TRY(hipEventCreate(&b));
     for (int k = 0; k < 3; ++k) {
         ms[k] = 0.0;
-        if (!slot_active(eng, d, k)) continue;
+        if (d.plan.step[k] == MdpStep::None) continue;
         if ((rc = launch_slot(eng, d, k, out, os, s))) break;  // warm
         (void)hipEventRecord(a, s);
         for (int r = 0; r < reps && !rc; ++r) rc = launch_slot(eng, d, k, out, os, s);
@@ -3121,7 +3148,8 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
     HIP_TRY(hipDeviceSynchronize());
     const char *names[3] = {"k_zpv", "k_coefs", "k_forward_lds"};
     int slots[3] = {3, 5, 3};
-    if (eng->jit) {  // direct path: k_qrows and the hipRTC forward kernel
+    const bool jit = path_is_jit(eng->path);
+    if (jit) {  // direct path: k_qrows and the hipRTC forward kernel
         names[1] = "k_qrows";
         names[2] = "k_forward(jit)";
         slots[0] = 0;
@@ -3140,7 +3168,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
         size_t nb = 0;
         for (size_t b = 0; b < d.plan.nst[k]; ++b) {
             const unsigned long long *st = &h[b * kStampSlots];
-            const int last = ((k == 2 && d.plan.fused) || k == 1) && eng->jit ? 3 : slots[k] - 1;
+            const int last = ((k == 2 && d.plan.fused) || k == 1) && jit ? 3 : slots[k] - 1;
             if (!st[0] || !st[last] || st[last] < st[0]) continue;
             ++nb;
             rs0 = std::min(rs0, st[6]);
@@ -3150,7 +3178,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
             t0 = std::min(t0, st[0]);
             t1 = std::max(t1, st[last]);
             // the fused forward kernel stamps slots 4 and 5 between 0 and 1
-            const bool fz = ((k == 2 && d.plan.fused) || k == 1) && eng->jit && slots[k] == 6;
+            const bool fz = ((k == 2 && d.plan.fused) || k == 1) && jit && slots[k] == 6;
             static const int seq_plain[6] = {0, 1, 2, 3, 4, 5}, seq_fused[6] = {0, 4, 5, 1, 2, 3};
             const int *seq = fz ? seq_fused : seq_plain;
             for (int q = 1; q < slots[k]; ++q) mean[q] += (double)(st[seq[q]] - st[seq[q - 1]]);
@@ -3186,7 +3214,7 @@ int mdp_engine_diag_report(mdp_engine *eng, char *buf, size_t len)
                 if (w > 0) used = std::min(len - 1, used + (size_t)w);
             }
         }
-        if (k == 2 && nb && !eng->jit) {  // forward: cycles summed over run ops / general ops (wave 0)
+        if (k == 2 && nb && !jit) {  // forward: cycles summed over run ops / general ops (wave 0)
             double cr = 0, cg = 0;
             for (size_t b = 0; b < d.plan.nst[k]; ++b) {
                 const unsigned long long *st = &h[b * kStampSlots];
@@ -3249,13 +3277,29 @@ int mdp_engine_kernel_ms(mdp_engine *eng, double *ms, int max_k)
 const char *mdp_engine_kernel_name(const mdp_engine *eng, int k)
 {
     if (!eng || k < 0 || k >= 3) return "";
-    if (eng->wide && eng->hs) return k == 0 && eng->nitems ? "k_zrows" : k == 1 && eng->nitems ? "k_witems" : k == 2 ? "k_fwd_hs" : "";
-    if (eng->wide) return k < 2 && !eng->nitems ? "" : k == 2 && eng->mmt ? "k_fwd_mmt" : k == 2 && eng->mma ? "k_fwd_mma" : kKernelNames[2][k];
-    if (eng->jit && eng->qglobal)  // Q rows built in HBM, then the hipRTC forward kernel
-        return k < 2 && !eng->nitems ? "" : k == 2 ? "k_forward" : kKernelNames[2][k];
-    // direct path: Z rows inside k_qrows (slot 0 idle); fused: one kernel
-    if (eng->jit && (k == 0 || (k == 1 && (eng->devs.empty() || eng->devs[0].plan.fused)))) return "";
-    return kKernelNames[eng->jit ? 1 : 0][k];
+    // the slot's step in the first context's grid plan (before a grid is set:
+    // the one the path alone implies, init_device); an engine without a
+    // device names what a fused grid would run
+    MdpGridPlan g;
+    g.fused = true;
+    if (eng->devs.empty()) mdp_plan_steps(eng, g);
+    switch (eng->devs.empty() ? g.step[k] : eng->devs[0].plan.step[k]) {
+    case MdpStep::None: return "";
+    case MdpStep::Zpv: return "k_zpv";
+    case MdpStep::Coefs: return "k_coefs";
+    case MdpStep::Zrows: return "k_zrows";
+    case MdpStep::Qrows: return "k_qrows";
+    case MdpStep::ItemsQ: return "k_witems+k_wq";
+    case MdpStep::ItemsAll: return "k_witems";
+    case MdpStep::FwdGeneric:
+    case MdpStep::FwdJit:
+    case MdpStep::FwdJitChunks: return "k_forward";
+    case MdpStep::FwdHs: return "k_fwd_hs";
+    case MdpStep::FwdMmt: return "k_fwd_mmt";
+    case MdpStep::FwdMma: return "k_fwd_mma";
+    case MdpStep::FwdPlain: return "k_fwd_wide";
+    }
+    return "";
 }
 
 int mdp_log_check(const double *x, double *y, size_t n)

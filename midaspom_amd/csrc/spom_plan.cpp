@@ -75,28 +75,31 @@ constexpr size_t kJitChunkQ = kJitMaxLds / sizeof(double) - 2;  // gathered coef
 
 constexpr int kDegBuckets[] = {4, 8, 16, 24};
 
-int select_variant(MdpEnginePlan *eng)
+int select_variant(MdpEnginePlan *eng, bool &wide)
 {
     uint32_t np = 0;
     for (uint32_t b : {1u, 2u, 4u, 8u, 16u})
         if (eng->npmax <= b) { np = b; break; }
     // a year with more than 16 states (over 4 missing patches) exceeds the
     // register-resident forward kernels: the wide path takes the problem
-    if (!np) eng->wide = true;
+    if (!np) wide = true;
     uint32_t deg = 0;
     for (int b : kDegBuckets)
         if (eng->maxA <= (uint32_t)b) { deg = (uint32_t)b; break; }
     if (!deg) return mdp_set_error(MDP_EUNSUPPORTED, "%u occupied patches in one state (max %d)", eng->maxA, kMaxDeg);
     eng->deg = deg;
-    eng->variant = eng->wide ? 20000u + deg : np * 100 + deg;
+    eng->variant = wide ? 20000u + deg : np * 100 + deg;
     return MDP_OK;
 }
 
 // Host plan: distinct transition pairs (sorted by |A&B| descending for load
 // balance in k_coefs), Q offsets, the per-use pair index in forward order, and
-// the step program (runs of 1x1 transitions / general years).
-int build_plan(MdpEnginePlan *eng, const mdp_problem *p)
+// the step program (runs of 1x1 transitions / general years).  wide: the
+// problem is the wide kernels' (MDP_WIDE=1, or a year of more than 16 states),
+// which take neither.
+int build_plan(MdpEnginePlan *eng, const mdp_problem *p, bool &wide)
 {
+    wide = false;
     eng->n = p->n;
     eng->tmax = p->tmax;
     eng->nvar = p->nvar;
@@ -105,7 +108,7 @@ int build_plan(MdpEnginePlan *eng, const mdp_problem *p)
         return mdp_set_error(MDP_EUNSUPPORTED, "%u variable columns (engine limit 24)", p->nvar);
     eng->nstates = 1u << p->nvar;
     eng->prior0 = (double)p->prior[0];
-    if (const char *wv = eng->opts.get("MDP_WIDE")) eng->wide = atoi(wv) != 0;
+    if (const char *wv = eng->opts.get("MDP_WIDE")) wide = atoi(wv) != 0;
     eng->np.resize(p->tmax);
     eng->npmax = 1;
     for (uint32_t t = 0; t < p->tmax; ++t) {
@@ -176,9 +179,9 @@ int build_plan(MdpEnginePlan *eng, const mdp_problem *p)
     eng->npairs = (uint32_t)eng->pairA.size();
     eng->nuses = (uint32_t)eng->use_pair.size();
     eng->ncoef = off;
-    int rc = select_variant(eng);
+    int rc = select_variant(eng, wide);
     if (rc) return rc;
-    if (eng->wide) return MDP_OK;  // no step program / k_coefs plan: build_wide_plan
+    if (wide) return MDP_OK;  // no step program / k_coefs plan: build_wide_plan
     // step program
     for (uint32_t t = 1; t < p->tmax;) {
         if (eng->np[t - 1] == 1 && eng->np[t] == 1) {
@@ -554,14 +557,15 @@ void plan_waves(const std::vector<uint32_t> &nch, uint32_t tmaxit, uint32_t inpl
 //    smaller years give every tile a wave and the spare waves to the tiles
 //    with the longest lists, each tile's list split into as many slices
 //    (at least two chunks each).
-void build_mmt_plan(MdpEnginePlan *eng)
+// False: the problem is not k_fwd_mmt's.
+bool build_mmt_plan(MdpEnginePlan *eng)
 {
-    if (eng->npmax > 1024 || eng->maxA > 24 || eng->tmax < 2) return;
+    if (eng->npmax > 1024 || eng->maxA > 24 || eng->tmax < 2) return false;
     const MmtShape shp = mmt_shape(eng);
     const uint32_t rows = shp.rows, rt = shp.rt, pts = mmt_pts(rt), ps = mmt_ps(rt);
     const uint32_t tmaxit = rows > 256 ? rows / 256 : 1, cw = 4 * mmt_u(rt), inplace = shp.db ? 2u : 1u;
     const uint32_t none = (uint32_t)eng->ncoef_d;
-    if (none > kOffMask) return;
+    if (none > kOffMask) return false;
     eng->mmt_rt = rt;
     eng->mmt_rows = rows;
     eng->mmt_kt.clear();
@@ -607,11 +611,12 @@ void build_mmt_plan(MdpEnginePlan *eng)
     }
     eng->mmt_flops_pt = fl + 2.0 * (eng->maxA + 1) + (double)eng->np[eng->tmax - 1];
     // (the offsets' table is the plan's largest: 64 bytes per K entry)
-    eng->mmt = mmt_lds(eng) <= eng->lds_max && eng->mmt_kt.size() < (1u << 26) && (size_t)none * 8u < 0xffffffffu;
-    if (!eng->mmt) {
+    const bool ok = mmt_lds(eng) <= eng->lds_max && eng->mmt_kt.size() < (1u << 26) && (size_t)none * 8u < 0xffffffffu;
+    if (!ok) {
         eng->mmt_kt.clear();
         eng->mmt_cidx.clear();
     }
+    return ok;
 }
 
 // k_fwd_hs's tables (c-independent; nvar <= 10, years of at most 1 024
@@ -630,12 +635,11 @@ void build_mmt_plan(MdpEnginePlan *eng)
 //    below B, padded states and padded entries);
 //  * the states' cube positions in tile order (~0: padding), the free 16-row
 //    park blocks (no state of the year in them), the wave plan.
-// Year 0's positions head dpos.  Refused (hs = false: k_fwd_mmt runs) for a
+// Year 0's positions head dpos.  Refused (false: k_fwd_mmt runs) for a
 // year with a repeated state or an item the direct plan lacks.
-void build_hs_plan(MdpEnginePlan *eng)
+bool build_hs_plan(MdpEnginePlan *eng)
 {
-    eng->hs = false;
-    if (eng->nvar > 10 || eng->tmax < 2 || eng->npmax > 1024 || eng->ystate.size() < eng->tmax) return;
+    if (eng->nvar > 10 || eng->tmax < 2 || eng->npmax > 1024 || eng->ystate.size() < eng->tmax) return false;
     const uint32_t nb = std::max<uint32_t>(8u, eng->nvar);
     // waves a block (MDP_HS_WAVES): 8 for 8 variable patches (32 points, a
     // 64 KiB cube: two blocks a CU, whose phases overlap; measured 5 % faster
@@ -646,7 +650,7 @@ void build_hs_plan(MdpEnginePlan *eng)
     const uint32_t rt = nb == 8 ? (nw == 8 ? 2u : 4u) : nb == 9 ? 2u : 1u, pts = mmt_pts(rt);
     const uint32_t ncube = 1u << nb, tmaxit = ncube / 16 > nw ? ncube / 16 / nw : 1u, cw = 4 * mmt_u(rt);
     const uint32_t zero = eng->nitems;  // the Pg row's zero slot
-    if ((uint64_t)zero * 8u >= 0xffffffffull) return;
+    if ((uint64_t)zero * 8u >= 0xffffffffull) return false;
     // patches per v Pe pass (MDP_HS_RADIX, 1 .. kHsRadix; default 4, the
     // measured best: profiles/r06/hs -- 1 024 cosets x points fill the block
     // in one sweep; 5 left half the threads idle on 1 024-state years)
@@ -681,14 +685,14 @@ void build_hs_plan(MdpEnginePlan *eng)
             if (st(t, l) < ncube) seen[st(t, l)] = 0;
         return ok;
     };
-    if (!distinct(0)) return;
+    if (!distinct(0)) return false;
     for (uint32_t l = 0; l < (eng->np[0] + 15) / 16 * 16; ++l) eng->hs_dpos.push_back(l < eng->np[0] ? st(0, l) : ~0u);
     double fb = 0.0, fm = 0.0;
     std::vector<uint8_t> live(ncube);
     std::vector<uint32_t> lv;
     for (uint32_t t = 1; t < eng->tmax; ++t) {
         const uint32_t npp = eng->np[t - 1], npc = eng->np[t], ncol = (npc + 15) / 16;
-        if (!distinct(t)) return;
+        if (!distinct(t)) return false;
         // butterfly passes
         std::fill(live.begin(), live.end(), 0);
         lv.clear();
@@ -860,7 +864,7 @@ void build_hs_plan(MdpEnginePlan *eng)
                     uint32_t o = zero;
                     if (i < npc && !(j & ~st(t, ord[i]))) {
                         auto it = item.find(((uint64_t)j << 32) | st(t, ord[i]));
-                        if (it == item.end()) return;
+                        if (it == item.end()) return false;
                         o = it->second;
                     }
                     eng->hs_cidx.push_back(o * 8u);
@@ -909,15 +913,17 @@ void build_hs_plan(MdpEnginePlan *eng)
     eng->hs_nb = nb;
     eng->hs_nw = nw;
     if (const char *pv = eng->opts.get("MDP_HS_PROBE")) eng->hs_probe = (uint32_t)atoi(pv) & 7u;
-    eng->hs = hs_lds(eng) <= eng->lds_max && eng->hs_kt.size() < (1u << 26);
+    return hs_lds(eng) <= eng->lds_max && eng->hs_kt.size() < (1u << 26);
 }
 
 // Wide-path plan: the direct plan's groups, items and per-use descriptors,
 // plus the FP64 work per grid point of k_fwd_wide (every use a (nX+1)-term
 // dot product with a weight multiply per term, one FMA into the state
-// vector; the per-lane power tables; the final prior sum).
-int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p)
+// vector; the per-lane power tables; the final prior sum).  path: the wide
+// forward the tables were built for.
+int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p, MdpPath &path)
 {
+    path = MdpPath::WidePlain;
     int rc = build_direct_plan(eng, p);
     if (rc) return rc;
     // Q rows with at least one zero slot past the coefficients (slot ncoef:
@@ -938,11 +944,8 @@ int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p)
     // / 5.8x faster on 128 / 256 / 512 / 1 024 states, 1.27x slower on 64)
     const char *mv = eng->opts.get("MDP_WIDE_MMA");
     const int mmode = mv ? atoi(mv) : (eng->npmax > 64 ? 3 : 2);
-    eng->mmt = false;
-    eng->hs = false;
-    if (mmode == 3) build_hs_plan(eng);
-    if (mmode == 2 || (mmode == 3 && !eng->hs)) build_mmt_plan(eng);
-    eng->mma = false;
+    if (mmode == 3 && build_hs_plan(eng)) path = MdpPath::WideHs;
+    else if ((mmode == 2 || mmode == 3) && build_mmt_plan(eng)) path = MdpPath::WideMmt;
     if (eng->npmax <= 256 && eng->maxA <= 24) {
         if (mmode == 1) {
             const uint32_t npm = eng->npmax <= 64 ? 64u : eng->npmax <= 128 ? 128u : 256u;
@@ -1009,7 +1012,7 @@ int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p)
             for (uint32_t i = 0; i < 4 * kMmaU; ++i) eng->mma_kt.push_back(make_uint2(0u, 0u));
             if (eng->mma_desc.empty()) eng->mma_desc.push_back(none);
             const size_t lmax = eng->lds_max;
-            eng->mma = mma_lds(eng) <= lmax && none <= kOffMask && !pad_overflow;
+            if (mma_lds(eng) <= lmax && none <= kOffMask && !pad_overflow) path = MdpPath::WideMma;
         }
     }
     return MDP_OK;
@@ -1159,7 +1162,7 @@ namespace {
 // or state vectors in LDS
 bool fused_path(const MdpEnginePlan *eng)
 {
-    return eng->jit && !eng->wide && !eng->qglobal && eng->chunks.empty() && !eng->jit_plan.vlds;
+    return eng->path == MdpPath::Direct && eng->chunks.empty() && !eng->jit_plan.vlds;
 }
 
 // The c tables for the bound cmax.
@@ -1266,8 +1269,9 @@ int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uin
         const double x = e[i] > 1.0 ? 1.0 : e[i];
         g.ne_sform += x < 1.0 - x;
     }
-    const bool qglobal = eng->wide || eng->qglobal;  // Q rows from k_zrows + k_witems + k_wq
-    if (eng->wide || eng->jit) {
+    const MdpPath path = eng->path;
+    const bool qglobal = path_q_global(path);  // Q rows from k_zrows + k_witems + k_wq
+    if (path != MdpPath::Generic) {
         double cmax = eng->cbound;
         for (uint32_t i = 0; i < nc; ++i) cmax = std::max(cmax, std::fabs(c[i]));
         g.n_qrow = (size_t)nc * eng->ldQ;
@@ -1287,7 +1291,7 @@ int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uin
     const char *cv = qglobal ? eng->opts.get("MDP_WIDE_CB") : nullptr;
     const int forced_cb = cv ? std::max(1, atoi(cv)) : 0;
     const size_t most_c = std::max<size_t>(1, std::min<size_t>(nc, 65535));  // a launch's grid y
-    if (qglobal && eng->hs) {  // k_fwd_hs reads the item factors of its columns: rows of nitems + 1 (zero slot)
+    if (path == MdpPath::WideHs) {  // k_fwd_hs reads the item factors of its columns: rows of nitems + 1 (zero slot)
         const size_t ldp = (size_t)eng->nitems + 1;
         g.wide_cb_items = wide_cb(nc, kHsPgBytes / 8 / ldp, forced_cb);
         g.n_pg = (size_t)g.wide_cb_items * ldp;
@@ -1296,14 +1300,14 @@ int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uin
         g.wide_cb_items = wide_cb(most_c, kWidePgBytes / 8 / std::max<size_t>(1, eng->nitems), forced_cb);
         g.n_pg = (size_t)g.wide_cb_items * eng->nitems + 1;
     }
-    if (eng->wide) {
+    if (path_is_wide(path)) {
         // c values per k_fwd_wide launch: the two state vectors of every
         // point of a launch within kWideVBytes (the matrix-core forwards keep
-        // them in LDS)
+        // them in LDS; k_fwd_hs does too, its reservation is unused)
         const size_t ne_pad = (size_t)std::max<uint32_t>(1u, (ne + kBlock - 1) / kBlock) * kBlock;
         g.wide_cb_fwd = wide_cb(most_c, kWideVBytes / 8 / (2 * (size_t)eng->npmax * ne_pad), forced_cb);
-        if (!eng->mma && !eng->mmt) g.n_v = 2 * (size_t)eng->npmax * g.wide_cb_fwd * ne_pad;
-    } else if (eng->jit) {
+        if (path == MdpPath::WidePlain || path == MdpPath::WideHs) g.n_v = 2 * (size_t)eng->npmax * g.wide_cb_fwd * ne_pad;
+    } else if (path_is_jit(path)) {
         // forward kernels with several points per lane read them from a list
         // that puts only e rows of one ratio form in a lane (spom_jit.cpp)
         const uint32_t epl = (uint32_t)eng->jit_epl;  // (the fused variant lists at the reading variant's: jit_source)
@@ -1352,8 +1356,9 @@ int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uin
         g.n_r = (size_t)nc * ldR_of(eng);
         if (!eng->lds_part) g.n_gpart = (size_t)nc * eng->partP.size() * (eng->nvar + 1);
     }
+    mdp_plan_steps(eng, g);
     if (eng->diag) {
-        g.nst[0] = eng->jit ? (size_t)nc : (size_t)((eng->nstates + kZpvJ - 1) / kZpvJ) * ((nc + kZpvCT - 1) / kZpvCT);
+        g.nst[0] = path_is_jit(path) ? (size_t)nc : (size_t)((eng->nstates + kZpvJ - 1) / kZpvJ) * ((nc + kZpvCT - 1) / kZpvCT);
         g.nst[1] = nc;
         g.nst[2] = (size_t)nc * ((ne + kBlock - 1) / kBlock);  // >= the JIT grid (EPL >= 1)
     }
@@ -1380,13 +1385,24 @@ void mdp_plan_fwd_launch(const MdpEnginePlan *eng, const MdpCTables &ct, uint32_
     g.fwd_lds = g.fused ? (ct.ct_len + 2) * (uint32_t)sizeof(double) : 0u;  // + staging scratch
 }
 
-bool mdp_plan_slot_active(const MdpEnginePlan *eng, const MdpGridPlan &g, int k)
+void mdp_plan_steps(const MdpEnginePlan *eng, MdpGridPlan &g)
 {
-    if (eng->wide || (eng->jit && eng->qglobal)) return k == 2 || eng->nitems;
-    // the direct path computes its Z rows inside k_qrows (slot 0 idle); the
-    // wide path (and Q rows built in HBM) keeps k_zrows for its item kernel
-    if (eng->jit) return k == 2 || (k == 1 && eng->nitems && !g.fused);
-    return k != 1 || eng->nuses;
+    // the Q-global paths keep k_zrows for their item kernel, and run neither
+    // without items; the direct path computes its Z rows inside k_qrows (slot
+    // 0 idle), the fused kernel its Q rows as well
+    const MdpStep none = MdpStep::None, zrows = eng->nitems ? MdpStep::Zrows : none;
+    const MdpStep items = !eng->nitems ? none : eng->path == MdpPath::WideHs ? MdpStep::ItemsAll : MdpStep::ItemsQ;
+    const MdpStep jit = eng->chunks.empty() ? MdpStep::FwdJit : MdpStep::FwdJitChunks;
+    auto set = [&](MdpStep s0, MdpStep s1, MdpStep s2) { g.step[0] = s0, g.step[1] = s1, g.step[2] = s2; };
+    switch (eng->path) {
+    case MdpPath::Generic: return set(MdpStep::Zpv, eng->nuses ? MdpStep::Coefs : none, MdpStep::FwdGeneric);
+    case MdpPath::Direct: return set(none, eng->nitems && !g.fused ? MdpStep::Qrows : none, jit);
+    case MdpPath::DirectQGlobal: return set(zrows, items, jit);
+    case MdpPath::WideHs: return set(zrows, items, MdpStep::FwdHs);
+    case MdpPath::WideMmt: return set(zrows, items, MdpStep::FwdMmt);
+    case MdpPath::WideMma: return set(zrows, items, MdpStep::FwdMma);
+    case MdpPath::WidePlain: return set(zrows, items, MdpStep::FwdPlain);
+    }
 }
 
 std::vector<std::string> mdp_plan_grid_kernels(const MdpEnginePlan *eng, const MdpGridPlan &g, uint32_t ne, uint32_t nc)
@@ -1398,33 +1414,39 @@ std::vector<std::string> mdp_plan_grid_kernels(const MdpEnginePlan *eng, const M
         names.insert(b);
     };
     auto witems = [&]() { for_nv(eng, [&](auto nv) { note(kFmtWitems, nv()); }); };
-    const bool qglobal = eng->wide || (eng->jit && eng->qglobal);
     for (int k = 0; k < 3 && ne && nc; ++k) {
-        if (!mdp_plan_slot_active(eng, g, k)) continue;
-        if (k == 0) {
-            names.insert(eng->jit || eng->wide ? "k_zrows" : "k_zpv");
-        } else if (k == 1 && qglobal) {
-            // k_fwd_hs: the item factors of every column in slot 1 when they fit one Pg block
-            if (!eng->hs || (g.wide_cb_items >= nc && eng->nitems)) witems();
-            if (!eng->hs) names.insert("k_wq");
-        } else if (k == 1 && eng->jit) {
-            for_qrows(eng, g.qrows_cb, [&](auto nv, auto ex, auto cb) { note(kFmtQrows, nv(), (int)ex(), cb()); });
-        } else if (k == 1) {
+        switch (g.step[k]) {
+        case MdpStep::None: break;
+        case MdpStep::Zpv: names.insert("k_zpv"); break;
+        case MdpStep::Coefs:
             for_coefs(eng, [&](auto ldsz, auto ldsp, auto nv) { note(kFmtCoefs, (int)ldsz(), (int)ldsp(), nv()); });
-        } else if (eng->wide && eng->hs) {
-            if (g.wide_cb_items < nc && eng->nitems) witems();
-            note(kFmtHs, eng->hs_rt, eng->hs_nb);
-        } else if (eng->wide && eng->mmt) {
-            note(kFmtMmt, eng->mmt_rt, eng->mmt_rows, mmt_shape(eng).db ? "2buf" : "1buf");
-        } else if (eng->wide && eng->mma) {
-            note(kFmtMma, eng->mma_npm);
-        } else if (eng->wide) {
-            names.insert("k_fwd_wide");
-        } else if (eng->jit && !eng->chunks.empty()) {
-            note(kFmtJitChunks, eng->maxA, eng->chunks.size(), eng->chunks[0].qidx.empty() ? "" : ",gather");
-        } else if (eng->jit) {
+            break;
+        case MdpStep::FwdGeneric: break;  // (left to its launcher)
+        case MdpStep::Zrows: names.insert("k_zrows"); break;
+        case MdpStep::Qrows:
+            for_qrows(eng, g.qrows_cb, [&](auto nv, auto ex, auto cb) { note(kFmtQrows, nv(), (int)ex(), cb()); });
+            break;
+        case MdpStep::ItemsQ:
+            witems();
+            names.insert("k_wq");
+            break;
+        case MdpStep::ItemsAll:
+            if (g.wide_cb_items >= nc) witems();
+            break;
+        case MdpStep::FwdJit:
             note(kFmtJit, g.fused ? "fused" : "reading", eng->maxA);
             if (g.tall) note(kFmtJitTall, kJitKblockTall);
+            break;
+        case MdpStep::FwdJitChunks:
+            note(kFmtJitChunks, eng->maxA, eng->chunks.size(), eng->chunks[0].qidx.empty() ? "" : ",gather");
+            break;
+        case MdpStep::FwdHs:
+            if (g.wide_cb_items < nc && eng->nitems) witems();
+            note(kFmtHs, eng->hs_rt, eng->hs_nb);
+            break;
+        case MdpStep::FwdMmt: note(kFmtMmt, eng->mmt_rt, eng->mmt_rows, mmt_shape(eng).db ? "2buf" : "1buf"); break;
+        case MdpStep::FwdMma: note(kFmtMma, eng->mma_npm); break;
+        case MdpStep::FwdPlain: names.insert("k_fwd_wide"); break;
         }
     }
     return std::vector<std::string>(names.begin(), names.end());
@@ -1552,7 +1574,9 @@ int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, Md
     const bool offline_check = mode == MdpPlanMode::OfflineCheck;
     auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     eng->lds_max = lds_max;
-    int rc = build_plan(eng, p);
+    // the path is decided in these locals and assigned once, at the end
+    bool wide = false, jit = false, qglobal = false;
+    int rc = build_plan(eng, p, wide);
     if (rc) return rc;
     eng->fwd_lds_bytes = ldR_of(eng) * sizeof(double) + (eng->prog.size() + 1) * sizeof(uint32_t);
     eng->fwd_lds = eng->fwd_lds_bytes <= kFwdLds;
@@ -1575,16 +1599,16 @@ int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, Md
         uint32_t vlds_max_uses = kVldsMaxUses;
         if (const char *mv = eng->opts.get("MDP_VLDS_MAXUSES")) vlds_max_uses = (uint32_t)std::max(0, atoi(mv));
         const uint32_t vkb = kBlock;  // points per workgroup (their states: npmax x vkb doubles of LDS)
-        if (eng->wide && !wide_forced && !jit_off && eng->npmax <= kVldsMaxStates && eng->nuses <= vlds_max_uses) {
-            eng->wide = false;
+        if (wide && !wide_forced && !jit_off && eng->npmax <= kVldsMaxStates && eng->nuses <= vlds_max_uses) {
+            wide = false;
             vlds = true;
         }
-        const bool want = !eng->wide && !jit_off;
+        const bool want = !wide && !jit_off;
         bool want_jit = want && build_direct_plan(eng, p) == MDP_OK;
         // k_qrows keeps every table of its c values in LDS; larger problems
         // build their Q rows in HBM (k_zrows + k_witems + k_wq, the same bits)
         const char *qg = eng->opts.get("MDP_QGLOBAL");
-        eng->qglobal = want_jit && (qrows_lds(eng, 1) > kQrowsLdsMax || (qg && atoi(qg) != 0));
+        qglobal = want_jit && (qrows_lds(eng, 1) > kQrowsLdsMax || (qg && atoi(qg) != 0));
         eng->ldQ = ((size_t)eng->ncoef_d + 1) & ~(size_t)1;
         // a series longer than kJitMaxUses uses (or a Q row past the LDS) runs
         // as chunks of years (MDP_JIT_CHUNK / MDP_JIT_GATHER force them)
@@ -1679,7 +1703,7 @@ int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, Md
                 if (!r)
                     mdp_set_error(MDP_ENODEV, "no HIP device available (forward kernels compiled; %zu chunks%s; "
                                   "nj %u nitems %u ldQ %zu qglobal %d)", eng->chunks.size(), gather ? ", gathered Q" : "",
-                                  plan.nj, plan.nitems, (size_t)plan.ldQ, (int)eng->qglobal);
+                                  plan.nj, plan.nitems, (size_t)plan.ldQ, (int)qglobal);
                 return r ? r : MDP_ENODEV;
             }
             if (offline_check) {
@@ -1700,29 +1724,30 @@ int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, Md
             // fused kernel wherever its tables fit: every grid of at most one
             // e block per column takes it), the other on demand (set_grid_dev's jit_load)
             const bool fused_first = eng->fused_mode == 1 ||
-                                     (eng->fused_mode == -1 && !vlds && !eng->qglobal &&
+                                     (eng->fused_mode == -1 && !vlds && !qglobal &&
                                       fused_lds(eng, plan.ct_max) <= kFusedLdsMax);
             if (jit_t) jit_t[0] = st_now();
             const int jrc = mode == MdpPlanMode::TablesOnly ? MDP_OK
                             : chunked                       ? jit_build_chunks(eng)
                                                             : jit_build(eng, fused_first);
             if (jit_t) jit_t[1] = st_now();
-            if (jrc == MDP_OK) eng->jit = true;
+            if (jrc == MDP_OK) jit = true;
             else fprintf(stderr, "midaspom: hipRTC specialisation failed, using the %s kernels:\n%s\n",
                          vlds ? "wide" : "generic", eng->jit_log.c_str());
         }
-        if (vlds && !eng->jit) {  // no specialised kernel after all: the wide kernels take the problem
-            eng->wide = true;
-            eng->qglobal = false;
+        if (vlds && !jit) {  // no specialised kernel after all: the wide kernels take the problem
+            wide = true;
             eng->chunks.clear();
         } else if (vlds) {
             eng->variant = (eng->npmax <= 32 ? 32u : eng->npmax <= 64 ? 64u : 128u) * 100u + eng->deg;
         }
     }
-    if (eng->wide) {
-        if ((rc = build_wide_plan(eng, p))) return rc;
+    MdpPath path = !jit ? MdpPath::Generic : qglobal ? MdpPath::DirectQGlobal : MdpPath::Direct;
+    if (wide) {
+        if ((rc = build_wide_plan(eng, p, path))) return rc;
         if (offline_check) return mdp_set_error(MDP_ENODEV, "no HIP device available (wide path planned)");
     }
+    eng->path = path;
     return MDP_OK;
 }
 
@@ -1736,7 +1761,7 @@ void mdp_plan_info(const MdpEnginePlan *eng, int n_devices, mdp_engine_info *inf
     info->nuses = eng->nuses;
     info->ncoef = eng->ncoef;
     info->npmax = eng->npmax;
-    info->variant = eng->variant + (eng->jit ? 10000u : 0u);
+    info->variant = eng->variant + (path_is_jit(eng->path) ? 10000u : 0u);
 }
 
 void mdp_plan_work(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double *flop_impl, double *flop_survey,
@@ -1749,8 +1774,15 @@ void mdp_plan_work(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double *f
     const double D = (double)eng->deg;
     double per_pt = (double)eng->nuses * (2.0 * (D + 1.0) + 2.0) + 3.0 * (D + 1.0) +
                     2.0 * (double)eng->npmax;
-    if (eng->jit) per_pt = eng->jit_flops_pt;  // the generated code's own count
-    if (eng->wide) per_pt = eng->hs ? eng->hs_flops_pt : eng->mmt ? eng->mmt_flops_pt : eng->wide_flops_pt;
+    switch (eng->path) {
+    case MdpPath::Generic: break;
+    case MdpPath::Direct:
+    case MdpPath::DirectQGlobal: per_pt = eng->jit_flops_pt; break;  // the generated code's own count
+    case MdpPath::WideHs: per_pt = eng->hs_flops_pt; break;
+    case MdpPath::WideMmt: per_pt = eng->mmt_flops_pt; break;
+    case MdpPath::WideMma:
+    case MdpPath::WidePlain: per_pt = eng->wide_flops_pt; break;
+    }
     if (flop_impl) *flop_impl = per_pt * pts;
     // SURVEY.md §8(d) F_alg (dense-in-j formulation)
     double fwd = 0;
@@ -1761,7 +1793,7 @@ void mdp_plan_work(const MdpEnginePlan *eng, uint64_t ne, uint64_t nc, double *f
     // compulsory bytes of k_forward: its coefficient stream once per c, the
     // e values, the output
     if (bytes_min)
-        *bytes_min = 8.0 * ((double)nc * (eng->jit || eng->wide ? eng->ldQ : ldR_of(eng)) + (double)ne + pts);
+        *bytes_min = 8.0 * ((double)nc * (eng->path != MdpPath::Generic ? eng->ldQ : ldR_of(eng)) + (double)ne + pts);
 }
 
 // cmax: the bound the device's c tables hold for (< 0: none yet); ns of nall:
