@@ -1,9 +1,11 @@
 // midaspom_amd/csrc/spom_engine.h -- internal to the posterior engine (not
 // installed; the public ABI is include/midaspom.h).  Shared by
-//   spom_plan.cpp    host planning: options, plan tables, the engine's path
-//                    (MdpPath), hipRTC sources, and per grid the c tables and
-//                    the grid plan (each slot's step, MdpStep, kernel variant,
-//                    point list, chunk widths, buffer sizes, launch shape)
+//   spom_plan.cpp    host planning: the options (parsed once into MdpOpts,
+//                    every later reader takes a field), plan tables, the
+//                    engine's path (MdpPath), hipRTC sources, and per grid the
+//                    c tables and the grid plan (each slot's step, MdpStep,
+//                    kernel variant, point list, chunk widths, buffer sizes,
+//                    launch shape)
 //   spom_engine.hip  the kernels; the engine (the plan plus its device contexts
 //                    and run-time state); device set-up, uploads and launches
 //                    as the plans say; timing
@@ -18,7 +20,7 @@
 
 #include <cstddef>
 #include <cstdint>
-#include <map>
+#include <optional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -163,13 +165,32 @@ struct MdpGridPlan {
     bool fwd_listed = false;    // the kernel reads plist / elist
 };
 
-struct EngineOpts {
-    std::map<std::string, std::string> kv;
-    const char *get(const char *name) const
-    {
-        auto it = kv.find(name);
-        return it == kv.end() ? nullptr : it->second.c_str();
-    }
+// The options of mdp_engine_create_opts as given, each converted once by
+// parse_engine_opts (its table, spom_plan.cpp, defines what a value means).  An
+// empty optional: the option was not given, and the default stays where it is
+// (MdpEnginePlan's and MdpJitPlan's initialisers, the planner's constants).
+// What depends on the plan (nb, the chunk count, vlds) is applied where the
+// field is read.
+struct MdpOpts {
+    bool jit = true;          // MDP_JIT: false for the value "0" alone
+    bool wide = false;        // MDP_WIDE
+    bool fwd_scalar = false;  // MDP_FWD=scalar (case-sensitive)
+    bool qglobal = false, gather = false, jit_check = false, jit_verbose = false;
+    // MDP_EPL as written: k_forward takes 1, 2 or 4 of it, the direct paths the number itself
+    std::optional<int> epl;
+    std::optional<bool> diag, fused, jit_xcd, jit_efast, qrows_xcd, fast_log, jit_split, jit_rot;
+    std::optional<int> fused_cols;   // 1 .. 4
+    std::optional<int> jit_slots, jit_wpe, jit_window, jit_hack, wide_mma, jit_threads;  // the number itself
+    std::optional<int> jit_kblock;   // 256 or 512
+    std::optional<uint32_t> jit_chunk;     // >= 1
+    std::optional<uint32_t> vlds_maxuses;  // >= 0
+    std::optional<int> vlds_epl;     // 1 or 2
+    std::optional<int> vsplit;       // 1, 2 or 4
+    std::optional<uint32_t> hs_radix;  // 1 .. kHsRadix
+    std::optional<uint32_t> hs_waves;  // 8 or 16
+    std::optional<uint32_t> hs_probe;  // 0 .. 7
+    std::optional<int> wide_cb;      // >= 1
+    std::optional<std::string> jit_dump;
 };
 
 // Everything the planner writes or reads of an engine.  The engine itself
@@ -256,7 +277,7 @@ struct MdpEnginePlan {
     size_t lds_max = 160 * 1024;  // the device's LDS per workgroup (mdp_plan_engine's argument; 160 KiB on gfx950)
     double prior0 = 1.0;
     std::vector<uint32_t> np, pairA, pairB, pairOff, use_pair, prog, udesc, pairPart0, partP, partK0;
-    EngineOpts opts;          // mdp_engine_create_opts (variant selection; no environment reads)
+    MdpOpts opts;             // mdp_engine_create_opts (variant selection; no environment reads)
 };
 
 // The forward kernels' output strides: log L of point (ie, ic) at
@@ -429,8 +450,10 @@ auto for_mma(const MdpEnginePlan *eng, F &&fn)
 // planner entry points (spom_plan.cpp)
 // ---------------------------------------------------------------------------
 
+// The options string into o (reset first), by the one table of names and
+// conversions; an unknown name is MDP_EINVAL, a value never is.
 // diag_build: the measurement-only names (MDP_DIAG, ...) are accepted
-int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build);
+int parse_engine_opts(const char *s, MdpOpts &o, bool diag_build);
 
 // How far mdp_plan_engine goes with hipRTC.
 enum class MdpPlanMode {

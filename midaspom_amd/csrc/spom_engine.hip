@@ -2991,7 +2991,7 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
     auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double st0 = st_now();
     double st_jit[2] = {st0, st0};  // around the hipRTC step (mdp_plan_engine)
-    EngineOpts opts;
+    MdpOpts opts;
     if (int orc = parse_engine_opts(options, opts, kDiagBuild)) return orc;
     if (p->n == 0 || p->tmax == 0 || !p->M || !p->year_off || !p->year_ids || !p->prior ||
         !p->short_state || (p->nvar && !p->var_cols))
@@ -3000,8 +3000,7 @@ int mdp_engine_create_opts(const mdp_problem *p, const int *devices, int n_devic
     // MDP_JIT_CHECK=1 without a device: plan and compile both forward
     // variants (hipRTC runs offline), then report MDP_ENODEV -- the CPU
     // test that the generated sources compile for gfx950
-    const char *jcheck = opts.get("MDP_JIT_CHECK");
-    const bool jit_check = jcheck && atoi(jcheck) != 0;
+    const bool jit_check = opts.jit_check;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         ndev = 0;
         if (!jit_check) return mdp_set_error(MDP_ENODEV, "no HIP device available");

@@ -1,6 +1,8 @@
 // midaspom_amd/csrc/spom_plan.cpp -- host planning of the posterior engine:
-// option parsing, the generic / direct / chunked / wide plan tables the
-// kernels index (spom_engine.h holds the shared constants), the hipRTC
+// option parsing (one table, kEngineOpts, converts every value once into a
+// field of MdpOpts; nothing after it reads option text), the engine plan as a
+// sequence of steps (mdp_plan_engine), the generic / direct / chunked / wide
+// plan tables the kernels index (spom_engine.h holds the shared constants), the hipRTC
 // forward sources, per grid the c tables and the grid plan (mdp_plan_grid:
 // the forward variant, the point list, the chunk widths, every buffer size
 // and the forward launch's shape) and the host-only part of the C ABI (work
@@ -33,31 +35,68 @@
 // libmidaspom_diag.so, used by scripts/): MDP_JIT_HACK's kernels do not
 // store correct results, and phase stamps / occupancy hints are profiling
 // aids.  An unknown name, or a measurement-only name in the default
-// build, is MDP_EINVAL.
+// build, is MDP_EINVAL.  A value is never refused: each row below converts
+// its text leniently (atoi: text that is no number is 0), a name without '='
+// has the value "1", and a repeated name takes its last value.
 namespace {
-const char *const kEngineOptNames[] = {
-    "MDP_JIT", "MDP_FUSED", "MDP_FUSED_COLS", "MDP_EPL", "MDP_JIT_SLOTS", "MDP_JIT_WINDOW", "MDP_JIT_XCD",
-    "MDP_JIT_EFAST", "MDP_QROWS_XCD", "MDP_FWD", "MDP_WIDE", "MDP_VSPLIT", "MDP_VLDS_EPL", "MDP_VLDS_MAXUSES",
-    "MDP_JIT_CHUNK", "MDP_JIT_GATHER", "MDP_QGLOBAL", "MDP_FAST_LOG", "MDP_JIT_KBLOCK", "MDP_WIDE_CB",
-    "MDP_JIT_CHECK", "MDP_JIT_DUMP", "MDP_JIT_THREADS", "MDP_JIT_VERBOSE", "MDP_JIT_SPLIT", "MDP_JIT_ROT",
-    "MDP_WIDE_MMA", "MDP_HS_RADIX", "MDP_HS_WAVES"};
-const char *const kDiagOptNames[] = {"MDP_DIAG", "MDP_JIT_HACK", "MDP_JIT_WPE", "MDP_HS_PROBE"};
+struct OptDef {
+    const char *name;
+    bool diag;  // measurement-only
+    void (*set)(MdpOpts &o, const char *v);
+};
+inline bool on(const char *v) { return atoi(v) != 0; }
+inline int clampi(int lo, int v, int hi) { return std::max(lo, std::min(hi, v)); }
+// The one list of the accepted names, with what each value means.
+const OptDef kEngineOpts[] = {
+    {"MDP_JIT", false, [](MdpOpts &o, const char *v) { o.jit = strcmp(v, "0") != 0; }},
+    {"MDP_WIDE", false, [](MdpOpts &o, const char *v) { o.wide = on(v); }},
+    {"MDP_FWD", false, [](MdpOpts &o, const char *v) { o.fwd_scalar = !strcmp(v, "scalar"); }},
+    {"MDP_EPL", false, [](MdpOpts &o, const char *v) { o.epl = atoi(v); }},
+    {"MDP_QGLOBAL", false, [](MdpOpts &o, const char *v) { o.qglobal = on(v); }},
+    {"MDP_JIT_GATHER", false, [](MdpOpts &o, const char *v) { o.gather = on(v); }},
+    {"MDP_JIT_CHECK", false, [](MdpOpts &o, const char *v) { o.jit_check = on(v); }},
+    {"MDP_JIT_VERBOSE", false, [](MdpOpts &o, const char *) { o.jit_verbose = true; }},
+    {"MDP_FUSED", false, [](MdpOpts &o, const char *v) { o.fused = on(v); }},
+    {"MDP_JIT_XCD", false, [](MdpOpts &o, const char *v) { o.jit_xcd = on(v); }},
+    {"MDP_JIT_EFAST", false, [](MdpOpts &o, const char *v) { o.jit_efast = on(v); }},
+    {"MDP_QROWS_XCD", false, [](MdpOpts &o, const char *v) { o.qrows_xcd = on(v); }},
+    {"MDP_FAST_LOG", false, [](MdpOpts &o, const char *v) { o.fast_log = on(v); }},
+    {"MDP_JIT_SPLIT", false, [](MdpOpts &o, const char *v) { o.jit_split = on(v); }},
+    {"MDP_JIT_ROT", false, [](MdpOpts &o, const char *v) { o.jit_rot = on(v); }},
+    {"MDP_FUSED_COLS", false, [](MdpOpts &o, const char *v) { o.fused_cols = clampi(1, atoi(v), 4); }},
+    {"MDP_JIT_SLOTS", false, [](MdpOpts &o, const char *v) { o.jit_slots = atoi(v); }},
+    {"MDP_JIT_WINDOW", false, [](MdpOpts &o, const char *v) { o.jit_window = atoi(v); }},
+    {"MDP_WIDE_MMA", false, [](MdpOpts &o, const char *v) { o.wide_mma = atoi(v); }},
+    {"MDP_JIT_THREADS", false, [](MdpOpts &o, const char *v) { o.jit_threads = atoi(v); }},
+    {"MDP_JIT_KBLOCK", false, [](MdpOpts &o, const char *v) { o.jit_kblock = atoi(v) == 512 ? 512 : 256; }},
+    {"MDP_JIT_CHUNK", false, [](MdpOpts &o, const char *v) { o.jit_chunk = (uint32_t)std::max(1, atoi(v)); }},
+    {"MDP_VLDS_MAXUSES", false, [](MdpOpts &o, const char *v) { o.vlds_maxuses = (uint32_t)std::max(0, atoi(v)); }},
+    {"MDP_VLDS_EPL", false, [](MdpOpts &o, const char *v) { o.vlds_epl = atoi(v) == 2 ? 2 : 1; }},
+    {"MDP_VSPLIT", false, [](MdpOpts &o, const char *v) { o.vsplit = atoi(v) == 1 ? 1 : atoi(v) == 2 ? 2 : 4; }},
+    {"MDP_HS_RADIX", false, [](MdpOpts &o, const char *v) { o.hs_radix = (uint32_t)clampi(1, atoi(v), (int)kHsRadix); }},
+    {"MDP_HS_WAVES", false, [](MdpOpts &o, const char *v) { o.hs_waves = atoi(v) == 8 ? 8u : 16u; }},
+    {"MDP_WIDE_CB", false, [](MdpOpts &o, const char *v) { o.wide_cb = std::max(1, atoi(v)); }},
+    {"MDP_JIT_DUMP", false, [](MdpOpts &o, const char *v) { o.jit_dump = v; }},
+    {"MDP_DIAG", true, [](MdpOpts &o, const char *v) { o.diag = on(v); }},
+    {"MDP_JIT_HACK", true, [](MdpOpts &o, const char *v) { o.jit_hack = atoi(v); }},
+    {"MDP_JIT_WPE", true, [](MdpOpts &o, const char *v) { o.jit_wpe = atoi(v); }},
+    {"MDP_HS_PROBE", true, [](MdpOpts &o, const char *v) { o.hs_probe = (uint32_t)atoi(v) & 7u; }},
+};
 }  // namespace
 
-int parse_engine_opts(const char *s, EngineOpts &o, bool diag_build)
+int parse_engine_opts(const char *s, MdpOpts &o, bool diag_build)
 {
-    o.kv.clear();
-    if (!s) return MDP_OK;
+    o = MdpOpts();
     return mdp_for_each_opt(s, [&](const std::string &k, const std::string &val, bool has) -> int {
-        bool known = false, diag = false;
-        for (const char *n : kEngineOptNames) known |= k == n;
-        for (const char *n : kDiagOptNames) diag |= k == n;
-        if (diag && !diag_build)
-            return mdp_set_error(MDP_EINVAL, "option %s is measurement-only (libmidaspom_diag.so, -DMDP_DIAG_BUILD)",
-                                 k.c_str());
-        if (!known && !diag) return mdp_set_error(MDP_EINVAL, "unknown engine option '%s'", k.c_str());
-        o.kv[k] = has ? val : std::string("1");
-        return MDP_OK;
+        for (const OptDef &d : kEngineOpts) {
+            if (k != d.name) continue;
+            if (d.diag && !diag_build)
+                return mdp_set_error(MDP_EINVAL, "option %s is measurement-only (libmidaspom_diag.so, -DMDP_DIAG_BUILD)",
+                                     k.c_str());
+            d.set(o, has ? val.c_str() : "1");
+            return MDP_OK;
+        }
+        return mdp_set_error(MDP_EINVAL, "unknown engine option '%s'", k.c_str());
     });
 }
 
@@ -99,7 +138,6 @@ int select_variant(MdpEnginePlan *eng, bool &wide)
 // which take neither.
 int build_plan(MdpEnginePlan *eng, const mdp_problem *p, bool &wide)
 {
-    wide = false;
     eng->n = p->n;
     eng->tmax = p->tmax;
     eng->nvar = p->nvar;
@@ -108,7 +146,7 @@ int build_plan(MdpEnginePlan *eng, const mdp_problem *p, bool &wide)
         return mdp_set_error(MDP_EUNSUPPORTED, "%u variable columns (engine limit 24)", p->nvar);
     eng->nstates = 1u << p->nvar;
     eng->prior0 = (double)p->prior[0];
-    if (const char *wv = eng->opts.get("MDP_WIDE")) wide = atoi(wv) != 0;
+    wide = eng->opts.wide;
     eng->np.resize(p->tmax);
     eng->npmax = 1;
     for (uint32_t t = 0; t < p->tmax; ++t) {
@@ -646,7 +684,7 @@ bool build_hs_plan(MdpEnginePlan *eng)
     // on the 256-state series, equal on the 128-state one, profiles/r06/hs),
     // else 16
     uint32_t nw = nb == 8 ? 8u : 16u;
-    if (const char *wv = eng->opts.get("MDP_HS_WAVES")) nw = atoi(wv) == 8 && nb == 8 ? 8u : 16u;
+    if (eng->opts.hs_waves) nw = *eng->opts.hs_waves == 8 && nb == 8 ? 8u : 16u;
     const uint32_t rt = nb == 8 ? (nw == 8 ? 2u : 4u) : nb == 9 ? 2u : 1u, pts = mmt_pts(rt);
     const uint32_t ncube = 1u << nb, tmaxit = ncube / 16 > nw ? ncube / 16 / nw : 1u, cw = 4 * mmt_u(rt);
     const uint32_t zero = eng->nitems;  // the Pg row's zero slot
@@ -654,8 +692,7 @@ bool build_hs_plan(MdpEnginePlan *eng)
     // patches per v Pe pass (MDP_HS_RADIX, 1 .. kHsRadix; default 4, the
     // measured best: profiles/r06/hs -- 1 024 cosets x points fill the block
     // in one sweep; 5 left half the threads idle on 1 024-state years)
-    uint32_t radix = kHsRadix;
-    if (const char *rv = eng->opts.get("MDP_HS_RADIX")) radix = std::min<uint32_t>(kHsRadix, std::max(1, atoi(rv)));
+    const uint32_t radix = eng->opts.hs_radix.value_or(kHsRadix);
     std::unordered_map<uint64_t, uint32_t> item;  // (j, B) -> item
     for (uint32_t js = 0; js < eng->nj; ++js)
         for (uint32_t i = eng->cj_item0[js]; i < eng->cj_item0[js + 1]; ++i)
@@ -912,7 +949,7 @@ bool build_hs_plan(MdpEnginePlan *eng)
     eng->hs_rt = rt;
     eng->hs_nb = nb;
     eng->hs_nw = nw;
-    if (const char *pv = eng->opts.get("MDP_HS_PROBE")) eng->hs_probe = (uint32_t)atoi(pv) & 7u;
+    if (eng->opts.hs_probe) eng->hs_probe = *eng->opts.hs_probe;
     return hs_lds(eng) <= eng->lds_max && eng->hs_kt.size() < (1u << 26);
 }
 
@@ -942,8 +979,7 @@ int build_wide_plan(MdpEnginePlan *eng, const mdp_problem *p, MdpPath &path)
     // else k_fwd_mmt); unset -> k_fwd_hs for years of more than 64 states,
     // else k_fwd_mmt (measured, profiles/r06/hs: k_fwd_hs 1.3x / 4.4x / 5.2x
     // / 5.8x faster on 128 / 256 / 512 / 1 024 states, 1.27x slower on 64)
-    const char *mv = eng->opts.get("MDP_WIDE_MMA");
-    const int mmode = mv ? atoi(mv) : (eng->npmax > 64 ? 3 : 2);
+    const int mmode = eng->opts.wide_mma.value_or(eng->npmax > 64 ? 3 : 2);
     if (mmode == 3 && build_hs_plan(eng)) path = MdpPath::WideHs;
     else if ((mmode == 2 || mmode == 3) && build_mmt_plan(eng)) path = MdpPath::WideMmt;
     if (eng->npmax <= 256 && eng->maxA <= 24) {
@@ -1288,8 +1324,7 @@ int mdp_plan_grid(const MdpEnginePlan *eng, MdpCTables &ct, const double *e, uin
             return mdp_set_error(MDP_EUNSUPPORTED, "%u explicit colonisation columns per row exceed the LDS of k_zrows",
                                  ct.kmax);
     }
-    const char *cv = qglobal ? eng->opts.get("MDP_WIDE_CB") : nullptr;
-    const int forced_cb = cv ? std::max(1, atoi(cv)) : 0;
+    const int forced_cb = qglobal ? eng->opts.wide_cb.value_or(0) : 0;
     const size_t most_c = std::max<size_t>(1, std::min<size_t>(nc, 65535));  // a launch's grid y
     if (path == MdpPath::WideHs) {  // k_fwd_hs reads the item factors of its columns: rows of nitems + 1 (zero slot)
         const size_t ldp = (size_t)eng->nitems + 1;
@@ -1495,8 +1530,8 @@ std::string jit_source(MdpEnginePlan *eng, int variant)
         eng->jit_pro_fused = (uint32_t)std::max(1, plan.pro);
     }
     eng->jit_flops_pt = plan.flops_pt;
-    if (const char *dump = eng->opts.get("MDP_JIT_DUMP")) {  // <path>.hip (reading) / <path>.fused.hip
-        if (FILE *f = fopen((std::string(dump) + (fused ? ".fused.hip" : ".hip")).c_str(), "w")) {
+    if (eng->opts.jit_dump) {  // <path>.hip (reading) / <path>.fused.hip
+        if (FILE *f = fopen((*eng->opts.jit_dump + (fused ? ".fused.hip" : ".hip")).c_str(), "w")) {
             fputs(src.c_str(), f);
             fclose(f);
         }
@@ -1530,8 +1565,8 @@ int jit_build_chunks(MdpEnginePlan *eng)
     for (size_t i = 0; i < nch; ++i) {
         srcs[i] = mdp_jit_forward_source(eng->chunks[i]);
         flops += eng->chunks[i].flops_pt;
-        if (const char *dump = eng->opts.get("MDP_JIT_DUMP"))
-            if (FILE *f = fopen((std::string(dump) + ".chunk" + std::to_string(i) + ".hip").c_str(), "w")) {
+        if (eng->opts.jit_dump)
+            if (FILE *f = fopen((*eng->opts.jit_dump + ".chunk" + std::to_string(i) + ".hip").c_str(), "w")) {
                 fputs(srcs[i].c_str(), f);
                 fclose(f);
             }
@@ -1539,8 +1574,8 @@ int jit_build_chunks(MdpEnginePlan *eng)
     {
         std::vector<std::thread> th;
         size_t nt = std::min<size_t>(8, nch);
-        if (const char *tv = eng->opts.get("MDP_JIT_THREADS")) nt = std::max<size_t>(1, std::min<size_t>(nch, atoi(tv)));
-        const bool verbose = eng->opts.get("MDP_JIT_VERBOSE") != nullptr;
+        if (eng->opts.jit_threads) nt = std::max<size_t>(1, std::min<size_t>(nch, *eng->opts.jit_threads));
+        const bool verbose = eng->opts.jit_verbose;
         for (size_t t = 0; t < nt; ++t)
             th.emplace_back([&, t]() {
                 for (size_t i = t; i < nch; i += nt) {
@@ -1566,186 +1601,214 @@ int jit_build_chunks(MdpEnginePlan *eng)
     return MDP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// mdp_plan_engine's steps
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kVldsBlock = kBlock;  // vlds: points per workgroup (their states: npmax x kVldsBlock doubles of LDS)
+
+// What the direct-path choice hands to the steps after it.
+struct DirectChoice {
+    bool vlds = false;      // years of 17-64 states on the specialised kernel, their state vectors in LDS
+    bool want_jit = false;  // the specialised kernel is wanted and the direct plan is built
+    bool qglobal = false;   // its Q rows are built in HBM
+    bool gather = false, chunked = false;  // the series runs as chunks of years (gather: each its own Q layout)
+    uint32_t chunk_uses = kJitChunkUses;   // target uses per chunk
+    size_t qlimit = 0;      // coefficients a forward kernel may stage
+};
+
+// an option that was given overrides what the plan holds
+template <typename T, typename U>
+void take(T &dst, const std::optional<U> &src)
+{
+    if (src) dst = (T)*src;
+}
+
+// Which direct plan, if any: builds it (build_direct_plan) and sets ldQ, also
+// when it is not wanted.  wide: in, the generic plan's verdict; out, cleared
+// when the vlds kernel takes the wide years.
+DirectChoice choose_direct(MdpEnginePlan *eng, const mdp_problem *p, bool &wide)
+{
+    const MdpOpts &o = eng->opts;
+    DirectChoice dc;
+    // years of 17-64 states: the specialised forward kernel with its
+    // state vectors in LDS (plan.vlds), unless the series is so long that
+    // hipRTC would take minutes; MDP_WIDE=1 forces the wide kernels
+    if (wide && !o.wide && o.jit && eng->npmax <= kVldsMaxStates &&
+        eng->nuses <= o.vlds_maxuses.value_or(kVldsMaxUses)) {
+        wide = false;
+        dc.vlds = true;
+    }
+    dc.want_jit = !wide && o.jit && build_direct_plan(eng, p) == MDP_OK;
+    // k_qrows keeps every table of its c values in LDS; larger problems
+    // build their Q rows in HBM (k_zrows + k_witems + k_wq, the same bits)
+    dc.qglobal = dc.want_jit && (qrows_lds(eng, 1) > kQrowsLdsMax || o.qglobal);
+    eng->ldQ = ((size_t)eng->ncoef_d + 1) & ~(size_t)1;
+    // a series longer than kJitMaxUses uses (or a Q row past the LDS) runs
+    // as chunks of years (MDP_JIT_CHUNK / MDP_JIT_GATHER force them)
+    dc.chunk_uses = o.jit_chunk.value_or(kJitChunkUses);
+    // coefficients a forward kernel may stage: what the LDS leaves beside
+    // the wide years' state vectors (npmax x 256 lanes) when they are there
+    // (halved: the forward kernel keeps each Q row twice, in stored and in
+    // reversed group order -- spom_jit.cpp, the ratio forms)
+    dc.qlimit = (dc.vlds ? std::min(kJitChunkQ, (kQrowsLdsMax - (size_t)eng->npmax * kVldsBlock * sizeof(double) - 2048) /
+                                                    sizeof(double))
+                         : kJitChunkQ) / 2;
+    dc.gather = eng->ldQ > dc.qlimit || o.gather;
+    dc.chunked = eng->nuses > kJitMaxUses || dc.gather || (o.jit_chunk && eng->nuses > dc.chunk_uses);
+    return dc;
+}
+
+// eng->jit_plan from the direct plan and the options: the generator's
+// switches, the series, the counts and the fused kernel's column-table layout.
+void fill_jit_plan(MdpEnginePlan *eng, bool vlds)
+{
+    const MdpOpts &o = eng->opts;
+    MdpJitPlan &plan = eng->jit_plan;
+    if (vlds) {  // the wide years' states in LDS: one point per lane, never fused
+        plan.vlds = true;
+        // points per lane: 1, or 2 (MDP_VLDS_EPL=2: 128 lanes per wave
+        // group, each Q read shared by two points)
+        plan.epl = o.vlds_epl.value_or(1);
+        plan.kblock = (int)kVldsBlock / plan.epl;
+        plan.window = 16;
+        eng->fused_mode = 0;
+        take(plan.vsplit, o.vsplit);
+    }
+    plan.np = eng->np;
+    plan.udesc = eng->udesc_d;
+    plan.ldQ = eng->ldQ;
+    plan.diag = eng->diag;
+    take(plan.slots, o.jit_slots);
+    take(plan.wpe, o.jit_wpe);
+    take(plan.xcd, o.jit_xcd);
+    take(plan.efast, o.jit_efast);
+    take(eng->qrows_xcd, o.qrows_xcd);
+    take(plan.epl, o.epl);
+    take(plan.window, o.jit_window);
+    take(eng->fused_mode, o.fused);
+    take(plan.fused_cols, o.fused_cols);
+    take(plan.hack, o.jit_hack);
+    take(plan.fast_log, o.fast_log);
+    if (!vlds) take(plan.kblock, o.jit_kblock);
+    eng->jit_shape_env = o.epl || (o.jit_kblock && !vlds);
+    take(plan.split_forms, o.jit_split);
+    take(plan.rot, o.jit_rot);
+    plan.nj = eng->nj;
+    plan.nvar = eng->nvar;
+    plan.nitems = eng->nitems;
+    plan.ncoef = eng->ncoef_d;
+    plan.nqi = (uint32_t)eng->qitem.size();
+    {   // zs rows compiled into the fused kernel: the longest row of
+        // explicit columns at |c| <= 1 (the default grid); a grid
+        // with more (|c| > 1) runs k_zrows + k_qrows instead
+        size_t kz = 0;
+        std::vector<double> large;
+        for (uint32_t js = 0; js < eng->nj; ++js) {
+            z_split(eng, js, 1.0, large, nullptr);
+            kz = std::max(kz, large.size());
+        }
+        plan.kzmax = (uint32_t)std::max<size_t>(8, (kz + 7) & ~(size_t)7);
+    }
+    plan.qmaxlen = 0;
+    for (size_t q = 0; q + 1 < eng->qstart.size(); ++q)
+        plan.qmaxlen = std::max(plan.qmaxlen, eng->qstart[q + 1] - eng->qstart[q]);
+    auto even = [](size_t v) { return (uint32_t)((v + 1) & ~(size_t)1); };
+    plan.off_it = even((size_t)eng->nj * eng->nvar);
+    plan.off_qs = even(plan.off_it + eng->nitems);
+    plan.off_qi = even(plan.off_qs + (eng->ncoef_d + 2) / 2);
+    plan.off_rq = even(plan.off_qi + (eng->qitem.size() + 1) / 2);
+    plan.off_zc = even(plan.off_rq + (eng->ldQ + 1) / 2);
+    plan.off_zs = even(plan.off_zc + (size_t)eng->nj * kZTerms);
+    // the largest image (kzmax >= 8 zs rows), and whether it fits the fused
+    // kernel's LDS: then the zs image is always zero-padded to it
+    const size_t ct_full = ((plan.off_zs + (size_t)plan.kzmax * eng->nj) + 127) & ~(size_t)127;
+    plan.ct_max = (uint32_t)std::min<size_t>(ct_full, kFusedLdsMax / sizeof(double));
+    plan.zpad = fused_lds(eng, ct_full) <= kFusedLdsMax;
+}
+
+// MDP_JIT_CHECK=1 without a device: compile every forward kernel of the plan,
+// then MDP_ENODEV with the plan's counts in the message.
+int report_offline(MdpEnginePlan *eng, const DirectChoice &dc)
+{
+    const MdpJitPlan &plan = eng->jit_plan;
+    if (dc.chunked) {
+        const int r = jit_build_chunks(eng);
+        if (!r)
+            mdp_set_error(MDP_ENODEV, "no HIP device available (forward kernels compiled; %zu chunks%s; "
+                          "nj %u nitems %u ldQ %zu qglobal %d)", eng->chunks.size(), dc.gather ? ", gathered Q" : "",
+                          plan.nj, plan.nitems, (size_t)plan.ldQ, (int)dc.qglobal);
+        return r ? r : MDP_ENODEV;
+    }
+    const int r0 = jit_build(eng, false), r1 = r0 ? r0 : jit_build(eng, true);
+    uint32_t ipr = 0;  // most items of one row
+    for (uint32_t js = 0; js + 1 < eng->cj_item0.size(); ++js)
+        ipr = std::max(ipr, eng->cj_item0[js + 1] - eng->cj_item0[js]);
+    if (!r1)
+        mdp_set_error(MDP_ENODEV,
+                      "no HIP device available (forward kernels compiled; nj %u nitems %u "
+                      "items/row %u ldQ %zu qitems %u qmaxlen %u kzmax %u qrows slots %u conflicts %u + %u fused LDS %zu)",
+                      plan.nj, plan.nitems, ipr, (size_t)plan.ldQ, plan.nqi, plan.qmaxlen, plan.kzmax,
+                      eng->npl_slots, eng->slot_conflicts, eng->slot_store_conflicts,
+                      fused_lds(eng, ((plan.off_zs + (size_t)plan.kzmax * eng->nj) + 127) & ~(size_t)127));
+    return r1 ? r1 : MDP_ENODEV;
+}
+
+// Compile now the variant the first grid most likely runs (the fused kernel
+// wherever its tables fit: every grid of at most one e block per column takes
+// it), the other on demand (set_grid_dev's jit_load).  False, with the log on
+// stderr: no specialised kernel, the generic or wide kernels take the problem.
+bool first_compile(MdpEnginePlan *eng, const DirectChoice &dc, MdpPlanMode mode, double *jit_t)
+{
+    auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const bool fused_first = eng->fused_mode == 1 || (eng->fused_mode == -1 && !dc.vlds && !dc.qglobal &&
+                                                      fused_lds(eng, eng->jit_plan.ct_max) <= kFusedLdsMax);
+    if (jit_t) jit_t[0] = st_now();
+    const int jrc = mode == MdpPlanMode::TablesOnly ? MDP_OK
+                    : dc.chunked                    ? jit_build_chunks(eng)
+                                                    : jit_build(eng, fused_first);
+    if (jit_t) jit_t[1] = st_now();
+    if (jrc != MDP_OK)
+        fprintf(stderr, "midaspom: hipRTC specialisation failed, using the %s kernels:\n%s\n", dc.vlds ? "wide" : "generic",
+                eng->jit_log.c_str());
+    return jrc == MDP_OK;
+}
+
+}  // namespace
+
 // The planning half of mdp_engine_create_opts (declared in spom_engine.h).  On
 // an error, and after an offline check (MDP_ENODEV with the counts in the
 // message), the caller deletes the engine.
 int mdp_plan_engine(MdpEnginePlan *eng, const mdp_problem *p, size_t lds_max, MdpPlanMode mode, double *jit_t)
 {
-    const bool offline_check = mode == MdpPlanMode::OfflineCheck;
-    auto st_now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const MdpOpts &o = eng->opts;
     eng->lds_max = lds_max;
     // the path is decided in these locals and assigned once, at the end
-    bool wide = false, jit = false, qglobal = false;
+    bool wide = false, jit = false;
     int rc = build_plan(eng, p, wide);
     if (rc) return rc;
     eng->fwd_lds_bytes = ldR_of(eng) * sizeof(double) + (eng->prog.size() + 1) * sizeof(uint32_t);
-    eng->fwd_lds = eng->fwd_lds_bytes <= kFwdLds;
-    if (const char *ev = eng->opts.get("MDP_FWD"))
-        if (!strcmp(ev, "scalar")) eng->fwd_lds = false;
-    if (const char *ev = eng->opts.get("MDP_EPL")) {
-        const int v = atoi(ev);
-        if (v == 1 || v == 2 || v == 4) eng->epl = v;
+    eng->fwd_lds = eng->fwd_lds_bytes <= kFwdLds && !o.fwd_scalar;
+    if (o.epl && (*o.epl == 1 || *o.epl == 2 || *o.epl == 4)) eng->epl = *o.epl;
+    take(eng->diag, o.diag);
+    const DirectChoice dc = choose_direct(eng, p, wide);
+    if (dc.want_jit && eng->nuses > 0) {
+        fill_jit_plan(eng, dc.vlds);
+        if (dc.chunked && (rc = plan_chunks(eng, dc.chunk_uses, dc.gather, dc.qlimit))) return rc;
+        if (mode == MdpPlanMode::OfflineCheck) return report_offline(eng, dc);
+        jit = first_compile(eng, dc, mode, jit_t);
     }
-    if (const char *ev = eng->opts.get("MDP_DIAG")) eng->diag = atoi(ev) != 0;
-    {
-        const char *jv = eng->opts.get("MDP_JIT");
-        const bool jit_off = jv && !strcmp(jv, "0");
-        // years of 17-64 states: the specialised forward kernel with its
-        // state vectors in LDS (plan.vlds), unless the series is so long that
-        // hipRTC would take minutes; MDP_WIDE=1 forces the wide kernels
-        const char *wv0 = eng->opts.get("MDP_WIDE");
-        const bool wide_forced = wv0 && atoi(wv0) != 0;
-        bool vlds = false;
-        uint32_t vlds_max_uses = kVldsMaxUses;
-        if (const char *mv = eng->opts.get("MDP_VLDS_MAXUSES")) vlds_max_uses = (uint32_t)std::max(0, atoi(mv));
-        const uint32_t vkb = kBlock;  // points per workgroup (their states: npmax x vkb doubles of LDS)
-        if (wide && !wide_forced && !jit_off && eng->npmax <= kVldsMaxStates && eng->nuses <= vlds_max_uses) {
-            wide = false;
-            vlds = true;
-        }
-        const bool want = !wide && !jit_off;
-        bool want_jit = want && build_direct_plan(eng, p) == MDP_OK;
-        // k_qrows keeps every table of its c values in LDS; larger problems
-        // build their Q rows in HBM (k_zrows + k_witems + k_wq, the same bits)
-        const char *qg = eng->opts.get("MDP_QGLOBAL");
-        qglobal = want_jit && (qrows_lds(eng, 1) > kQrowsLdsMax || (qg && atoi(qg) != 0));
-        eng->ldQ = ((size_t)eng->ncoef_d + 1) & ~(size_t)1;
-        // a series longer than kJitMaxUses uses (or a Q row past the LDS) runs
-        // as chunks of years (MDP_JIT_CHUNK / MDP_JIT_GATHER force them)
-        uint32_t chunk_uses = kJitChunkUses;
-        const char *cv = eng->opts.get("MDP_JIT_CHUNK");
-        if (cv) chunk_uses = (uint32_t)std::max(1, atoi(cv));
-        const char *gv = eng->opts.get("MDP_JIT_GATHER");
-        // coefficients a forward kernel may stage: what the LDS leaves beside
-        // the wide years' state vectors (npmax x 256 lanes) when they are there
-        // (halved: the forward kernel keeps each Q row twice, in stored and in
-        // reversed group order -- spom_jit.cpp, the ratio forms)
-        const size_t qlimit = (vlds ? std::min(kJitChunkQ, (kQrowsLdsMax - (size_t)eng->npmax * vkb * sizeof(double) -
-                                                          2048) / sizeof(double))
-                                    : kJitChunkQ) / 2;
-        const bool gather = eng->ldQ > qlimit || (gv && atoi(gv) != 0);
-        const bool chunked = eng->nuses > kJitMaxUses || gather || (cv && eng->nuses > chunk_uses);
-        if (want_jit && eng->nuses > 0) {
-            MdpJitPlan &plan = eng->jit_plan;
-            if (vlds) {  // the wide years' states in LDS: one point per lane, never fused
-                plan.vlds = true;
-                // points per lane: 1, or 2 (MDP_VLDS_EPL=2: 128 lanes per wave
-                // group, each Q read shared by two points)
-                const char *ve = eng->opts.get("MDP_VLDS_EPL");
-                plan.epl = ve && atoi(ve) == 2 ? 2 : 1;
-                plan.kblock = (int)vkb / plan.epl;
-                plan.window = 16;
-                eng->fused_mode = 0;
-                if (const char *sv = eng->opts.get("MDP_VSPLIT")) plan.vsplit = atoi(sv) == 1 ? 1 : atoi(sv) == 2 ? 2 : 4;
-            }
-            plan.np = eng->np;
-            plan.udesc = eng->udesc_d;
-            plan.ldQ = eng->ldQ;
-            plan.diag = eng->diag;
-            if (const char *cv = eng->opts.get("MDP_JIT_SLOTS")) plan.slots = atoi(cv);
-            if (const char *wv = eng->opts.get("MDP_JIT_WPE")) plan.wpe = atoi(wv);
-            if (const char *xv = eng->opts.get("MDP_JIT_XCD")) plan.xcd = atoi(xv) != 0;
-            if (const char *fv2 = eng->opts.get("MDP_JIT_EFAST")) plan.efast = atoi(fv2) != 0;
-            if (const char *qx = eng->opts.get("MDP_QROWS_XCD")) eng->qrows_xcd = atoi(qx) != 0;
-            if (const char *ev = eng->opts.get("MDP_EPL")) {
-                plan.epl = atoi(ev);
-                eng->jit_shape_env = true;
-            }
-            if (const char *wv = eng->opts.get("MDP_JIT_WINDOW")) plan.window = atoi(wv);
-            // compile the variant a small grid uses now (the other on demand)
-            if (const char *fv = eng->opts.get("MDP_FUSED")) eng->fused_mode = atoi(fv) != 0;
-            if (const char *cv = eng->opts.get("MDP_FUSED_COLS")) plan.fused_cols = std::max(1, std::min(4, atoi(cv)));
-            if (const char *cv = eng->opts.get("MDP_JIT_HACK")) plan.hack = atoi(cv);
-            if (const char *cv = eng->opts.get("MDP_FAST_LOG")) plan.fast_log = atoi(cv) != 0;
-            if (const char *cv = eng->opts.get("MDP_JIT_KBLOCK"); cv && !vlds) {
-                plan.kblock = atoi(cv) == 512 ? 512 : 256;
-                eng->jit_shape_env = true;
-            }
-            plan.nj = eng->nj;
-            plan.nvar = eng->nvar;
-            plan.nitems = eng->nitems;
-            plan.ncoef = eng->ncoef_d;
-            plan.nqi = (uint32_t)eng->qitem.size();
-            {   // zs rows compiled into the fused kernel: the longest row of
-                // explicit columns at |c| <= 1 (the default grid); a grid
-                // with more (|c| > 1) runs k_zrows + k_qrows instead
-                size_t kz = 0;
-                std::vector<double> large;
-                for (uint32_t js = 0; js < eng->nj; ++js) {
-                    z_split(eng, js, 1.0, large, nullptr);
-                    kz = std::max(kz, large.size());
-                }
-                plan.kzmax = (uint32_t)std::max<size_t>(8, (kz + 7) & ~(size_t)7);
-            }
-            plan.qmaxlen = 0;
-            for (size_t q = 0; q + 1 < eng->qstart.size(); ++q)
-                plan.qmaxlen = std::max(plan.qmaxlen, eng->qstart[q + 1] - eng->qstart[q]);
-            auto even = [](size_t v) { return (uint32_t)((v + 1) & ~(size_t)1); };
-            if (const char *sv = eng->opts.get("MDP_JIT_SPLIT")) plan.split_forms = atoi(sv) != 0;
-            if (const char *sv = eng->opts.get("MDP_JIT_ROT")) plan.rot = atoi(sv) != 0;
-            {
-                plan.off_it = even((size_t)eng->nj * eng->nvar);
-                plan.off_qs = even(plan.off_it + eng->nitems);
-                plan.off_qi = even(plan.off_qs + (eng->ncoef_d + 2) / 2);
-                plan.off_rq = even(plan.off_qi + (eng->qitem.size() + 1) / 2);
-                plan.off_zc = even(plan.off_rq + (eng->ldQ + 1) / 2);
-                plan.off_zs = even(plan.off_zc + (size_t)eng->nj * kZTerms);
-                const size_t kmax_max = plan.kzmax;
-                plan.ct_max = (uint32_t)std::min<size_t>(((plan.off_zs + kmax_max * eng->nj) + 127) & ~(size_t)127,
-                                                         kFusedLdsMax / sizeof(double));
-                // zero-padded zs image when the largest one fits the fused kernel's LDS
-                const size_t kz = std::max<size_t>(8, kmax_max);
-                plan.zpad = fused_lds(eng, ((plan.off_zs + kz * eng->nj) + 127) & ~(size_t)127) <= kFusedLdsMax;
-            }
-            if (chunked && (rc = plan_chunks(eng, chunk_uses, gather, qlimit))) return rc;
-            if (offline_check && chunked) {
-                const int r = jit_build_chunks(eng);
-                if (!r)
-                    mdp_set_error(MDP_ENODEV, "no HIP device available (forward kernels compiled; %zu chunks%s; "
-                                  "nj %u nitems %u ldQ %zu qglobal %d)", eng->chunks.size(), gather ? ", gathered Q" : "",
-                                  plan.nj, plan.nitems, (size_t)plan.ldQ, (int)qglobal);
-                return r ? r : MDP_ENODEV;
-            }
-            if (offline_check) {
-                const int r0 = jit_build(eng, false), r1 = r0 ? r0 : jit_build(eng, true);
-                uint32_t ipr = 0;  // most items of one row
-                for (uint32_t js = 0; js + 1 < eng->cj_item0.size(); ++js)
-                    ipr = std::max(ipr, eng->cj_item0[js + 1] - eng->cj_item0[js]);
-                if (!r1)
-                    mdp_set_error(MDP_ENODEV,
-                                  "no HIP device available (forward kernels compiled; nj %u nitems %u "
-                                  "items/row %u ldQ %zu qitems %u qmaxlen %u kzmax %u qrows slots %u conflicts %u + %u fused LDS %zu)",
-                                  plan.nj, plan.nitems, ipr, (size_t)plan.ldQ, plan.nqi, plan.qmaxlen, plan.kzmax,
-                                  eng->npl_slots, eng->slot_conflicts, eng->slot_store_conflicts,
-                                  fused_lds(eng, ((plan.off_zs + (size_t)plan.kzmax * eng->nj) + 127) & ~(size_t)127));
-                return r1 ? r1 : MDP_ENODEV;
-            }
-            // compile now the variant the first grid most likely runs (the
-            // fused kernel wherever its tables fit: every grid of at most one
-            // e block per column takes it), the other on demand (set_grid_dev's jit_load)
-            const bool fused_first = eng->fused_mode == 1 ||
-                                     (eng->fused_mode == -1 && !vlds && !qglobal &&
-                                      fused_lds(eng, plan.ct_max) <= kFusedLdsMax);
-            if (jit_t) jit_t[0] = st_now();
-            const int jrc = mode == MdpPlanMode::TablesOnly ? MDP_OK
-                            : chunked                       ? jit_build_chunks(eng)
-                                                            : jit_build(eng, fused_first);
-            if (jit_t) jit_t[1] = st_now();
-            if (jrc == MDP_OK) jit = true;
-            else fprintf(stderr, "midaspom: hipRTC specialisation failed, using the %s kernels:\n%s\n",
-                         vlds ? "wide" : "generic", eng->jit_log.c_str());
-        }
-        if (vlds && !jit) {  // no specialised kernel after all: the wide kernels take the problem
-            wide = true;
-            eng->chunks.clear();
-        } else if (vlds) {
-            eng->variant = (eng->npmax <= 32 ? 32u : eng->npmax <= 64 ? 64u : 128u) * 100u + eng->deg;
-        }
+    if (dc.vlds && !jit) {  // no specialised kernel after all: the wide kernels take the problem
+        wide = true;
+        eng->chunks.clear();
+    } else if (dc.vlds) {
+        eng->variant = (eng->npmax <= 32 ? 32u : eng->npmax <= 64 ? 64u : 128u) * 100u + eng->deg;
     }
-    MdpPath path = !jit ? MdpPath::Generic : qglobal ? MdpPath::DirectQGlobal : MdpPath::Direct;
+    MdpPath path = !jit ? MdpPath::Generic : dc.qglobal ? MdpPath::DirectQGlobal : MdpPath::Direct;
     if (wide) {
         if ((rc = build_wide_plan(eng, p, path))) return rc;
-        if (offline_check) return mdp_set_error(MDP_ENODEV, "no HIP device available (wide path planned)");
+        if (mode == MdpPlanMode::OfflineCheck) return mdp_set_error(MDP_ENODEV, "no HIP device available (wide path planned)");
     }
     eng->path = path;
     return MDP_OK;

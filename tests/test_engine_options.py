@@ -231,3 +231,26 @@ def test_integration_option_table():
         if any(n in sentence for n in diag):
             assert "diag" in sentence, sentence
     assert "MDP_WIDE_MMA" in names and "k_fwd_mmt" in sec
+
+
+def test_design_option_table():
+    """DESIGN.md §4.4 names only options the default library accepts, the
+    scenario options, the three variables read from the environment (in a row
+    that says so) and the diag-only names (in a row that says diag)."""
+    import re
+    from midaspom_amd import _lib
+    text = (ROOT / "DESIGN.md").read_text()
+    sec = text[text.index("### 4.4 Engine options"):text.index("### 4.6 ")]
+    names = set(re.findall(r"MDP_[A-Z0-9_]+", sec))
+    accepted = set(_lib.ENGINE_OPTION_NAMES) - set(_lib.DIAG_OPTION_NAMES)
+    env_read = {"MDP_JIT_CACHE", "MDP_JIT_NOCACHE", "MDP_SETUP_TIMING"}
+    diag = set(_lib.DIAG_OPTION_NAMES)
+    unknown = names - accepted - set(_lib.SCENARIO_OPTION_NAMES) - env_read - diag
+    assert not unknown, f"DESIGN.md §4.4 names options the library does not accept: {sorted(unknown)}"
+    assert "mdp_engine_create_opts" in sec and "parse_engine_opts" in sec
+    for row in sec.splitlines():
+        named = set(re.findall(r"MDP_[A-Z0-9_]+", row))
+        if named & diag:
+            assert "diag" in row, row
+        if named & env_read:
+            assert "environment" in row, row

@@ -99,6 +99,41 @@ def test_option_variant_matches_oracle(golden, tmp_path, opts, prob):
         assert_loglik_close(got[ie, ic], om.loglik_points(e[ie], c[ic], threads=16))
 
 
+@pytest.fixture(scope="module")
+def generic_manual(golden):
+    """run(options) -> (log L of the manual example on a 4 x 4 grid, the launched kernels), each options string once."""
+    model = mdp.Model.load(golden / "manual_p3_obs.txt")
+    g = mdp.grid(4)[0]
+    done = {}
+
+    def run(options):
+        if options not in done:
+            with mdp.Engine(model, options=options) as eng:
+                done[options] = (eng.loglik_grid(g, g), eng.launched())
+        return done[options]
+    return run
+
+
+# The two values of the generic path that the host planner's driver cannot
+# see (tests/test_engine_option_values.py pins the others there).
+@pytest.mark.parametrize("opts", ["MDP_JIT=0;MDP_EPL=3",      # k_forward takes 1, 2 or 4 points per lane: 3 is ignored
+                                  "MDP_JIT=0;MDP_FWD=Scalar"])  # the value is case-sensitive: not "scalar"
+def test_generic_value_without_effect(generic_manual, opts):
+    ref, ref_kernels = generic_manual("MDP_JIT=0")
+    got, kernels = generic_manual(opts)
+    assert np.array_equal(got, ref)
+    assert kernels == ref_kernels
+
+
+def test_fwd_scalar_runs_k_forward(generic_manual):
+    ref, ref_kernels = generic_manual("MDP_JIT=0")
+    got, kernels = generic_manual("MDP_JIT=0;MDP_FWD=scalar")
+    assert any(k.startswith("k_forward_lds<") for k in ref_kernels), ref_kernels
+    assert any(k.startswith("k_forward<") for k in kernels), kernels
+    assert not any(k.startswith("k_forward_lds<") for k in kernels), kernels
+    assert_loglik_close(got, ref)
+
+
 def test_tooling_options_change_no_result(golden, tmp_path):
     f = golden / "config2_64x50.txt"
     e, c = mdp.grid(24)[0], mdp.grid(21)[0]
