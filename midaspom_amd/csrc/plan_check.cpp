@@ -1,7 +1,7 @@
 // midaspom_amd/csrc/plan_check.cpp -- the engine's host planner over one
 // problem, without a device or the HIP runtime:
 //   plan_check [--diag] [--sources] [--grid NE NC NCU [--e LO HI] [--c LO HI]
-//              [--cbound B] [--list]] OBSFILE M D "OPTIONS"
+//              [--cbound B] [--list] [--ztables]] OBSFILE M D "OPTIONS"
 // loads the observations (prior 0.5), parses the engine options, plans with
 // the 160 KiB LDS of gfx950 and generates the forward sources the plan would
 // compile (hipRTC is never called).  One line: the path taken, the counts of
@@ -24,6 +24,14 @@
 // with FNV-1a digests of the point list, its e values and each c table; a
 // refused grid is mdp_last_error() on stderr and exit 1.  --list adds the
 // point list itself (plist v v ...; bit 31 marks a padding duplicate).
+// --ztables adds the grid's Z-row tables (MdpCTables, z_split) after those:
+//   ztables nj <rows> kmax <kmax> cmax <%a>
+// and one line per row,
+//   zrow <row> bits <hidden state> nl <explicit columns> zs <patch>:<S %a> ...
+//        | zsq <%a> ... | zc <%a> x 8
+// zs: the row's kmax stored slots in order (the explicit "large" columns, the
+// largest S first, then the padding, patch "-"), zsq: k_qrows' chain-major copy
+// of the same slots, zc: the series coefficients P_i / i of the small columns.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -176,7 +184,7 @@ unsigned long long fnv(const std::vector<T> &v)
 }
 
 struct GridArgs {
-    bool on = false, list = false;
+    bool on = false, list = false, ztables = false;
     uint32_t ne = 0, nc = 0, ncu = 0;
     double e[2] = {0.0, 1.0}, c[2] = {0.0, 1.0}, cbound = 0.0;
 };
@@ -218,6 +226,25 @@ int grid_line(MdpEnginePlan *eng, const GridArgs &a)
         for (uint32_t v : g.plist) printf(" %u", v);
         printf("\n");
     }
+    if (a.ztables) {
+        const uint32_t nrows = ct.zc.empty() ? 0u : eng->nj;  // (the generic path builds no c tables)
+        printf("ztables nj %u kmax %u cmax %a\n", nrows, ct.kmax, ct.cmax);
+        std::vector<double> large;
+        std::vector<uint32_t> cols;
+        for (uint32_t js = 0; js < nrows; ++js) {
+            z_split(eng, js, ct.cmax, large, nullptr, &cols);  // (the patch of each stored column)
+            printf("zrow %u bits %u nl %zu zs", js, eng->cj_bits[js], large.size());
+            for (uint32_t k = 0; k < ct.kmax; ++k) {
+                if (k < cols.size()) printf(" %u:%a", cols[k], ct.zs[(size_t)js * ct.kmax + k]);
+                else printf(" -:%a", ct.zs[(size_t)js * ct.kmax + k]);
+            }
+            printf(" | zsq");
+            for (uint32_t k = 0; k < ct.kmax; ++k) printf(" %a", ct.zsq[(size_t)js * ct.kmax + k]);
+            printf(" | zc");
+            for (int i = 0; i < kZTerms; ++i) printf(" %a", ct.zc[(size_t)js * kZTerms + i]);
+            printf("\n");
+        }
+    }
     return 0;
 }
 
@@ -248,6 +275,7 @@ int main(int argc, char **argv)
         if (flag == "--diag") diag = true;
         else if (flag == "--sources") g_sources = true;
         else if (flag == "--list") grid.list = true;
+        else if (flag == "--ztables") grid.ztables = true;
         else if (flag == "--grid" && values(3, v)) grid.on = true, grid.ne = (uint32_t)v[0], grid.nc = (uint32_t)v[1], grid.ncu = (uint32_t)v[2];
         else if (flag == "--e" && values(2, grid.e)) continue;
         else if (flag == "--c" && values(2, grid.c)) continue;
@@ -256,7 +284,7 @@ int main(int argc, char **argv)
     }
     if (argc != 5) {
         fprintf(stderr, "usage: plan_check [--diag] [--sources] [--grid NE NC NCU [--e LO HI] [--c LO HI] [--cbound B] "
-                        "[--list]] OBSFILE M D \"OPTIONS\"\n");
+                        "[--list] [--ztables]] OBSFILE M D \"OPTIONS\"\n");
         return 2;
     }
     auto fail = []() {

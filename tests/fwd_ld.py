@@ -76,6 +76,33 @@ target year, |A_k| occupied patches in source state k, per year:
          (padded K entries add exact zeros): H = max_l 2^|B_l & W| k-steps,
          16 slice sums.   3 nv + 17 + H   (and no qsum; the kernel takes at
          most 10 variable patches, so this enters for nv <= 10 only).
+  zser   (every path but the generic one: k_zrows, k_qrows, the fused kernel)
+         For the grid's bound cmax (its largest c, or mdp_engine_set_cbound's
+         if larger) z_split (csrc/spom_plan.cpp) takes the always-zero columns
+         of a row with cmax S <= 2^-55 out of the product ("dropped") and
+         replaces those with 2^-55 < cmax S <= 2^-7 ("small", ns of them) by
+         exp(-A~), A = sum_i=1..8 c^i P_i / i, P_i = sum_small S^i.  Against
+         the reference's prod (1 - fl(c S)), in units of u:
+           A (ns + 16)   the argument: a coefficient P_i / i is ns additions,
+                         at most 7 multiplications and a division of
+                         non-negative terms (ns + 8), Horner's 7 FMAs and the
+                         product with c (8); a relative error r of the
+                         argument is A r in exp(-A);
+           sum_small p / (1 - p) / 2   the reference's own p = fl(c S), against
+                         the series of the exact c S (as for the fma, `item`);
+           sum_small (c S)^9 / (9 (1 - c S)) / u   the truncated tail of
+                         -log(1 - x) = sum x^i / i;
+           2 + 1         the device library's exp, 1 ulp = 2 u in double (the
+                         HIP programming guide's "HIP math API" table of
+                         double-precision functions; the toolchain installs no
+                         copy of it), and the product of Z with it;
+           nd / 4        nd dropped columns with S > 0, each factor within
+                         2^-55 = u / 4 of 1 (S = 0: the factor is exactly 1).
+         The largest such sum over the grid's c and the reachable rows (the
+         subsets of A & B of a transition), once per year on top of `item`,
+         whose count of explicit columns stays at all n: over-counted.  0
+         where no row has a small or a dropped column with S > 0 (every case
+         from before this term, asserted in tests/test_forward_ld.py).
 After the years the final sum, the prior and the final power: np_last + 18.
 Fused multiply-adds only remove roundings from these counts.  The reference's
 own error is the same count times 2^-64 (count / 2048 in units of u), and
@@ -157,15 +184,19 @@ def _inputs(shape, raw, m, p, d):
     return Inputs(n, nvar, tuple(var), M, S, float(pr), tuple(years), bits)
 
 
-def _pc(inp: Inputs, c: float, cols):
+def _pc(inp: Inputs, c: float, cols, z=None):
     """Dense Pc[j][B] for the target states `cols`, every hidden state j, in
-    long double from the double pressures."""
+    long double from the double pressures.  `z` (tests/test_forward_ld.py's
+    mutated series alone): z(c) -> [2^nvar] stands in for the product over the
+    always-zero patches."""
     p = np.minimum(1.0, c * inp.S).astype(LD)
     nj = 1 << inp.nvar
     Pc = np.ones((nj, len(cols)), dtype=LD)
     var = set(inp.var_cols)
+    if z is not None:
+        Pc *= np.asarray(z(c), dtype=LD)[:, None]
     for k in range(inp.n):
-        if k not in var:
+        if k not in var and z is None:
             Pc *= (LD(1) - p[:, k])[:, None]
     cols = np.asarray(cols, dtype=np.int64)
     for b, k in enumerate(inp.var_cols):
@@ -176,8 +207,8 @@ def _pc(inp: Inputs, c: float, cols):
     return Pc
 
 
-def grid(inp: Inputs, e, c) -> np.ndarray:
-    """L[ie][ic] in long double."""
+def grid(inp: Inputs, e, c, z=None) -> np.ndarray:
+    """L[ie][ic] in long double (`z`: _pc)."""
     e = np.atleast_1d(np.asarray(e, dtype=np.float64))
     c = np.atleast_1d(np.asarray(c, dtype=np.float64))
     x = np.minimum(e, 1.0).astype(LD)
@@ -196,7 +227,7 @@ def grid(inp: Inputs, e, c) -> np.ndarray:
                 V[hi] = y * V[hi]
             cols = list(inp.years[t])
             live = np.flatnonzero((V != 0).any(axis=1))  # (the other rows are exact zeros)
-            new = _pc(inp, float(cv), cols)[live].T @ V[live] if live.size else np.zeros((len(cols), e.size), LD)
+            new = _pc(inp, float(cv), cols, z)[live].T @ V[live] if live.size else np.zeros((len(cols), e.size), LD)
             V = np.zeros((nj, e.size), dtype=LD)
             V[cols] = new
         out[:, ic] = V.sum(axis=0) * LD(inp.prior0)
@@ -237,11 +268,75 @@ def kappa(inp: Inputs, c) -> float:
     return worst
 
 
-def roundings(inp: Inputs, c=()) -> float:
+Z_TAU = 2.0 ** -7     # z_split: cmax S above this stays an explicit factor
+Z_DROP = 2.0 ** -55   # z_split: cmax S up to this is dropped
+Z_TERMS = 8
+
+
+@functools.lru_cache(maxsize=None)
+def _reachable(years, nvar):
+    rows = set()
+    for t in range(1, len(years)):
+        for x in {a & b for a in years[t - 1] for b in years[t]}:
+            j = x
+            while True:  # every subset of x
+                rows.add(j)
+                if j == 0:
+                    break
+                j = (j - 1) & x
+    return tuple(sorted(rows))
+
+
+def reachable_rows(inp: Inputs) -> tuple:
+    """The hidden states j with a Pc[j][B] some transition reads: the subsets
+    of A & B (the engine's Z rows)."""
+    return _reachable(inp.years, inp.nvar)
+
+
+def nonvar_cols(inp: Inputs) -> list:
+    return [k for k in range(inp.n) if k not in inp.var_cols]
+
+
+def z_classes(inp: Inputs, cmax: float):
+    """z_split's classes restated: (rows, cols, x, small, large) with x =
+    fl(cmax S)[rows][cols] in double over the reachable rows and the
+    always-zero columns; dropped = neither small nor large."""
+    rows, cols = list(reachable_rows(inp)), nonvar_cols(inp)
+    x = float(cmax) * inp.S[np.ix_(rows, cols)] if rows and cols else np.zeros((len(rows), len(cols)))
+    small = (x > Z_DROP) & (x <= Z_TAU)
+    large = ~(x <= Z_DROP) & ~small
+    return rows, cols, x, small, large
+
+
+def zseries_term(inp: Inputs, c=(), cbound=0.0) -> float:
+    """`zser` of the module docstring, in units of u: the largest over the
+    grid's c values and the reachable rows."""
+    c = np.atleast_1d(np.asarray(c, dtype=np.float64))
+    if not c.size or not nonvar_cols(inp):
+        return 0.0
+    cmax = max(float(c.max()), float(cbound))
+    rows, cols, _, small, large = z_classes(inp, cmax)
+    S = inp.S[np.ix_(rows, cols)].astype(LD)
+    nd = ((S > 0) & ~small & ~large).sum(axis=1)
+    ns = small.sum(axis=1)
+    if not ns.any() and not nd.any():
+        return 0.0
+    worst = 0.0
+    for cv in c:
+        p = np.where(small, LD(float(cv)) * S, LD(0))   # < 2^-7 (1 + u)
+        A = sum((p ** i).sum(axis=1) / i for i in range(1, Z_TERMS + 1))
+        own = (p / (1 - p)).sum(axis=1) / 2
+        tail = (p ** (Z_TERMS + 1) / ((Z_TERMS + 1) * (1 - p))).sum(axis=1) / LD(U)
+        term = A * (ns + 16) + own + tail + np.where(ns > 0, 3, 0) + nd / LD(4)
+        worst = max(worst, float(term.max()))
+    return worst * (1 + 2.0 ** -40)   # (rounded up: the sums above are long double)
+
+
+def roundings(inp: Inputs, c=(), cbound=0.0) -> float:
     """The count of the module docstring, in units of u."""
     n, nv = inp.n, inp.nvar
     pc = [bin(s).count("1") for s in range(1 << nv)]
-    item = 2 * n + 4 + (n - nv) * kappa(inp, c) / 2
+    item = 2 * n + 4 + (n - nv) * kappa(inp, c) / 2 + zseries_term(inp, c, cbound)
     qsum = 7 + 2 * max(0, nv - 3)
     total, ops = 0.0, 0
     for t in range(1, len(inp.years)):
@@ -261,11 +356,12 @@ def roundings(inp: Inputs, c=()) -> float:
     return total * (1 + 1 / 2048) + math.ceil(ops / 2 ** 19)
 
 
-def bound(inp: Inputs, c=()) -> float:
+def bound(inp: Inputs, c=(), cbound=0.0) -> float:
     """A-priori relative error of L on any forward path against grid()
     (module docstring); `c` = the grid's c values (they enter through kappa
-    only)."""
-    return roundings(inp, c) * U
+    and zser), `cbound` = the engine's mdp_engine_set_cbound value if any: the
+    Z rows' classes are split at max(the grid's largest c, cbound)."""
+    return roundings(inp, c, cbound) * U
 
 
 def check(got_loglik, ref_L, bnd, what="", k_log=K_LOG_FAST) -> float:
@@ -371,6 +467,11 @@ class Case:
     m: float = 400.0
     p: float = 0.5
     d: float = 100.0
+    # None: no always-zero column is in the Z rows' series; a double: the case
+    # is built so that fl(cmax S) of one reachable (row, always-zero column)
+    # equals it (2^-7: the last small column; around 2^-55: the last dropped)
+    zedge: float | None = None
+    zprops: object = None   # (x, small, large) -> None: asserts the case's class mix (z_classes at cmax)
 
     @property
     def inp(self) -> Inputs:
@@ -386,8 +487,13 @@ class Case:
         r = reference(self.obs, self.m, self.p, self.d, self.e, self.c)
         assert 2 * (r >= L_NORMAL).sum() >= r.size, f"{self.name}: only {normal_fraction(r):.2f} of the cells are normal"
         assert self.bound <= 2e-12, f"{self.name}: bound {self.bound:.3e}"
-        # no always-zero patch in the Z rows' exp series (2^-55 < cmax S <= 2^-7)
-        assert float(self.c.max()) * math.exp(-(self.inp.n - 1) * self.d / self.m) > 2.0 ** -7
+        if self.zedge is None:
+            # no always-zero patch in the Z rows' exp series (2^-55 < cmax S <= 2^-7)
+            assert float(self.c.max()) * math.exp(-(self.inp.n - 1) * self.d / self.m) > 2.0 ** -7
+        else:
+            _, _, x, small, large = z_classes(self.inp, float(self.c.max()))
+            assert (x == self.zedge).any(), f"{self.name}: no reachable column with fl(cmax S) = {self.zedge!r}"
+            self.zprops(x, small, large)
         return r
 
 
@@ -427,6 +533,75 @@ def _series(occ, n):
     return obs
 
 
+def edge_c(inp: Inputs, value: float, order):
+    """(c, j, k): the largest double c with fl(c S[j][k]) == value exactly
+    (so the next double above c puts the product above value), for the first
+    reachable row j and always-zero column k in the order of the key
+    `order(S[j][k])` that has one (a nextafter search around value / S: the
+    products of neighbouring c values are S ulp(c) apart, which can step
+    over the one double `value`)."""
+    rows, cols = reachable_rows(inp), nonvar_cols(inp)
+    cand = sorted(((float(inp.S[j, k]), j, k) for j in rows for k in cols if inp.S[j, k] > 0), key=lambda t: order(t[0]))
+    for s, j, k in cand:
+        c = value / s
+        for _ in range(4):
+            c = float(np.nextafter(c, np.inf))
+        for _ in range(9):
+            if c * s == value:
+                return c, j, k
+            c = float(np.nextafter(c, 0.0))
+    raise AssertionError(f"no c with fl(c S) = {value!r}")
+
+
+def _obs_z(n, var, T, seed, missing, stay=0.8, col=0.15):
+    """T years x n patches, always zero outside the columns `var`; there a
+    patch stays occupied with probability `stay` and is colonised with `col`
+    (few colonisations: L stays far above 2^-950 at the small c of the flat
+    cases); `missing` = {year: unvisited variable patches}."""
+    rng = np.random.default_rng(seed)
+    obs = np.zeros((T, n), dtype=np.int32)
+    cur = rng.random(len(var)) < 0.7
+    cur[0] = True
+    for t in range(T):
+        obs[t, var] = cur
+        cur = np.where(cur, rng.random(len(var)) < stay, rng.random(len(var)) < col)
+    for yr, k in missing.items():
+        obs[yr, rng.choice(var, size=k, replace=False)] = -1
+    return obs
+
+
+def z_case(name, obs, m, d, value, order, zprops) -> Case:
+    """A case whose largest c puts one reachable (row, always-zero column)
+    at fl(cmax S) == value: c = cmax / 4, cmax / 2, the double below cmax and
+    cmax, on E12."""
+    obs = np.ascontiguousarray(obs, dtype=np.int32)
+    cmax, _, _ = edge_c(inputs(obs, m, 0.5, d), value, order)
+    c = np.array([cmax / 4, cmax / 2, np.nextafter(cmax, 0.0), cmax])
+    return Case(name, obs, E12, c, m, 0.5, d, zedge=value, zprops=zprops)
+
+
+def _z_steep(x, small, large):
+    # all three classes in one row, at most 8 explicit columns a row (kmax 8)
+    assert (small.any(axis=1) & large.any(axis=1) & (~small & ~large & (x > 0)).any(axis=1)).any()
+    assert large.sum(axis=1).max() <= 8 and small.sum(axis=1).max() >= 30
+
+
+def _z_all_small(x, small, large):
+    # every column of every occupied row small; the full row within 10 % of the threshold
+    assert not large.any() and (small == (x > 0)).all()
+    full = x[np.argmax(x.sum(axis=1))]
+    assert (full > 0.9 * Z_TAU).all() and (full <= Z_TAU).all()
+
+
+def _z_just_small(x, small, large):
+    # every column just above the drop threshold: small, within the rows' spread (<= 6 patches) of it
+    assert not large.any() and (small == (x > 0)).all() and small.any() and (x[small] <= 8 * Z_DROP).all()
+
+
+def _z_all_dropped(x, small, large):
+    assert not large.any() and not small.any() and (x > 0).any()
+
+
 @functools.lru_cache(maxsize=None)
 def cases() -> dict:
     from test_gpu_parity import _wide_obs
@@ -458,4 +633,24 @@ def cases() -> dict:
     a1 = out["a1"]
     e600 = np.sort(np.concatenate([E12, np.linspace(0.011, 0.989, 588)]))
     out["f600"] = Case("f600", a1.obs, e600, a1.c[[2, 4, 5]], a1.m, a1.p, a1.d)
+    # (z) the Z rows' series (module docstring, `zser`): 6 years each, up to
+    # 4 unvisited variable patches a year
+    miss = {0: 2, 1: 4, 3: 3, 4: 3, 5: 1}
+    # steep: 68 patches, the 8 variable ones in columns 20-27, S falls by e a
+    # column: up to 8 explicit columns a row (4 on either side), the small
+    # ones, and from 38 columns away (e^-38 cmax < 2^-55: a row of 48 patches
+    # would have none) dropped ones, in one row; cmax near 0.73, kappa < 1
+    steep = _obs_z(68, list(range(20, 28)), 6, 2401, miss, stay=0.75, col=0.3)
+    out["z-steep"] = z_case("z-steep", steep, 100.0, 100.0, Z_TAU, lambda s: abs(Z_TAU / s - 0.73), _z_steep)
+    # flat: 6 variable patches at one end, S within 10 % along the row; cmax =
+    # 2^-7 / max S: every column small and near the threshold (A = 0.26 at 34
+    # columns, 0.85 at 114)
+    flat = _obs_z(40, list(range(6)), 6, 2402, miss)
+    out["z-flat"] = z_case("z-flat", flat, 4000.0, 10.0, Z_TAU, lambda s: -s, _z_all_small)
+    wide = _obs_z(120, list(range(6)), 6, 2403, miss)
+    out["z-flat-wide"] = z_case("z-flat-wide", wide, 12000.0, 10.0, Z_TAU, lambda s: -s, _z_all_small)
+    # drop: the flat shape with the smallest S one double above 2^-55 (all
+    # small, A of the order of ns 2^-55), and with the largest at 2^-55 (all dropped)
+    out["z-drop"] = z_case("z-drop", flat, 4000.0, 10.0, float(np.nextafter(Z_DROP, 1.0)), lambda s: s, _z_just_small)
+    out["z-drop0"] = z_case("z-drop0", flat, 4000.0, 10.0, Z_DROP, lambda s: -s, _z_all_dropped)
     return out

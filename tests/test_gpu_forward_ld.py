@@ -30,6 +30,24 @@ chunked with gather and with Q rows from HBM alike; the one-year series
 0.014; a1 with the library log 0.151 of its smaller tolerance; two e blocks
 and 1, 2, 4 points per lane 0.091.  The bounds run from 2.9e-15 (one year) to
 7.3e-13 (the 1 024-state year).
+
+The Z rows' small-column series (section (z); fwd_ld's `zser` term in the
+bound), same device: z-steep 0.049 on every path, z-flat 0.063 on the eight
+paths with the series and 0.076 on the generic one (k_zpv multiplies the 34
+factors out: the control), Q rows from HBM and a chunked forward alike;
+z-flat-wide (114 small columns, argument 0.85) 0.057, z-drop 0.087 and z-drop0
+0.094 on the fused kernel, k_qrows + reading and k_zrows alike; z-steep under
+the six |c| bounds (kmax 8, 16, 16, 32, 40, 64) 0.049-0.050; z-flat on 512 /
+1 024 c values (k_qrows<8,0,2> / <8,0,4>) 0.074 / 0.070; k_zrows' block edges
+(130, 193 c values) 0.056, 0.057.  Bounds 9.9e-14 to 2.6e-13.  On these cells
+the 3.5 ulp of log L are about a tenth of the tolerance: the arithmetic's own
+error is far inside bound().  What the section can and cannot see: a series
+term k <= 6 gone or exchanged on any one implementation leaves the bound on
+z-flat (term 6, the weakest: 6.9 times the tolerance, tests/test_forward_ld.py);
+an error of less than about a seventh of P6 / 6 alone, and anything in terms
+7 and 8 (<= 3e-14 and 2e-16 of L), is below it -- the host table is held by
+tests/test_zsplit_host.py, and an exchange among coefficients 7 and 8 in one
+kernel shows only in test_series_fused_and_qrows_identical.
 """
 from __future__ import annotations
 
@@ -39,6 +57,7 @@ import pytest
 import midaspom_amd as mdp
 import fwd_ld
 from test_gpu_parity import engine_path, _wide_engine_run, launched_forward  # noqa: F401 (engine_path: a fixture)
+from test_zsplit_host import STEEP_BOUNDS, steep_bound
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not fwd_ld.OK, reason=fwd_ld.SKIP_REASON)]
 
@@ -68,9 +87,10 @@ def run(cs, monkeypatch, env=None):
         return got, eng.launched(), eng.info()
 
 
-def held(got, ref, cs, what, k_log=fwd_ld.K_LOG_FAST):
-    frac = fwd_ld.check(got, ref, cs.bound, what, k_log)
-    print(f"\n{what}: frac {frac:.3f} of the tolerance (bound {cs.bound:.3e}, {fwd_ld.normal_fraction(ref):.2f} normal)")
+def held(got, ref, cs, what, k_log=fwd_ld.K_LOG_FAST, bnd=None):
+    bnd = cs.bound if bnd is None else bnd
+    frac = fwd_ld.check(got, ref, bnd, what, k_log)
+    print(f"\n{what}: frac {frac:.3f} of the tolerance (bound {bnd:.3e}, {fwd_ld.normal_fraction(ref):.2f} normal)")
     return frac
 
 
@@ -83,8 +103,13 @@ def test_every_engine_path(name, engine_path, monkeypatch):
     always-zero patches: Z rows), 6 years of up to 16 states; a2: 9 patches,
     all variable, 5 years, p = 0.3, m = 250."""
     cs, ref = case(name)
-    model = model_of(cs)
     got, launched, info = run(cs, monkeypatch)
+    ran_on(engine_path, model_of(cs), launched, info)
+    held(got, ref, cs, f"{name} {engine_path} {sorted(launched)}")
+
+
+def ran_on(engine_path, model, launched, info):
+    """The kernels of the engine_path fixture's value ran."""
     if engine_path.startswith("wide"):
         assert info["variant"] >= 20000, info
         path = {"wide-plain": "wide-plain", "wide-hs": "wide-hs", "wide-hs-chunked": "wide-hs"}.get(engine_path, "wide")
@@ -96,7 +121,6 @@ def test_every_engine_path(name, engine_path, monkeypatch):
         assert any(k.startswith("mdp_fwd_jit<") for k in launched), launched
         if engine_path == "direct-qrows":
             assert any(k.startswith("k_qrows<") for k in launched) and "mdp_fwd_jit<fused" not in " ".join(launched), launched
-    held(got, ref, cs, f"{name} {engine_path} {sorted(launched)}")
 
 
 def test_clamp_on_an_always_zero_patch(monkeypatch):
@@ -285,3 +309,157 @@ def test_points_per_lane(epl, monkeypatch):
     got, launched, _ = run(cs, monkeypatch, {"MDP_EPL": epl})
     assert any(k.startswith("mdp_fwd_jit<") for k in launched), launched
     held(got, ref, cs, f"a1 epl {epl} {sorted(launched)}")
+
+
+# ---------------------------------------------------------------------------
+# (z) the Z rows' small-column series (fwd_ld's docstring, `zser`): every
+# implementation -- zseries in k_zrows, k_qrows' quad gather at 1, 2 and 4 c
+# values a workgroup, the fused kernel's Horner -- on cases whose columns sit
+# in the series, under the bound extended by its term
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["z-steep", "z-flat"])
+def test_series_on_every_engine_path(name, engine_path, monkeypatch):
+    """z-steep (68 patches: explicit, small and dropped columns in one row, a
+    column at fl(cmax S) = 2^-7) and z-flat (34 small columns within 10 % of
+    the threshold) on the nine paths: the fused kernel, the reading kernel
+    behind k_qrows, k_zrows behind k_witems for the mmt, plain and hs
+    forwards; the generic path (k_zpv: no series) is the control."""
+    cs, ref = case(name)
+    got, launched, info = run(cs, monkeypatch)
+    ran_on(engine_path, model_of(cs), launched, info)
+    if engine_path.startswith("wide"):
+        assert "k_zrows" in launched, launched
+    if engine_path == "direct":
+        assert any(k.startswith("mdp_fwd_jit<fused") for k in launched), launched
+    held(got, ref, cs, f"{name} {engine_path} {sorted(launched)}")
+
+
+@pytest.mark.parametrize("variant", ["qglobal", "chunks"])
+@pytest.mark.parametrize("name", ["z-steep", "z-flat"])
+def test_series_qglobal_and_chunked(name, variant, monkeypatch):
+    """Q rows built in HBM (k_zrows + k_witems + k_wq ahead of the reading
+    kernel) and a chunked forward behind k_qrows."""
+    cs, ref = case(name)
+    got, launched, _ = run(cs, monkeypatch, {"qglobal": {"MDP_QGLOBAL": "1"}, "chunks": {"MDP_JIT_CHUNK": "40"}}[variant])
+    names = " ".join(sorted(launched))
+    if variant == "qglobal":
+        assert {"k_zrows", "k_wq"} <= launched and "k_qrows<" not in names, launched
+    else:
+        assert "chunks" in names and "k_qrows<" in names, launched
+    held(got, ref, cs, f"{name} {variant} {sorted(launched)}")
+
+
+SERIES_ENV = {"fused": {"MDP_FUSED": "1"}, "reading": {"MDP_FUSED": "0"}, "wide": {"MDP_WIDE": "1"}}
+
+
+def _series_ran(variant, launched):
+    names = " ".join(sorted(launched))
+    if variant == "fused":
+        assert "mdp_fwd_jit<fused" in names, launched
+    elif variant == "reading":
+        assert "mdp_fwd_jit<reading" in names and "k_qrows<" in names, launched
+    else:
+        assert "k_zrows" in launched, launched
+
+
+@pytest.mark.parametrize("variant", list(SERIES_ENV))
+@pytest.mark.parametrize("name", ["z-flat-wide", "z-drop", "z-drop0"])
+def test_series_large_and_tiny_arguments(name, variant, monkeypatch):
+    """z-flat-wide: 114 small columns, a series argument of 0.85; z-drop:
+    every column one notch above 2^-55 (an argument of the order of 2^-50);
+    z-drop0: every column dropped (all coefficients zero: exp(0))."""
+    cs, ref = case(name)
+    got, launched, _ = run(cs, monkeypatch, SERIES_ENV[variant])
+    _series_ran(variant, launched)
+    held(got, ref, cs, f"{name} {variant} {sorted(launched)}")
+
+
+@pytest.mark.parametrize("which", list(STEEP_BOUNDS))
+def test_class_boundary_moves(which, monkeypatch):
+    """z-steep behind k_qrows under mdp_engine_set_cbound = cmax, the next
+    double (the threshold column turns explicit), 2 cmax, 2^14, 2^20 and a
+    bound that makes every column explicit: kmax 8, 16, 16, 32, 40, 64
+    (asserted on the host planner for these very bounds by tests/
+    test_zsplit_host.py::test_steep_kmax_under_a_bound; the engine reports no
+    kmax), so k_qrows' long-row loop (chain pairs past the first three) does
+    not run, runs without its trailing pair (32), with it (40) and twice
+    (64).  Each run within the bound of its own split."""
+    cs, ref = case("z-steep")
+    b = steep_bound(which)
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("MDP_FUSED", "0")
+    with mdp.Engine(model_of(cs)) as eng:
+        eng.set_cbound(b)
+        got = eng.loglik_grid(cs.e, cs.c)
+        launched = eng.launched()
+    _series_ran("reading", launched)
+    held(got, ref, cs, f"z-steep cbound {which} = {b!r} (kmax {STEEP_BOUNDS[which]})", bnd=fwd_ld.bound(cs.inp, cs.c, b))
+
+
+def _columns(nc, must, groups, seed):
+    """Sorted column indices: `must`, and `groups` whole groups of four
+    consecutive columns drawn with `seed`."""
+    rng = np.random.default_rng(seed)
+    g = rng.choice(np.arange(1, nc // 4 - 1), size=groups, replace=False)
+    return np.unique(np.concatenate([np.asarray(must), (4 * g[:, None] + np.arange(4)).ravel()]))
+
+
+@pytest.mark.parametrize("nc,cb", [(512, 2), (1024, 4)])
+def test_qrows_two_and_four_c_per_workgroup(nc, cb, monkeypatch):
+    """z-flat on 12 e values x 512 and 1 024 c values up to the case's cmax,
+    MDP_FUSED=0: k_qrows<8,0,2> and <8,0,4> (mdp_plan_grid's choice, asserted
+    on what ran), whose lanes gather the eight coefficients across a quad and
+    pick c per lane (cq at 4 c values).  The reference on 64 columns: the
+    first and the last group of four and 14 groups between, so every
+    position of a group."""
+    cs, _ = case("z-flat")
+    cmax = float(cs.c.max())
+    c = np.linspace(cmax / 4, cmax, nc)
+    assert c[-1] == cmax
+    idx = _columns(nc, [0, 1, 2, 3, nc - 4, nc - 3, nc - 2, nc - 1], 14, 2500 + cb)
+    assert idx.size == 64 and {int(i) % 4 for i in idx} == {0, 1, 2, 3}
+    ref = fwd_ld.reference(cs.obs, cs.m, cs.p, cs.d, cs.e, c[idx])
+    assert 2 * (ref >= fwd_ld.L_NORMAL).sum() >= ref.size
+    bnd = fwd_ld.bound(cs.inp, c[idx])   # (idx holds the last column, cmax: the engine's split)
+    assert bnd <= 2e-12
+    big = fwd_ld.Case(f"z-flat-{nc}", cs.obs, cs.e, c, cs.m, cs.p, cs.d)
+    got, launched, _ = run(big, monkeypatch, {"MDP_FUSED": "0"})
+    assert f"k_qrows<8,0,{cb}>" in launched, launched
+    held(got[:, idx], ref, big, f"z-flat {nc} c values {sorted(launched)}", bnd=bnd)
+
+
+@pytest.mark.parametrize("nc", [130, 193])
+def test_zrows_block_edges(nc, monkeypatch):
+    """z-steep under MDP_WIDE=1 on 130 and 193 c values: k_zrows takes 128 a
+    block (two per lane), so a second block in x with two live lanes in its
+    first slot, and with one live lane in its second.  The reference on the
+    columns at every edge."""
+    cs, _ = case("z-steep")
+    cmax = float(cs.c.max())
+    c = np.linspace(cmax / 4, cmax, nc)
+    assert c[-1] == cmax
+    idx = np.unique([0, 1, 62, 63, 64, 65, 126, 127, 128, 129, nc - 2, nc - 1] + ([190, 191, 192] if nc > 192 else []))
+    ref = fwd_ld.reference(cs.obs, cs.m, cs.p, cs.d, cs.e, c[idx])
+    assert 2 * (ref >= fwd_ld.L_NORMAL).sum() >= ref.size
+    bnd = fwd_ld.bound(cs.inp, c[idx])
+    assert bnd <= 2e-12
+    big = fwd_ld.Case(f"z-steep-{nc}", cs.obs, cs.e, c, cs.m, cs.p, cs.d)
+    got, launched, _ = run(big, monkeypatch, {"MDP_WIDE": "1"})
+    assert "k_zrows" in launched, launched
+    held(got[:, idx], ref, big, f"z-steep {nc} c values {sorted(launched)}", bnd=bnd)
+
+
+@pytest.mark.parametrize("name", ["z-steep", "z-flat"])
+def test_series_fused_and_qrows_identical(name, monkeypatch):
+    """The fused kernel's Horner and k_qrows' gathered one give the same
+    bits (the claim of test_gpu_parity's test_fused_and_qrows_identical, here
+    where the series carries Z).  The only test that can see an exchange
+    among coefficients 7 and 8 on one side: their terms move L by less than
+    any bound on it."""
+    cs, _ = case(name)
+    fused, lf, _ = run(cs, monkeypatch, SERIES_ENV["fused"])
+    reading, lr, _ = run(cs, monkeypatch, SERIES_ENV["reading"])
+    _series_ran("fused", lf)
+    _series_ran("reading", lr)
+    assert np.array_equal(fused, reading, equal_nan=True), np.argwhere(fused != reading)[:4].tolist()
